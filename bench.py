@@ -5,15 +5,17 @@ sequence (BASELINE.json configs[1]): HIP ray gather ->
 -> volume rendering -> losses -> backward -> (N>1: RCCL all-reduce of the flat gradient) -> fused Adam.  Frames shard
 data-parallel over ranks (weak scaling: 2048 rays per rank).  Prints ONE JSON line on rank 0.
 
-    python bench.py                          # cfg2, N = 1 (the driver's default run); adds "secondary" (cfg4, cfg4 + marcher, cfg5's loss
-                                             # stack: 20 steps each) and "psnr_at_2k" (the committed pooled record) to the same line
+    python bench.py                          # cfg2, N = 1: the headline line only (set-up, warm-up, the K timed steps)
+    python bench.py --full                   # the same, plus `kernels`, `roofline`, `cpu_baseline`, `parity_check`, "secondary" (cfg4,
+                                             # cfg4 + marcher, cfg5's loss stack: 20 steps each) and "psnr_at_2k" (the committed record)
     python bench.py --family hash            # BASELINE.json configs[3]: hash-grid encoding + shallow MLPs, same batch
     python bench.py --arithmetic fp32_mfma   # every GEMM on native fp32 MFMA (the independent, exact-fp32 arithmetic)
-    python bench.py --psnr --psnr-seeds 2    # "psnr_at_2k" measured now: HIP vs oracle at equal iterations (minutes per seed)
+    python bench.py --full --psnr            # "psnr_at_2k" measured now: HIP vs oracle at equal iterations (minutes per seed)
+    python bench.py --dump-outputs DIR       # also write what the last timed step computed as DIR/<name>.npy
 
 Timing protocol: W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides with NO per-stage
-timers (the headline `value`); then a separate short loop (--kernel-steps, default 20) with the per-stage HIP-event timers on
-fills `kernels` and `roofline`.
+timers (the headline `value`).  With --full, a separate short loop (--kernel-steps, default 20) with the per-stage HIP-event timers
+on then fills `kernels` and `roofline`.
 """
 import argparse
 import json
@@ -239,6 +241,23 @@ def lib_identity():
     return h, build
 
 
+DUMP_MAX_FLOATS = 1 << 22          # per array (16 MB of float32): the hash family's 12.2 M-entry vectors are sampled
+
+
+def dump_outputs(out_dir, stats, store):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files -- the loss statistics train_iteration returned, the
+    flat parameters after its Adam step and the flat gradient it applied.  A vector longer than DUMP_MAX_FLOATS is written as a fixed,
+    seeded sample of its entries (the same indices in every run), so that all files stay well under 64 MB."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, t in (("stats", stats), ("params", store.flat), ("grad", store.grad_flat)):
+        t = t.detach().reshape(-1).float().cpu()
+        if t.numel() > DUMP_MAX_FLOATS:
+            t = t[torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_FLOATS].sort().values]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -278,7 +297,14 @@ def main():
     ap.add_argument("--no-check-sync", action="store_true")
     ap.add_argument("--force-dist", action="store_true", help="TEST ONLY: initialise the process group even for one rank")
     ap.add_argument("--lib", type=str, default=None, help="DEVELOPMENT: another build of the library (scripts/build_variant.sh), for same-box A/Bs")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the per-stage timer loop (kernels, roofline), the all-reduce diagnostics (comm), "
+                         "cpu_baseline, parity_check, the secondary lines and psnr_at_2k (their --no-* / --psnr options apply here)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step computed (loss statistics, updated parameters, flat gradient) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.psnr and not args.full:
+        ap.error("--psnr is a measurement of --full: pass both")
 
     from dynhor_amd import launch
     if args.gpus > 1 and not launch.launched_by_torchrun():
@@ -361,19 +387,22 @@ def main():
             t = torch.tensor([dt], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        # second, short loop with the per-stage HIP-event timers on (on the launch stream): the `kernels` block and the roofline's
-        # launch duration -- kept out of the headline loop above
-        runner.renderer.timer.enabled = True
-        runner.renderer.timer.reset()
-        for _ in range(max(args.kernel_steps, 1)):
-            runner.train_iteration()
-        torch.cuda.synchronize()
-        runner.renderer.timer.enabled = False
-        kern = runner.renderer.timer.summary()
-        kern_steps = max(args.kernel_steps, 1)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, stats, runner.store)
+        kern, kern_steps = {}, max(args.kernel_steps, 1)
+        if args.full:
+            # second, short loop with the per-stage HIP-event timers on (on the launch stream): the `kernels` block and the roofline's
+            # launch duration -- kept out of the headline loop above
+            runner.renderer.timer.enabled = True
+            runner.renderer.timer.reset()
+            for _ in range(kern_steps):
+                runner.train_iteration()
+            torch.cuda.synchronize()
+            runner.renderer.timer.enabled = False
+            kern = runner.renderer.timer.summary()
 
         comm = None
-        if use_dist:
+        if use_dist and args.full:
             # self-diagnosis for the first real multi-GPU run: what the process group reports, and the cost of the one collective
             # on this path in isolation (the flat gradient bucket; 20 back-to-back all-reduces, HIP events)
             g = runner.store.grad_bucket()           # the very buffer the training loop reduces (same registered address)
@@ -462,6 +491,27 @@ def main():
                 return None, None
 
             if hash_family:
+                workload = (f"instant-nsr-pl-shaped hash-grid family (BASELINE.json configs[3]): 16-level x 2-feature hash grid (T = 2^19) + "
+                            f"1x64 geometry MLP with finite-difference normals + SH-4 2x64 colour MLP, custom_shoes-shaped synthetic seq, "
+                            f"512x512, {B} rays x " + ("(64+64) samples" if args.hash_sampler == "hierarchical" else
+                                                         "occupancy-grid marching (packed rays: fixed capacity of 128 samples per ray on average, "
+                                                         "per-ray cap up to 1024 chosen on the device)")
+                            + " per rank, full training iteration; 'LDS-resident grid tiles' of the config's wording: built (levels 0-1, the "
+                            "only ones that fit 160 KB), measured slower (0.48 vs 0.44 ms per forward), not shipped")
+                arithmetic = ("fp32 everywhere (VALU / fp32 MFMA for the small dW GEMMs); table gradient by "
+                              + ("2^-48 fixed-point integer atomics (bitwise reproducible)" if not args.float_atomic_table_grad else "float atomics"))
+            else:
+                workload = (f"custom_shoes-shaped synthetic seq, 512x512, {B} rays x (64+64) samples per rank, "
+                            "NeuS SDF(8x256, skip 4, softplus100) + colour(4x256) MLP, full training iteration")
+                arithmetic = {"fp32_mfma": "fp32 everywhere, every GEMM on v_mfma_f32_32x32x2_f32 (--arithmetic fp32_mfma)",
+                              "split_bf16": "fp32 in / fp32 out everywhere; GEMMs as 3-way bf16 split of both operands (6 MFMA "
+                                            "products, fp32 accumulate: 2^-24 relative = fp32 accuracy; --arithmetic split_bf16)",
+                              "split_f16": "fp32 in / fp32 out everywhere; GEMMs as 2-way fp16 split of both operands scaled by powers of two "
+                                           "(3 MFMA products, fp32 accumulate: fp32 accuracy, measured 1.9e-7 vs fp64 against 2.3e-7 for "
+                                           "the exact fp32 MFMA)"}[args.arithmetic]
+            if not args.full:
+                roof = None          # the per-stage timer loop did not run
+            elif hash_family:
                 # dominant stage of this family: the table-gradient scatter of dh_hash_weight_grads_parts (memory-side-atomic bound; the
                 # five small dW reductions of the same entry point run beside it on a second stream: hash_weight_grads_mlp).
                 # Algorithmic bytes per launch = every add the per-evaluation scatter defines (7 evaluations x 16 levels x 8 corners x
@@ -515,15 +565,6 @@ def main():
                     per_kernel["march"] = {"samples_per_ray_last_step": round(lm["samples_per_ray"], 2), "per_ray_cap": lm["per_ray_cap"],
                                            "rays_at_cap": lm["rays_at_cap"], "rays_truncated": lm["rays_truncated"],
                                            "capacity": lm["capacity"]}
-                workload = (f"instant-nsr-pl-shaped hash-grid family (BASELINE.json configs[3]): 16-level x 2-feature hash grid (T = 2^19) + "
-                            f"1x64 geometry MLP with finite-difference normals + SH-4 2x64 colour MLP, custom_shoes-shaped synthetic seq, "
-                            f"512x512, {B} rays x " + ("(64+64) samples" if args.hash_sampler == "hierarchical" else
-                                                         "occupancy-grid marching (packed rays: fixed capacity of 128 samples per ray on average, "
-                                                         "per-ray cap up to 1024 chosen on the device)")
-                            + " per rank, full training iteration; 'LDS-resident grid tiles' of the config's wording: built (levels 0-1, the "
-                            "only ones that fit 160 KB), measured slower (0.48 vs 0.44 ms per forward), not shipped")
-                arithmetic = ("fp32 everywhere (VALU / fp32 MFMA for the small dW GEMMs); table gradient by "
-                              + ("2^-48 fixed-point integer atomics (bitwise reproducible)" if not args.float_atomic_table_grad else "float atomics"))
             else:
                 names = _lib.STAGE_KERNELS[arith]
                 dom = max((k for k in per_kernel if per_kernel[k]["launches_per_step"] <= 1.01 and "tflops" in per_kernel[k]),
@@ -591,14 +632,6 @@ def main():
                              "whole_step_frac_of_fp32_mfma_peak": round(step_tf / FP32_MFMA_PEAK_TFLOPS, 4),
                              "whole_step_design_hbm_gbps": round(step_bytes / (ms * 1e-3) / 1e9, 1),
                              "whole_step_design_frac_of_hbm_peak": round(step_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)})
-                workload = (f"custom_shoes-shaped synthetic seq, 512x512, {B} rays x (64+64) samples per rank, "
-                            "NeuS SDF(8x256, skip 4, softplus100) + colour(4x256) MLP, full training iteration")
-                arithmetic = {"fp32_mfma": "fp32 everywhere, every GEMM on v_mfma_f32_32x32x2_f32 (--arithmetic fp32_mfma)",
-                              "split_bf16": "fp32 in / fp32 out everywhere; GEMMs as 3-way bf16 split of both operands (6 MFMA "
-                                            "products, fp32 accumulate: 2^-24 relative = fp32 accuracy; --arithmetic split_bf16)",
-                              "split_f16": "fp32 in / fp32 out everywhere; GEMMs as 2-way fp16 split of both operands scaled by powers of two "
-                                           "(3 MFMA products, fp32 accumulate: fp32 accuracy, measured 1.9e-7 vs fp64 against 2.3e-7 for "
-                                           "the exact fp32 MFMA)"}[args.arithmetic]
             # which matrix pipe ran: `dtype` is the I/O, accumulate and optimizer type
             mfma_dtype = ("f32 (v_mfma_f32_32x32x2_f32, small weight-gradient GEMMs only; the MLPs run on the vector ALU)" if hash_family else
                           {"split_f16": "f16 (2-piece split, 3 products per fp32 product, fp32 accumulate)",
@@ -613,18 +646,19 @@ def main():
                               "loss": "rgb L1 + 0.1 eikonal + 0.1 mask BCE + 0.05 mono-normal"
                                       + (" + 0.1 dense-correspondence reprojection (Huber 4 px) on 25 % of the rays" if full else ""),
                               "arithmetic": arithmetic},
-                   "roofline": roof, "kernels": per_kernel, "lib_sha16": lib_identity()[0], "build": lib_identity()[1],
+                   **({"roofline": roof, "kernels": per_kernel} if args.full else {}),
+                   "lib_sha16": lib_identity()[0], "build": lib_identity()[1],
                    "final_stats": {"loss": round(float(stats[0]), 5), "psnr": round(float(stats[5]), 3)}}
             if comm is not None:
                 out["comm"] = comm
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 frame = int(runner.image_perm[0])
                 g = torch.Generator(device=device); g.manual_seed(99)
                 n_cpu = args.cpu_rays if args.cpu_rays is not None else (128 if hash_family else 2048)
                 rays = runner.dataset.gen_random_rays_at(frame, n_cpu, generator=g)
                 out["cpu_baseline"] = cpu_baseline(rays, runner.dataset.R[frame], runner.renderer.n_samples,
                                                    runner.renderer.n_importance, runner.normal_weight, family=args.family)
-            if (world == 1 and not hash_family and not args.no_parity_check and args.rays_per_rank == 2048 and restore_stdout
+            if (args.full and world == 1 and not hash_family and not args.no_parity_check and args.rays_per_rank == 2048 and restore_stdout
                     and args.loss == "cfg2"):
                 # measured by THIS run, outside the timed region; last, because it replaces the runner's optimizer state
                 try:
@@ -650,7 +684,7 @@ def main():
 
     out = bench_line(args, True)
     if rank == 0:
-        if (world == 1 and args.family == 'neus' and args.loss == 'cfg2' and args.arithmetic == 'split_f16' and not args.no_secondary
+        if (args.full and world == 1 and args.family == 'neus' and args.loss == 'cfg2' and args.arithmetic == 'split_f16' and not args.no_secondary
                 and args.rays_per_rank == 2048):
             # the other configurations BASELINE.json names, made visible in the one line the driver records:
             # 20 steps each, same schema, no CPU baseline of their own
@@ -659,7 +693,7 @@ def main():
             for name, over in (('hash', dict(family='hash')), ('hash_occgrid', dict(family='hash', hash_sampler='occgrid')),
                                ('full_loss', dict(loss='full'))):
                 a2 = copy.copy(args)
-                a2.steps, a2.warmup, a2.kernel_steps, a2.no_cpu_baseline, a2.psnr = 20, 5, 10, True, False
+                a2.steps, a2.warmup, a2.kernel_steps, a2.no_cpu_baseline, a2.psnr, a2.dump_outputs = 20, 5, 10, True, False, None
                 for k, v in over.items():
                     setattr(a2, k, v)
                 try:

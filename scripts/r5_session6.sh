@@ -8,7 +8,7 @@ grep -h "float-atomic launches\|table gradient rel L2\|occupied .* of" $O/pytest
 for f in "" "--float-atomic-table-grad"; do   # (round 6: the flag that exists; the default IS the reproducible form)
   for smp in hierarchical occgrid; do
     tag=${smp}${f:+_float}
-    timeout 600 python3 bench.py --family hash --hash-sampler $smp $f --steps 100 --no-cpu-baseline --no-secondary > $O/bench_hash_$tag.json 2> $O/bench_hash_$tag.err
+    timeout 600 python3 bench.py --full --family hash --hash-sampler $smp $f --steps 100 --no-cpu-baseline --no-secondary > $O/bench_hash_$tag.json 2> $O/bench_hash_$tag.err
     python3 - $O/bench_hash_$tag.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

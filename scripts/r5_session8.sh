@@ -8,7 +8,7 @@ for rep in 1 2; do
  for smp in hierarchical occgrid; do
   for f in "" "--serial-weight-grads"; do
     tag=${smp}${f:+_serial}_$rep
-    timeout 600 python3 bench.py --family hash --hash-sampler $smp $f --steps 100 --no-cpu-baseline --no-secondary > $O/bench_hash_$tag.json 2> $O/bench_hash_$tag.err
+    timeout 600 python3 bench.py --full --family hash --hash-sampler $smp $f --steps 100 --no-cpu-baseline --no-secondary > $O/bench_hash_$tag.json 2> $O/bench_hash_$tag.err
     python3 - $O/bench_hash_$tag.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -24,6 +24,6 @@ cp gpurun_out/prof_summary.json gpurun_out/${R}_hash_pmc_summary.json
 cp $(ls -t gpurun_out/keep/*_kernel_stats.csv | head -1) gpurun_out/${R}_hash_kernel_stats.csv
 python3 scripts/make_traffic_json.py gpurun_out/${R}_hash_pmc_summary.json gpurun_out/pmc_traffic_hash.json hash > $O/traffic_hash.log 2>&1; tail -3 $O/traffic_hash.log
 cp gpurun_out/pmc_traffic_hash.json profiles/
-python3 bench.py --family hash > gpurun_out/${R}_bench_n1_hash.json 2> gpurun_out/bench_hash.err
-python3 bench.py --family hash --hash-sampler occgrid --no-cpu-baseline --no-secondary > gpurun_out/${R}_bench_n1_hash_occgrid.json 2> gpurun_out/bench_hash_occ.err
-for f in ${R}_bench_n1_hash ${R}_bench_n1_hash_occgrid; do echo "== $f"; head -c 330 gpurun_out/$f.json; echo; done
+python3 bench.py --full --family hash > $O/${R}_bench_n1_hash.json 2> $O/bench_hash.err
+python3 bench.py --full --family hash --hash-sampler occgrid --no-cpu-baseline --no-secondary > $O/${R}_bench_n1_hash_occgrid.json 2> $O/bench_hash_occ.err
+for f in ${R}_bench_n1_hash ${R}_bench_n1_hash_occgrid; do echo "== $f"; head -c 330 $O/$f.json; echo; done

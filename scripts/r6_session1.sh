@@ -7,8 +7,8 @@ O=gpurun_out/r6s1; mkdir -p $O
 timeout 900 python3 -m pytest tests/test_gpu_hash_reproducible.py tests/test_gpu_hash_family.py tests/test_gpu_hashgrid.py tests/test_gpu_occgrid.py -x -q -s > $O/pytest_hash.log 2>&1; tail -5 $O/pytest_hash.log
 grep -h "target \|float-atomic launches\|table gradient rel L2" $O/pytest_hash.log
 for rpr in 2048 256; do
-  timeout 300 python3 bench.py --rays-per-rank $rpr --no-secondary --no-cpu-baseline > $O/r06_bench_n1_rpr$rpr.json 2> $O/bench_rpr$rpr.err
-  timeout 300 python3 bench.py --rays-per-rank $rpr --no-secondary --no-cpu-baseline --force-dist --backend nccl > $O/r06_bench_n1_rpr${rpr}_rccl_1rank.json 2> $O/bench_rpr${rpr}_rccl.err
+  timeout 300 python3 bench.py --full --rays-per-rank $rpr --no-secondary --no-cpu-baseline > $O/r06_bench_n1_rpr$rpr.json 2> $O/bench_rpr$rpr.err
+  timeout 300 python3 bench.py --full --rays-per-rank $rpr --no-secondary --no-cpu-baseline --force-dist --backend nccl > $O/r06_bench_n1_rpr${rpr}_rccl_1rank.json 2> $O/bench_rpr${rpr}_rccl.err
 done
 python3 - <<'PY'
 import json, glob

@@ -9,7 +9,7 @@ timeout 600 python3 -m pytest tests/test_gpu_golden_replay.py -x -q -s > $O/pyte
 timeout 900 python3 -m pytest tests/test_gpu_hash_reproducible.py tests/test_gpu_hash_family.py tests/test_gpu_hashgrid.py tests/test_gpu_occgrid.py -q -s > $O/pytest_hash.log 2>&1; tail -5 $O/pytest_hash.log
 grep -h "target \|float-atomic launches\|table gradient rel L2" $O/pytest_hash.log
 timeout 600 python3 scripts/hash_grad_noise.py --iters 0,500,2000 --out $O/hash_grad_noise.json > $O/hash_grad_noise.log 2>&1; grep "^iter" $O/hash_grad_noise.log
-timeout 400 python3 bench.py --no-secondary --no-cpu-baseline > $O/bench.json 2> $O/bench.err; python3 - <<'PY'
+timeout 400 python3 bench.py --full --no-secondary --no-cpu-baseline > $O/bench.json 2> $O/bench.err; python3 - <<'PY'
 import json
 try:
     d = json.loads(open("gpurun_out/r6s2/bench.json").read().strip().splitlines()[-1])

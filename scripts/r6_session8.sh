@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 O=gpurun_out/r6s8; mkdir -p $O
 timeout 1500 python3 -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; tail -6 $O/pytest_gpu.log
-timeout 400 python3 bench.py --no-secondary --no-cpu-baseline > $O/bench.json 2> $O/bench.err; python3 - <<'PY'
+timeout 400 python3 bench.py --full --no-secondary --no-cpu-baseline > $O/bench.json 2> $O/bench.err; python3 - <<'PY'
 import json
 try:
     d = json.loads(open("gpurun_out/r6s8/bench.json").read().strip().splitlines()[-1])

@@ -124,8 +124,8 @@ def _build():
         procs.append(subprocess.Popen(["hipcc"] + flags + ["-c", s, "-o", o]))
     for p in procs:
         assert p.wait() == 0, "sanitizer build failed"
-    subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-fsanitize=address,undefined", "-shared-libsan",
-                           "-o", LIB] + objs)
+    subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
+                           "-shared-libsan", "-o", LIB] + objs)
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")

@@ -30,7 +30,7 @@ def _run(cmd, timeout=420):
 
 def test_single_rank_rccl_allreduce_runs():
     p = _run([sys.executable, "bench.py", "--gpus", "1", "--force-dist", "--backend", "nccl", "--steps", "3", "--warmup", "1",
-              "--frames", "8", "--no-cpu-baseline"])
+              "--frames", "8", "--no-cpu-baseline", "--full"])
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), "stdout is ONE JSON line (RCCL's version banner must not land in it): " + p.stdout[:400]
     out = json.loads(lines[0])
@@ -45,7 +45,7 @@ def test_single_rank_rccl_allreduce_runs():
 def test_bench_starts_its_own_two_ranks():
     """The driver's command form: no torch.distributed.run on the command line."""
     p = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--kernel-steps", "2", "--frames", "8",
-              "--backend", "gloo", "--share-gpu", "--no-cpu-baseline"])
+              "--backend", "gloo", "--share-gpu", "--no-cpu-baseline", "--full"])
     assert "check-sync ok" in p.stderr, "at N > 1 the parameter / frame check runs by default (VERDICT r3 next #6)"
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line (rank 0's) must reach the parent's stdout"
@@ -146,7 +146,7 @@ def test_hash_family_table_gradient_allreduce_overlaps_and_equals_the_serial_pat
 
 def test_bench_reports_two_collectives_for_the_hash_family():
     p = _run([sys.executable, "bench.py", "--gpus", "2", "--family", "hash", "--steps", "3", "--warmup", "1", "--kernel-steps", "2",
-              "--frames", "8", "--backend", "gloo", "--share-gpu", "--no-cpu-baseline"])
+              "--frames", "8", "--backend", "gloo", "--share-gpu", "--no-cpu-baseline", "--full"])
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     comm = out["comm"]
     assert comm["collectives_per_step"] == 2 and sum(comm["collective_bytes"].values()) == 12206065 * 4
