@@ -85,6 +85,8 @@ SIGNATURES = {
     "dh_render_scan_bwd_packed": (_i32, [_vp] * 7 + [_f32, _f32, _vp, _i64] + [_vp] * 13),
     "dh_neus_loss": (_i32, [_vp] * 6 + [_i64, _f32, _f32, _f32] + [_vp] * 6),
     "dh_corr_loss": (_i32, [_vp] * 7 + [_i32, _vp, _i64, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "dh_nearest_sqdist_workspace": (_i64, [_i64, _i64]),
+    "dh_nearest_sqdist": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -564,4 +564,18 @@ int dh_hash_weight_grads_parts(const float* params, const float* packed, int64_t
     return launch_hash_weight_grads(params, packed, n, ws, grad, n_active, parts, static_cast<hipStream_t>(stream));
 }
 
+int64_t dh_nearest_sqdist_workspace(int64_t nq, int64_t nr) {
+    if (nq < 0 || nr < 0) return DH_ERR_BAD_ARG;
+    return nearest_sqdist_workspace(nq, nr);
+}
+
+int dh_nearest_sqdist(const float* q, int64_t nq, const float* ref, int64_t nr, float* d2, int32_t* idx, void* ws, void* stream) {
+    if (nq < 0 || nr < 0) return DH_ERR_BAD_ARG;
+    if (nr >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;               // indices are int32
+    if (nq == 0) return DH_OK;
+    if (!q || !ref || !d2 || nr == 0 || misaligned16(ws)) return DH_ERR_BAD_ARG;
+    if (nq > ((int64_t)1 << 40)) return DH_ERR_UNSUPPORTED;                // grid.x = nq / 2048 must fit 2^31
+    return launch_nearest_sqdist(q, nq, ref, nr, d2, idx, ws, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -152,4 +152,8 @@ int launch_hash_geo_bwd(const float* params, const float* hp, const float* pts, 
 int launch_hash_weight_grads(const float* params, const float* hp, int64_t n, float* ws, float* grad, const int64_t* n_act,
                              int parts, hipStream_t st);
 
+// exact nearest-neighbour squared distance (nn.hip): ws = nearest_sqdist_workspace(nq, nr) bytes for the slab-split path, or null
+int64_t nearest_sqdist_workspace(int64_t nq, int64_t nr);
+int launch_nearest_sqdist(const float* q, int64_t nq, const float* ref, int64_t nr, float* d2, int32_t* idx, void* ws, hipStream_t st);
+
 }  // namespace dh

@@ -2,6 +2,7 @@
 
     python -m dynhor_amd.run --config_path configs/synthetic.yaml                 # one GPU
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --gpus 8        # frames shard 8-way data-parallel (RCCL)
+    python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode evaluate_mesh --is_continue   # Chamfer / F-score, one JSON line
 
 With --gpus N > 1 this process starts N ranks (one per GPU) through dynhor_amd.launch before it touches the GPU and exits
 with their code; under an external `torch.distributed.run` (WORLD_SIZE set) it is one of the ranks.
@@ -14,13 +15,18 @@ import sys
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config_path", type=str, required=True)
-    ap.add_argument("--mode", type=str, default="train", choices=["train", "validate_image", "validate_mesh"])
+    ap.add_argument("--mode", type=str, default="train", choices=["train", "validate_image", "validate_mesh", "evaluate_mesh"])
     ap.add_argument("--is_continue", action="store_true")
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks on this node (one process per GPU)")
     ap.add_argument("--backend", type=str, default="nccl", help="torch.distributed backend (nccl == RCCL; gloo for tests)")
     ap.add_argument("--share-gpu", action="store_true", help="TEST ONLY: every rank uses cuda:0 (with --backend gloo)")
     ap.add_argument("--exp_root", type=str, default="exps")
+    # evaluate_mesh only (defaults: the config's eval: block, else the analytic scene of a synthetic sequence, resolution 512)
+    ap.add_argument("--gt_mesh", type=str, default=None, help="evaluate_mesh: ground-truth mesh (.obj / .ply)")
+    ap.add_argument("--gt_normalize", type=str, default=None, choices=["none", "reference"],
+                    help="evaluate_mesh: 'reference' = bring the ground truth into the canonical frame (mean 0, max vertex norm 0.5)")
+    ap.add_argument("--mesh_resolution", type=int, default=None, help="evaluate_mesh: marching-cubes grid of the reconstruction")
     args = ap.parse_args()
 
     from . import launch
@@ -51,6 +57,11 @@ def main():
             print(f"trained to iteration {runner.iter_step} on {world} rank(s)", flush=True)
     elif args.mode == "validate_image":
         print("psnr", runner.validate_image())
+    elif args.mode == "evaluate_mesh":
+        res = runner.evaluate_mesh(gt_mesh=args.gt_mesh, gt_normalize=args.gt_normalize, resolution=args.mesh_resolution)
+        if runner.rank == 0:
+            import json
+            print(json.dumps(res), flush=True)
     else:
         print("surface crossings", runner.validate_mesh()[1])
     if world > 1:

@@ -420,6 +420,74 @@ class Runner:
             write_ply(os.path.join(d, "{:0>8d}.ply".format(self.iter_step)), verts, faces)
         return verts, faces
 
+    @torch.no_grad()
+    def evaluate_mesh(self, gt_mesh=None, gt_normalize=None, resolution=None, n_samples=None, taus=None, seed=0, save=True,
+                      gt_resolution=None):
+        """Geometry metrics of the current reconstruction against a ground-truth surface (dynhor_amd/metrics.py: Chamfer distance,
+        F-score, normal consistency; definitions in its docstring).  The mesh is extracted as validate_mesh does (renderer
+        extract_geometry over the object bounding box, model.mesh_method) at `resolution`, then scored by metrics.mesh_metrics.
+
+        Ground truth: the mesh file `gt_mesh` (.obj / .ply), in the canonical frame (gt_normalize "none") or brought into it as the
+        reference normalises its shape prior (gt_normalize "reference": metrics.normalize_like_reference; the result then carries
+        gt_scale).  Without one, a synthetic dataset's true surface is the zero level set of scene.scene_sdf, extracted by marching
+        cubes at gt_resolution over [-0.55, 0.55]^3; any other dataset raises ValueError.  Arguments left at None take the YAML's
+        optional `eval:` block (gt_mesh, gt_normalize, resolution, gt_resolution, n_samples, taus), else 512 / 1,000,000 /
+        (0.005, 0.01, 0.02).  data_info.obj_path is NOT ground truth (the reference's stage-1 shape prior) and is never used.
+        Rank 0 writes meshes/<iter:08d>_eval.json and logs every number as eval/<key> to <exp>/board.  Returns the dict."""
+        from . import metrics
+        ev = self.conf.get("eval") or {}
+        pick = lambda v, key, default: v if v is not None else (ev.get(key) if ev.get(key) is not None else default)
+        gt_mesh = pick(gt_mesh, "gt_mesh", None)
+        gt_normalize = pick(gt_normalize, "gt_normalize", "none")
+        resolution = int(pick(resolution, "resolution", 512))
+        gt_resolution = int(pick(gt_resolution, "gt_resolution", 512))
+        n_samples = int(pick(n_samples, "n_samples", 1_000_000))
+        taus = tuple(float(t) for t in pick(taus, "taus", (0.005, 0.01, 0.02)))
+        if gt_mesh is not None:
+            gt_v, gt_f = metrics.load_mesh(gt_mesh)
+            gt_name = str(gt_mesh)
+        elif getattr(self.dataset, "synthetic", False):
+            gt_v, gt_f = self._scene_gt_mesh(gt_resolution)
+            gt_name = f"scene_sdf@{gt_resolution}"
+            gt_normalize = "none"                      # the analytic scene is defined in the canonical frame
+        else:
+            raise ValueError("evaluate_mesh: no ground truth -- pass gt_mesh (or set eval.gt_mesh in the config); only a synthetic "
+                             "dataset has one built in")
+        verts, faces = self.validate_mesh(resolution=resolution, save=False)
+        res = metrics.mesh_metrics(verts, faces, gt_v, gt_f, n_samples=n_samples, taus=taus, seed=seed, gt_normalize=gt_normalize,
+                                   device=self.device)
+        res.update(iter=self.iter_step, resolution=resolution, gt=gt_name)
+        if save and self.rank == 0:
+            d = os.path.join(self.base_exp_dir, "meshes")
+            os.makedirs(d, exist_ok=True)
+            with open(os.path.join(d, "{:0>8d}_eval.json".format(self.iter_step)), "w") as f:
+                json.dump(res, f, indent=1)
+            if self._board is None:
+                from .tb_events import make_writer
+                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+            for k, v in res.items():
+                if k != "iter" and isinstance(v, (int, float)):
+                    self._board.add_scalar("eval/" + k, float(v), self.iter_step)
+            self._board.flush()
+        return res
+
+    def _scene_gt_mesh(self, resolution, chunk=1 << 22):
+        """Zero level set of the synthetic scene's analytic SDF (scene.scene_sdf) by mesh.marching_cubes over [-0.55, 0.55]^3
+        (the object lies inside the radius-0.5 ball), the SDF evaluated on the device in chunks.  Cached per resolution."""
+        from .mesh import marching_cubes
+        from .scene import scene_sdf
+        cache = self.__dict__.setdefault("_gt_meshes", {})
+        if resolution not in cache:
+            N = int(resolution)
+            ax = torch.linspace(-0.55, 0.55, N, device=self.device)
+            u = torch.empty(N * N * N, device=self.device)
+            for s in range(0, N * N * N, chunk):
+                i = torch.arange(s, min(s + chunk, N * N * N), device=self.device)
+                p = torch.stack([ax[i // (N * N)], ax[(i // N) % N], ax[i % N]], dim=-1)
+                u[s:s + i.shape[0]] = -scene_sdf(p)
+            cache[resolution] = marching_cubes(u.view(N, N, N), 0.0, [-0.55] * 3, [0.55] * 3)
+        return cache[resolution]
+
 
 def _to_cpu(d):
     return {k: (_to_cpu(v) if isinstance(v, dict) else (v.detach().cpu() if torch.is_tensor(v) else v)) for k, v in d.items()}
