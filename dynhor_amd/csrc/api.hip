@@ -578,4 +578,30 @@ int dh_nearest_sqdist(const float* q, int64_t nq, const float* ref, int64_t nr, 
     return launch_nearest_sqdist(q, nq, ref, nr, d2, idx, ws, static_cast<hipStream_t>(stream));
 }
 
+int dh_label_dilate(const int8_t* label, int64_t n_frames, int H, int W, int radius, uint8_t* tmp, uint8_t* keep, void* stream) {
+    if (n_frames < 0 || H <= 0 || W <= 0 || radius < 0) return DH_ERR_BAD_ARG;
+    if (n_frames == 0) return DH_OK;
+    if (!label || !tmp || !keep) return DH_ERR_BAD_ARG;
+    if (n_frames * H >= ((int64_t)1 << 31) || W > 65535 * 256) return DH_ERR_UNSUPPORTED;   // grid (rows, column blocks)
+    const int r = radius < (H > W ? H : W) ? radius : (H > W ? H : W);                       // a wider window adds nothing
+    return launch_label_dilate(label, n_frames, H, W, r, tmp, keep, static_cast<hipStream_t>(stream));
+}
+
+int dh_mesh_mask_votes(const float* verts, int64_t nv, const uint8_t* keep, const float* R, const float* T, const float* K,
+                       int64_t n_frames, int H, int W, int32_t* bg_votes, int32_t* seen, void* stream) {
+    if (nv < 0 || n_frames < 0 || H <= 0 || W <= 0) return DH_ERR_BAD_ARG;
+    if (nv == 0) return DH_OK;
+    if (!verts || !K || !bg_votes || !seen || (n_frames > 0 && (!keep || !R || !T))) return DH_ERR_BAD_ARG;
+    if (nv >= ((int64_t)1 << 40)) return DH_ERR_UNSUPPORTED;
+    return launch_mesh_mask_votes(verts, nv, keep, R, T, K, n_frames, H, W, bg_votes, seen, static_cast<hipStream_t>(stream));
+}
+
+int dh_mesh_components(const int64_t* faces, int64_t nf, int64_t nv, int32_t* labels, void* stream) {
+    if (nf < 0 || nv < 0) return DH_ERR_BAD_ARG;
+    if (nv >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;               // labels are int32
+    if (nv == 0) return DH_OK;
+    if (!labels || (nf > 0 && !faces)) return DH_ERR_BAD_ARG;
+    return launch_mesh_components(faces, nf, nv, labels, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

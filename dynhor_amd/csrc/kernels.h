@@ -156,4 +156,10 @@ int launch_hash_weight_grads(const float* params, const float* hp, int64_t n, fl
 int64_t nearest_sqdist_workspace(int64_t nq, int64_t nr);
 int launch_nearest_sqdist(const float* q, int64_t nq, const float* ref, int64_t nr, float* d2, int32_t* idx, void* ws, hipStream_t st);
 
+// mesh cleaning (mesh_clean.hip): label dilation, silhouette votes per vertex, connected components by union-find
+int launch_label_dilate(const int8_t* label, int64_t n_frames, int H, int W, int radius, uint8_t* tmp, uint8_t* keep, hipStream_t st);
+int launch_mesh_mask_votes(const float* verts, int64_t nv, const uint8_t* keep, const float* R, const float* T, const float* K,
+                           int64_t n_frames, int H, int W, int32_t* bg_votes, int32_t* seen, hipStream_t st);
+int launch_mesh_components(const int64_t* faces, int64_t nf, int64_t nv, int32_t* labels, hipStream_t st);
+
 }  // namespace dh

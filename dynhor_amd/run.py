@@ -3,6 +3,7 @@
     python -m dynhor_amd.run --config_path configs/synthetic.yaml                 # one GPU
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --gpus 8        # frames shard 8-way data-parallel (RCCL)
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode evaluate_mesh --is_continue   # Chamfer / F-score, one JSON line
+    python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode evaluate_mesh --is_continue --mesh_clean mask+largest
 
 With --gpus N > 1 this process starts N ranks (one per GPU) through dynhor_amd.launch before it touches the GPU and exits
 with their code; under an external `torch.distributed.run` (WORLD_SIZE set) it is one of the ranks.
@@ -27,6 +28,8 @@ def main():
     ap.add_argument("--gt_normalize", type=str, default=None, choices=["none", "reference"],
                     help="evaluate_mesh: 'reference' = bring the ground truth into the canonical frame (mean 0, max vertex norm 0.5)")
     ap.add_argument("--mesh_resolution", type=int, default=None, help="evaluate_mesh: marching-cubes grid of the reconstruction")
+    ap.add_argument("--mesh_clean", type=str, default=None, choices=["none", "mask", "largest", "mask+largest"],
+                    help="validate_mesh / evaluate_mesh: clean the extracted mesh (default: the config's mesh_clean.mode, else none)")
     args = ap.parse_args()
 
     from . import launch
@@ -58,12 +61,17 @@ def main():
     elif args.mode == "validate_image":
         print("psnr", runner.validate_image())
     elif args.mode == "evaluate_mesh":
-        res = runner.evaluate_mesh(gt_mesh=args.gt_mesh, gt_normalize=args.gt_normalize, resolution=args.mesh_resolution)
+        res = runner.evaluate_mesh(gt_mesh=args.gt_mesh, gt_normalize=args.gt_normalize, resolution=args.mesh_resolution,
+                                   clean=args.mesh_clean)
         if runner.rank == 0:
             import json
             print(json.dumps(res), flush=True)
     else:
-        print("surface crossings", runner.validate_mesh()[1])
+        print("surface crossings", runner.validate_mesh(clean=args.mesh_clean)[1])
+        st = runner.last_clean_stats
+        if st is not None:
+            print(f"mesh_clean {st['mode']}: removed {st['removed_verts']} of {st['verts_in']} vertices, {st['removed_faces']} of "
+                  f"{st['faces_in']} faces ({st['components']} components)", flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -52,6 +52,13 @@ DEFAULT_CONF = {
 }
 
 
+# the optional mesh_clean: block of the YAML (validate_mesh / evaluate_mesh; dynhor_amd/mesh_clean.py).  dilate_px 2 = the smallest
+# safe dilation plus one pixel of margin: on the synthetic scene (64 frames of 512 x 512, hand on) meshed at resolution 512, mask culling
+# removes 176,562 of the 395,896 object vertices at 0 px (silhouette vertices whose pixel centre misses the object in some frame) and
+# none at 1, 2 or 3 px (MI355X; tests/test_gpu_mesh_clean.py::test_default_dilation_culls_no_object_vertex prints the sweep)
+MESH_CLEAN_DEFAULTS = {"mode": "none", "dilate_px": 2, "min_bg_votes": 1, "min_area_frac": None}
+
+
 def _merge(base, over):
     out = dict(base)
     for k, v in (over or {}).items():
@@ -143,6 +150,7 @@ class Runner:
         self.frame_perm = schedules.FramePermutation(self.dataset.n_images, tr["ray_seed"])   # same on every rank
         self.scalars = []
         self._board = None
+        self.last_clean_stats = None     # validate_mesh / evaluate_mesh with cleaning: mesh_clean.clean_mesh's counts
         if is_continue:
             ck_dir = os.path.join(self.base_exp_dir, "checkpoints")
             ck = sorted(f for f in os.listdir(ck_dir) if f.endswith(".pth")) if os.path.isdir(ck_dir) else []
@@ -406,23 +414,50 @@ class Runner:
         return psnr
 
     @torch.no_grad()
-    def validate_mesh(self, resolution=64, threshold=0.0, world_space=False, save=True):
+    def validate_mesh(self, resolution=64, threshold=0.0, world_space=False, save=True, clean=None):
         """Upstream Runner.validate_mesh / NeuSRenderer.extract_geometry: -sdf on a regular grid over
         the object bounding box (HIP no-grad SDF kernel, 64^3-point chunks), iso-surface by marching cubes (model.mesh_method: 'cubes' | 'tetrahedra')
-        (dynhor_amd/mesh.py; mcubes is not available), written as meshes/<iter>.ply.  Returns (vertices, triangles)."""
+        (dynhor_amd/mesh.py; mcubes is not available), written as meshes/<iter>.ply.  Returns (vertices, triangles).
+        clean: a mesh_clean.clean_mesh mode (None: the config's mesh_clean.mode, default "none").  With a mode other than "none" the raw
+        mesh is still written as <iter>.ply, the cleaned one as <iter>_clean.ply, and the cleaned mesh is returned (its counts in
+        self.last_clean_stats)."""
         from .mesh import write_ply
         bmin, bmax = self.dataset.object_bbox_min, self.dataset.object_bbox_max
         verts, faces = self.renderer.extract_geometry(bmin, bmax, resolution=resolution, threshold=threshold,
                                                       method=self.conf.get("model", {}).get("mesh_method", "cubes"))
+        d = os.path.join(self.base_exp_dir, "meshes")
         if save and self.rank == 0:
-            d = os.path.join(self.base_exp_dir, "meshes")
             os.makedirs(d, exist_ok=True)
             write_ply(os.path.join(d, "{:0>8d}.ply".format(self.iter_step)), verts, faces)
+        mode = self._clean_conf(clean)["mode"]
+        if mode != "none":
+            verts, faces = self._clean_mesh(verts, faces, clean)
+            if save and self.rank == 0:
+                write_ply(os.path.join(d, "{:0>8d}_clean.ply".format(self.iter_step)), verts, faces)
+        return verts, faces
+
+    def _clean_conf(self, mode=None):
+        """The YAML's optional mesh_clean: block over MESH_CLEAN_DEFAULTS; `mode` (when not None) overrides its mode."""
+        from .mesh_clean import MODES
+        c = dict(MESH_CLEAN_DEFAULTS)
+        c.update(self.conf.get("mesh_clean") or {})
+        if mode is not None:
+            c["mode"] = mode
+        if c["mode"] not in MODES:
+            raise ValueError(f"mesh_clean mode must be one of {MODES}, got {c['mode']!r}")
+        return c
+
+    def _clean_mesh(self, verts, faces, mode=None):
+        """mesh_clean.clean_mesh with the config's parameters, the dataset's labels and its current (refined) poses."""
+        from .mesh_clean import clean_mesh
+        c = self._clean_conf(mode)
+        verts, faces, self.last_clean_stats = clean_mesh(verts, faces, self.dataset, c["mode"], dilate_px=int(c["dilate_px"]),
+                                                         min_bg_votes=int(c["min_bg_votes"]), min_area_frac=c["min_area_frac"])
         return verts, faces
 
     @torch.no_grad()
     def evaluate_mesh(self, gt_mesh=None, gt_normalize=None, resolution=None, n_samples=None, taus=None, seed=0, save=True,
-                      gt_resolution=None):
+                      gt_resolution=None, clean=None):
         """Geometry metrics of the current reconstruction against a ground-truth surface (dynhor_amd/metrics.py: Chamfer distance,
         F-score, normal consistency; definitions in its docstring).  The mesh is extracted as validate_mesh does (renderer
         extract_geometry over the object bounding box, model.mesh_method) at `resolution`, then scored by metrics.mesh_metrics.
@@ -433,6 +468,8 @@ class Runner:
         cubes at gt_resolution over [-0.55, 0.55]^3; any other dataset raises ValueError.  Arguments left at None take the YAML's
         optional `eval:` block (gt_mesh, gt_normalize, resolution, gt_resolution, n_samples, taus), else 512 / 1,000,000 /
         (0.005, 0.01, 0.02).  data_info.obj_path is NOT ground truth (the reference's stage-1 shape prior) and is never used.
+        clean: a mesh_clean.clean_mesh mode (None: the config's mesh_clean.mode, default "none"); with a mode other than "none" the
+        cleaned mesh is scored and the dict gains clean, clean_removed_verts, clean_removed_faces and clean_components.
         Rank 0 writes meshes/<iter:08d>_eval.json and logs every number as eval/<key> to <exp>/board.  Returns the dict."""
         from . import metrics
         ev = self.conf.get("eval") or {}
@@ -453,10 +490,17 @@ class Runner:
         else:
             raise ValueError("evaluate_mesh: no ground truth -- pass gt_mesh (or set eval.gt_mesh in the config); only a synthetic "
                              "dataset has one built in")
-        verts, faces = self.validate_mesh(resolution=resolution, save=False)
+        verts, faces = self.validate_mesh(resolution=resolution, save=False, clean="none")
+        mode = self._clean_conf(clean)["mode"]
+        if mode != "none":
+            verts, faces = self._clean_mesh(verts, faces, clean)
         res = metrics.mesh_metrics(verts, faces, gt_v, gt_f, n_samples=n_samples, taus=taus, seed=seed, gt_normalize=gt_normalize,
                                    device=self.device)
         res.update(iter=self.iter_step, resolution=resolution, gt=gt_name)
+        if mode != "none":
+            st = self.last_clean_stats
+            res.update(clean=mode, clean_removed_verts=st["removed_verts"], clean_removed_faces=st["removed_faces"],
+                       clean_components=st["components"])
         if save and self.rank == 0:
             d = os.path.join(self.base_exp_dir, "meshes")
             os.makedirs(d, exist_ok=True)

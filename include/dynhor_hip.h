@@ -395,6 +395,32 @@ int dh_hash_set_scatter_mode(int mode);
 int64_t dh_nearest_sqdist_workspace(int64_t nq, int64_t nr);
 int dh_nearest_sqdist(const float* q, int64_t nq, const float* ref, int64_t nr, float* d2, int32_t* idx, void* ws, void* stream);
 
+/* ---- mesh cleaning (dynhor_amd/mesh_clean.py: silhouette culling with the object masks of every view, connected components) ----
+ * dh_label_dilate: label i8 [n_frames,H,W] (1 object / 0 background / -1 hand, Dataset.label) -> keep u8 [n_frames,H,W]:
+ * keep[f,y,x] = 1 if any pixel of the square window of half-width `radius` about (x,y), clipped to the image, has label != 0 (object
+ * and hand both count as "not background": a hand pixel hides what lies behind it), else 0.  radius 0 = a copy of label != 0.
+ * Two separable passes through the caller's tmp u8 [n_frames,H,W].  n_frames == 0: no-op.
+ * DH_ERR_BAD_ARG: null pointer, negative n_frames or radius, H or W < 1.  DH_ERR_UNSUPPORTED: n_frames * H >= 2^31, W > 65535 * 256.
+ *
+ * dh_mesh_mask_votes: for each vertex v of verts [nv,3] and each frame f, x_cam = R_f v + T_f (R [n_frames,9] row-major, T
+ * [n_frames,3]: Dataset.R / Dataset.T), u = (K0 . x_cam) / z, w = (K1 . x_cam) / z with K [3,3] row-major, one for the sequence
+ * (z = x_cam[2]; the inverse of dh_gen_rays, whose ray of pixel (x,y) passes through K^-1 [x,y,1]).  v is SEEN in f when z > 0 and the
+ * pixel (floor(u + 0.5), floor(w + 0.5)) lies inside the image (range-checked in fp32 before any integer conversion); a seen vertex
+ * whose pixel has keep == 0 is a background vote.  seen[v] and bg_votes[v] (int32) count the frames: bitwise reproducible.
+ * Dataset.T of a sequence read from disk is already T / obj_scale; a pinhole camera does not see that factor, so the pixels are those
+ * of the on-disk poses.  fp32 in the order: c_r = fma(R_r2, z, fma(R_r1, y, R_r0 x)) + T_r; u = fma(K02, c2, fma(K01, c1, K00 c0)) / c2.
+ * nv == 0: no-op.  DH_ERR_BAD_ARG: null pointer, negative count, H or W < 1.
+ *
+ * dh_mesh_components: connected components of the graph on nv vertices whose edges are the three edges of every face of faces
+ * int64 [nf,3]: labels[v] (int32) = the smallest vertex index of v's component (independent of scheduling: bitwise reproducible);
+ * a vertex in no face is its own component; a face with an index outside [0, nv) is ignored.  Lock-free union-find (agent-scope
+ * atomics only while hooking) and then ceil(log2 nv) pointer-jumping launches: a bounded number of launches whatever the depth.
+ * DH_ERR_BAD_ARG: null pointer, negative count.  DH_ERR_UNSUPPORTED: nv >= 2^31. */
+int dh_label_dilate(const int8_t* label, int64_t n_frames, int H, int W, int radius, uint8_t* tmp, uint8_t* keep, void* stream);
+int dh_mesh_mask_votes(const float* verts, int64_t nv, const uint8_t* keep, const float* R, const float* T, const float* K,
+                       int64_t n_frames, int H, int W, int32_t* bg_votes, int32_t* seen, void* stream);
+int dh_mesh_components(const int64_t* faces, int64_t nf, int64_t nv, int32_t* labels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
