@@ -326,11 +326,11 @@ struct SdfGradEpi : PEpi<SdfGradEpi<SAVE>, 5, 3> {
     const float inv;
     const rsrc_t hr, st;           // act[l-1] (read), asave[l-1] (written; a 0-record descriptor where this tile stores nothing)
     const int loff;
-    float& hmax;
+    unsigned& hmax;
     float sa = 0.f, sb = 0.f;
     f32x4 hq[RING];
     __device__ __forceinline__ SdfGradEpi(f32x16 (&acc_)[MT][2], _Float16* img_, HScratchP& hs_, float* lmax_, int wave_, int lane_, int tid_,
-                                          float inv_, rsrc_t hr_, rsrc_t st_, int loff_, bool, float& hmax_)
+                                          float inv_, rsrc_t hr_, rsrc_t st_, int loff_, bool, unsigned& hmax_)
         : acc(acc_), hs(hs_), lmax(lmax_), wave(wave_), lane(lane_), tid(tid_), inv(inv_), hr(hr_), st(st_), loff(loff_), hmax(hmax_) {
         this->handoff_init(img_, wave_, lane_);
         DH_UNROLL for (int g = 0; g < RING; ++g) hq[g] = tile_ld(hr, loff, g);       // groups 0 .. RING-1 (float4 index == group index)
@@ -342,7 +342,7 @@ struct SdfGradEpi : PEpi<SdfGradEpi<SAVE>, 5, 3> {
         const f32x4& h = hq[G % RING];
         if constexpr (SUB == 0 || SUB == 2) {
             constexpr int i = SUB;                                               // values i, i + 1 of the group
-            if constexpr (SUB == 0) { hmax = fmaxf(hmax, fmaxf(h[0], h[1])); hmax = fmaxf(hmax, fmaxf(h[2], h[3])); }
+            if constexpr (SUB == 0) { hmax = watch_max3(hmax, h[0], h[1]); hmax = watch_max3(hmax, h[2], h[3]); }
             sa = 1.f - __builtin_amdgcn_exp2f(h[i] * C);                         // softplus_deriv_from_h
             sb = 1.f - __builtin_amdgcn_exp2f(h[i + 1] * C);
         } else if constexpr (SUB == 1 || SUB == 3) {
@@ -385,7 +385,7 @@ __global__ __launch_bounds__(256, 1) void sdf_grad_p_kernel(SdfGradPPtrs P, cons
     auto winv = [&](int l) { return l == 0 ? wi[0] : l == 1 ? wi[1] : l == 2 ? wi[2] : l == 3 ? wi[3] : l == 4 ? wi[4] : l == 5 ? wi[5] : l == 6 ? wi[6] : wi[7]; };
     auto rev = [&](int l) { return l == 1 ? P.rev1 : l == 2 ? P.rev2 : l == 3 ? P.rev3 : l == 4 ? P.rev4 : l == 5 ? P.rev5 : l == 6 ? P.rev6 : P.rev7; };
     const float w0 = P.w8row0[acc_col(wave, 0, lane)], w1 = P.w8row0[acc_col(wave, 1, lane)];
-    float hmax = 0.f;                                             // RANGE WATCH of the forward chain: kernels_mlp_h.hip sdf_grad_h_kernel
+    unsigned hmax = 0u;                                           // RANGE WATCH of the forward chain: kernels_mlp_h.hip sdf_grad_h_kernel
     PW<GRAD_NREG> W;
     pw_load_all(W, P.rev7, wave, lane);
     _Float16* imgA = simg[0];
@@ -419,7 +419,7 @@ __global__ __launch_bounds__(256, 1) void sdf_grad_p_kernel(SdfGradPPtrs P, cons
             const int64_t tile = which ? tileB : tileA;
             acc_load_native_b(acc, tile_rsrc(act + ((int64_t)7 * ntiles + tile) * TILE_F), loff);
             DH_UNROLL for (int m = 0; m < MT; ++m) DH_UNROLL for (int t = 0; t < 2; ++t)
-                DH_UNROLL for (int r = 0; r < 16; r += 2) hmax = fmaxf(hmax, fmaxf(acc[m][t][r], acc[m][t][r + 1]));
+                DH_UNROLL for (int r = 0; r < 16; r += 2) hmax = watch_max3(hmax, acc[m][t][r], acc[m][t][r + 1]);
             acc_map(acc, [&](int, int t, int, float h) { float s, em; softplus_deriv_from_h(h, s, em); return (t ? w1 : w0) * s; });
             if (SAVE && (which == 0 || okB)) acc_store_native_b(acc, tile_rsrc(asave + ((int64_t)7 * ntiles + tile) * TILE_F), loff);
             tile_max_publish(hs.sred, wave, lane, acc_absmax(acc));
@@ -514,8 +514,8 @@ __global__ __launch_bounds__(256, 1) void sdf_grad_p_kernel(SdfGradPPtrs P, cons
     }
     if (SAVE && absmax && tid < 8) post_class_max(absmax, ABSMAX_ASAVE + tid, hs.lmax[tid]);
     if (absmax) {                                      // (also forward-only renders)
-        hmax = wave_max(hmax);
-        if (lane == 0) post_class_max(absmax, ABSMAX_ACT, hmax);
+        const float m = wave_max(watch_close(hmax));
+        if (lane == 0) post_class_max(absmax, ABSMAX_ACT, m);
     }
 }
 

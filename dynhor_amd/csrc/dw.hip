@@ -373,7 +373,9 @@ constexpr int DWH_BUF = 16 * DWH_TILE;
 // per pair (plain scalars, selected with ?: -- an array indexed by the run-time pair number goes to scratch and turns the tile
 // maximum's load into a flat load): prod = S_X(launch) S_Y, also the tame operand's scale before the per-tile division; xt = the
 // heavy operand's per-tile maxima; heavy_a: X is A
-// poison: 1, or NaN when the workspace's scale tables were not written by this step's SPLIT_F16 stages (workspace.h ABSMAX_TAG)
+// poison: 1, or NaN when the workspace's scale tables were not written by this step's SPLIT_F16 stages (workspace.h ABSMAX_TAG) or
+// when a class maximum of the job's operands is not finite (ABSMAX_ACT is +inf after an activation overflowed the forward chain's
+// constant scale: its scale would clamp to 2^-60 and flush the finite values to zero -- a finite gradient that is garbage)
 struct DwScales { float prod0, prod1; const unsigned* xt0; const unsigned* xt1; bool heavy_a0, heavy_a1; float poison; };
 __device__ __forceinline__ float dw_class_scale(const unsigned* __restrict__ absmax, int cls) {
     return cls < 0 ? H2_XS : __builtin_bit_cast(float, pow2_scale_bits(absmax[cls * ABSMAX_STRIDE], H2_AT));
@@ -381,15 +383,18 @@ __device__ __forceinline__ float dw_class_scale(const unsigned* __restrict__ abs
 __device__ __forceinline__ DwScales dw_job_scales(const DwJob& J, const unsigned* __restrict__ absmax, const unsigned* __restrict__ tmax,
                                                   int64_t ntiles) {
     DwScales s;
+    bool finite = true;
+    auto cls_ok = [&](int cls) { return cls < 0 || absmax[cls * ABSMAX_STRIDE] < 0x7f800000u; };
     auto one = [&](int i, float& prod, const unsigned*& xt, bool& heavy_a) {
         heavy_a = J.ha[i] >= 0;
         const int hx = heavy_a ? J.ha[i] : J.hb[i];
         xt = tmax + (int64_t)(hx < 0 ? 0 : hx) * ntiles;
         prod = dw_class_scale(absmax, J.ca[i]) * dw_class_scale(absmax, J.cb[i]);
+        finite = finite && cls_ok(J.ca[i]) && cls_ok(J.cb[i]);
     };
     one(0, s.prod0, s.xt0, s.heavy_a0);
     one(1, s.prod1, s.xt1, s.heavy_a1);
-    s.poison = absmax[ABSMAX_TAG * ABSMAX_STRIDE] == ABSMAX_TAG_F16 ? 1.f : __builtin_nanf("");
+    s.poison = finite && absmax[ABSMAX_TAG * ABSMAX_STRIDE] == ABSMAX_TAG_F16 ? 1.f : __builtin_nanf("");
     return s;
 }
 // development switches of the main body (scripts/build_variant.sh; same-box A/Bs in profiles/r05_ab_dw_variants.json)

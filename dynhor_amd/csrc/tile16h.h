@@ -141,6 +141,15 @@ __device__ __forceinline__ TileScale tile_scale(const float* sred, float* lmax, 
 __device__ __forceinline__ void post_class_max(unsigned* absmax, int cls, float m) {
     atomicMax(absmax + cls * ABSMAX_STRIDE, __builtin_bit_cast(unsigned, m));
 }
+// RANGE WATCH of the SDF forward's saved activations (sdf_grad_h_kernel, sdf_grad_p_kernel): a running maximum over the fp32 BIT
+// PATTERNS, one v_max3_u32 per two values (the issue cost of the v_max3_f32 it replaces).  An fmaxf maximum drops NaN -- and an
+// overflowed piece turns its whole m-tile of saved values into NaN (chain_t.hip T_SAVE_MFMA: inf * 0, inf + -inf) -- while every NaN
+// and +inf pattern lies at or above 0x7f800000: clamped there by watch_close, a non-finite activation posts +inf.  Premise: a saved
+// activation never has the sign bit set (softplus >= 0, a zero saved as +0; tests/test_gpu_saved_tiles.py pins it).
+__device__ __forceinline__ unsigned watch_max3(unsigned m, float a, float b) {
+    return max(m, max(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b)));
+}
+__device__ __forceinline__ float watch_close(unsigned m) { return __builtin_bit_cast(float, min(m, 0x7f800000u)); }
 // ---------------------------------------------------------------- the piece-plane LDS image
 constexpr int LDH = 264;                 // row stride of a plane in halves: 528 B = 132 dwords, 132 % 64 == 4 like LDX -> conflict-free b128 reads
 constexpr int PLANE_H = TM * LDH;        // halves per plane; the image is hi plane, then lo plane

@@ -100,7 +100,9 @@ int dh_workspace_floats(int64_t npts, int64_t* infer_floats, int64_t* fwd_floats
  * results downstream of it are NaN (every other operand class of the MLPs is scaled dynamically, per tile or per launch, and has no
  * such limit; the embedding input shares the constant scale but is a point of the unit sphere).  dh_sdf_gradient(_ex) -- which reads
  * every activation tile the forward saved -- therefore posts the largest activation of the launch into the workspace: one fp32 word
- * at float offset *act_max_off of ws, valid once dh_sdf_gradient of the step has run.  A caller that can afford a device read (the
+ * at float offset *act_max_off of ws, valid once dh_sdf_gradient of the step has run; +inf when any activation overflowed (a saved
+ * value downstream of an overflowed piece is NaN, and the word never lets a finite survivor stand for it), and then the step's
+ * weight-gradient launch writes NaN for every weight the activations feed.  A caller that can afford a device read (the
  * Runner: at report iterations) compares it with *limit and switches to DH_ARITH_SPLIT_BF16 / raises.  *tag_off: the word that holds
  * 0x00F16F16 after a SPLIT_F16 forward (see "ONE ARITHMETIC PER STEP" above).  The no-grad chain has no workspace: beyond the limit
  * its outputs are NaN (never finite garbage). */

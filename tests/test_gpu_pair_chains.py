@@ -20,10 +20,13 @@ pytestmark = pytest.mark.gpu
 F16, TILE, PAIR = 2, 0x100, 0x200
 
 
-def _setup(hiplib, npts, n_per_ray, seed):
+def _setup(hiplib, npts, n_per_ray, seed, overflow=False):
     from dynhor_amd import _lib
     dev = torch.device("cuda:0")
     sdf, col, var = randomized_models(seed=seed, device=dev, jitter=0.05)
+    if overflow:                    # every softplus(lin1) beyond the forward chain's fp16 range (tests/test_gpu_range_watch.py)
+        with torch.no_grad():
+            sdf.lin1.weight_g *= 3.0e6
     flat = flat_from_oracle(sdf, var, col)
     packed = torch.empty(hiplib.dh_packed_floats(), device=dev)
     _lib.check(hiplib.dh_pack_weights(_lib.ptr(flat), _lib.ptr(packed), _lib.stream()))
@@ -72,10 +75,31 @@ def test_colour_forward_pair_form_is_bit_identical_to_the_tile_form(hiplib, npts
 @pytest.mark.parametrize("save", [1, 0, 2])
 def test_input_gradient_pair_form_is_bit_identical_to_the_tile_form(hiplib, npts, save):
     """normals, the saved tiles a_0..a_7, the class maxima, the activation range word (and gesave with save = 2: pose refinement)."""
-    packed, pts, dirs = _setup(hiplib, npts, 4, seed=6)
+    n_tile, n_pair, ws_tile, ws_pair = _input_gradient_both_forms(hiplib, npts, save, overflow=False)
+    assert torch.isfinite(n_tile).all() and n_tile.abs().max().item() > 1e-3
+    _assert_same_bits(n_tile, n_pair, ws_tile, ws_pair)
+
+
+@pytest.mark.parametrize("npts", [64 * 6, 64 * 7 + 5, 64 * 1301 + 17, 64])
+@pytest.mark.parametrize("save", [1, 0, 2])
+def test_input_gradient_pair_form_is_bit_identical_to_the_tile_form_under_overflow(hiplib, npts, save):
+    """every activation of lin1 overflows the forward chain's fp16 range (tests/test_gpu_range_watch.py): NaN tiles and a +inf range
+    word, the same bits in both forms."""
+    from dynhor_amd import _lib
+    n_tile, n_pair, ws_tile, ws_pair = _input_gradient_both_forms(hiplib, npts, save, overflow=True)
+    a = _lib.range_words()[0]
+    assert int(ws_tile[a: a + 1].view(torch.int32).item()) == 0x7F800000 and not torch.isfinite(n_tile).any()
+    _assert_same_bits(n_tile, n_pair, ws_tile, ws_pair)
+
+
+def _input_gradient_both_forms(hiplib, npts, save, overflow):
+    packed, pts, dirs = _setup(hiplib, npts, 4, seed=6, overflow=overflow)
     _, ws_tile, n_tile = _forward(hiplib, packed, pts, dirs, 4, TILE, 1 if save else 0, TILE) if save != 2 else _grad_only(hiplib, packed, pts, TILE, 2)
     _, ws_pair, n_pair = _forward(hiplib, packed, pts, dirs, 4, TILE, 1 if save else 0, PAIR) if save != 2 else _grad_only(hiplib, packed, pts, PAIR, 2)
-    assert torch.isfinite(n_tile).all() and n_tile.abs().max().item() > 1e-3
+    return n_tile, n_pair, ws_tile, ws_pair
+
+
+def _assert_same_bits(n_tile, n_pair, ws_tile, ws_pair):
     assert torch.equal(n_tile.view(torch.int32), n_pair.view(torch.int32)), f"normals differ: max |d| {(n_tile - n_pair).abs().max().item():.3e}"
     d = (ws_tile.view(torch.int32) != ws_pair.view(torch.int32))
     assert not d.any(), f"{int(d.sum())} workspace words differ (first at float offset {int(d.nonzero()[0])})"

@@ -111,7 +111,7 @@ def test_sdf_activations_beyond_the_constant_scales_range_are_reported_not_hidde
     a, _, lim = _lib.range_words()
     m = float(s.ws[a])
     print(f"posted max activation {m:.4g}, limit {lim:.0f}")
-    assert m > lim
+    assert m == float("inf")                # an overflowed activation is NaN in its saved tile: the watch posts +inf for it
     with pytest.raises(_lib.DynhorHipError, match="split_f16 range exceeded"):
         p_r.check_range(s)
     # the same network in the three-piece bf16 arithmetic has no such limit and no range word to consult

@@ -75,6 +75,10 @@ def test_saved_activation_tiles_match_the_oracle_and_are_two_piece_sums(hiplib, 
         ref = _oracle_activations(sdf, pts)
         sdf.float()
     assert len(ref) == 8
+    # the range watch takes its maximum over fp32 bit patterns (csrc/tile16h.h watch_max3): no saved activation word, pad rows and
+    # lin3's pad columns included, has the sign bit set
+    acts = ws[act0: act0 + 8 * nt * TILE_F]
+    assert not bool((acts.view(torch.int32) < 0).any()), int((acts.view(torch.int32) < 0).sum())
     worst = 0.0
     for l in range(8):
         tiles = ws[act0 + l * nt * TILE_F: act0 + (l + 1) * nt * TILE_F]
