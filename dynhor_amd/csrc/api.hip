@@ -604,4 +604,27 @@ int dh_mesh_components(const int64_t* faces, int64_t nf, int64_t nv, int32_t* la
     return launch_mesh_components(faces, nf, nv, labels, static_cast<hipStream_t>(stream));
 }
 
+int dh_mesh_raster_depth(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* R, const float* T,
+                         const float* K, int64_t n_frames, int H, int W, uint64_t* zbuf, void* stream) {
+    if (nv < 0 || nf < 0 || n_frames < 0 || H <= 0 || W <= 0) return DH_ERR_BAD_ARG;
+    if (nf >= ((int64_t)1 << 32) || n_frames >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;   // face ids are 32-bit key halves
+    if (H > (1 << 24) || W > (1 << 24)) return DH_ERR_UNSUPPORTED;                                // pixel centres exact in fp32
+    if (nf == 0 || n_frames == 0) return DH_OK;
+    if (!verts || !faces || !R || !T || !K || !zbuf) return DH_ERR_BAD_ARG;
+    return launch_mesh_raster_depth(verts, nv, faces, nf, R, T, K, n_frames, H, W, zbuf, static_cast<hipStream_t>(stream));
+}
+
+int dh_mesh_bake_colors(const float* verts, const float* normals, int64_t nv, const uint8_t* rgb, const uint8_t* usable,
+                        const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
+                        float depth_eps, float min_cos, float* acc, int32_t* n_views, void* stream) {
+    if (nv < 0 || n_frames < 0 || H <= 0 || W <= 0) return DH_ERR_BAD_ARG;
+    if (depth_eps != depth_eps || depth_eps < 0.f || min_cos != min_cos) return DH_ERR_BAD_ARG;      // NaN, negative
+    if (nv >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;                                        // n_views is int32
+    if (H > (1 << 24) || W > (1 << 24)) return DH_ERR_UNSUPPORTED;
+    if (nv == 0 || n_frames == 0) return DH_OK;
+    if (!verts || !normals || !rgb || !usable || !zbuf || !R || !T || !K || !acc || !n_views) return DH_ERR_BAD_ARG;
+    return launch_mesh_bake_colors(verts, normals, nv, rgb, usable, zbuf, R, T, K, n_frames, H, W, depth_eps, min_cos, acc, n_views,
+                                   static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

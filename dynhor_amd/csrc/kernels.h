@@ -162,4 +162,11 @@ int launch_mesh_mask_votes(const float* verts, int64_t nv, const uint8_t* keep, 
                            int64_t n_frames, int H, int W, int32_t* bg_votes, int32_t* seen, hipStream_t st);
 int launch_mesh_components(const int64_t* faces, int64_t nf, int64_t nv, int32_t* labels, hipStream_t st);
 
+// mesh colouring (mesh_color.hip): z-buffer of the mesh in every frame, per-vertex colour gathered over the frames
+int launch_mesh_raster_depth(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* R, const float* T,
+                             const float* K, int64_t n_frames, int H, int W, uint64_t* zbuf, hipStream_t st);
+int launch_mesh_bake_colors(const float* verts, const float* normals, int64_t nv, const uint8_t* rgb, const uint8_t* usable,
+                            const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
+                            float depth_eps, float min_cos, float* acc, int32_t* n_views, hipStream_t st);
+
 }  // namespace dh

@@ -262,14 +262,27 @@ def marching_cubes(u: torch.Tensor, threshold: float, bound_min, bound_max):
     return verts, faces
 
 
-def write_ply(path: str, verts: torch.Tensor, faces: torch.Tensor):
+def write_ply(path: str, verts: torch.Tensor, faces: torch.Tensor, colors=None):
+    """Binary little-endian PLY: float x y z per vertex, then the triangles.  colors: u8 [V,3] per-vertex red, green, blue (vertex
+    element gains `property uchar red/green/blue`); None writes geometry only."""
     v = verts.detach().cpu().numpy().astype(np.float32)
     f = faces.detach().cpu().numpy().astype(np.int32)
+    if colors is not None:
+        c = colors.detach().cpu().numpy() if torch.is_tensor(colors) else np.asarray(colors)
+        if c.dtype != np.uint8 or c.shape != (len(v), 3):
+            raise ValueError(f"write_ply: colors must be uint8 [{len(v)},3], got {c.dtype} {c.shape}")
     with open(path, "wb") as fh:
         fh.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
-                  "property float z\nelement face %d\nproperty list uchar int vertex_indices\nend_header\n"
-                  % (len(v), len(f))).encode())
-        fh.write(v.tobytes())
+                  "property float z\n%selement face %d\nproperty list uchar int vertex_indices\nend_header\n"
+                  % (len(v), "" if colors is None else "property uchar red\nproperty uchar green\nproperty uchar blue\n",
+                     len(f))).encode())
+        if colors is None:
+            fh.write(v.tobytes())
+        else:
+            rec = np.empty(len(v), dtype=[("p", "<f4", (3,)), ("c", "u1", (3,))])
+            rec["p"] = v
+            rec["c"] = c
+            fh.write(rec.tobytes())
         rec = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
         rec["n"] = 3
         rec["i"] = f

@@ -1,0 +1,194 @@
+"""Vertex colours for an extracted mesh, from the observed pixels of the training frames or from the colour network.
+
+  * ``raster_depth``: z-buffer of the mesh in every frame (csrc/mesh_color.hip, dh_mesh_raster_depth): the key
+    (float_bits(depth) << 32) | face of the nearest face at every pixel centre, by a 64-bit atomic minimum (bitwise reproducible).
+  * ``bake_vertex_colors``: per vertex, the cosine-weighted mean of the pixels that see it (dh_mesh_bake_colors): a frame counts when
+    the vertex is in front of the camera and inside the image, its nearest pixel is usable (object label, eroded by ``erode_px`` so
+    that silhouette edges bleed neither background nor hand colour), the vertex is not hidden (camera depth <= z-buffer depth +
+    ``depth_eps``), and it faces the camera (cos >= ``min_cos``).  Hand (-1) and background (0) pixels never colour the object.
+  * ``network_vertex_colors``: the colour MLP at each vertex, seen along -n (n the normalised SDF gradient; instant-nsr-pl's export
+    rule), through the renderer's family hooks, so the neus and hash families both work.
+  * ``color_mesh``: "none" | "views" | "network" | "views+network" (unseen vertices take the network colour; in "views" 0.5 grey).
+
+The kernels run on the current stream; there is no CPU path.
+"""
+from __future__ import annotations
+
+from types import SimpleNamespace
+
+import torch
+
+from . import _lib
+from .mesh_clean import _device_tensor, _faces, dilate_labels
+
+MODES = ("none", "views", "network", "views+network")
+NET_CHUNK = 1 << 20
+
+
+def _verts(fn, verts):
+    return _device_tensor(fn, "verts", verts, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[V,3]")
+
+
+def _cams(fn, F, R, T, K, device):
+    R = _device_tensor(fn, "R", R, torch.float32, lambda s: s in ((F, 3, 3), (F, 9)), f"[{F},3,3]")
+    T = _device_tensor(fn, "T", T, torch.float32, lambda s: s in ((F, 3), (F, 1, 3)), f"[{F},3]")
+    K = _device_tensor(fn, "K", K, torch.float32, lambda s: s == (3, 3), "[3,3]")
+    if any(t.device != device for t in (R, T, K)):
+        raise ValueError(f"{fn}: every tensor must be on {device}")
+    return R, T, K
+
+
+def raster_depth(verts, faces, R, T, K, H: int, W: int) -> torch.Tensor:
+    """zbuf int64 [F,H,W]: the uint64 keys (float_bits(camera depth) << 32) | face of the nearest face whose screen triangle covers
+    each pixel centre (integer coordinates; both windings), -1 where none does.  R [F,3,3], T [F,3], K [3,3] (Dataset.R / T / K).
+    zbuf >> 32 (as int32 bits) is the depth as float32; zbuf & 0xffffffff the face."""
+    verts = _verts("raster_depth", verts)
+    faces = _faces("raster_depth", faces)
+    if verts.device != faces.device:
+        raise ValueError(f"raster_depth: verts on {verts.device}, faces on {faces.device}")
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0:
+        raise ValueError(f"raster_depth: empty images {H}x{W}")
+    F = R.shape[0] if torch.is_tensor(R) and R.dim() >= 1 else -1
+    R, T, K = _cams("raster_depth", F, R, T, K, verts.device)
+    zbuf = torch.full((F, H, W), -1, dtype=torch.int64, device=verts.device)
+    with torch.cuda.device(verts.device):
+        _lib.check(_lib.lib().dh_mesh_raster_depth(_lib.ptr(verts), verts.shape[0], _lib.ptr(faces), faces.shape[0], _lib.ptr(R),
+                                                   _lib.ptr(T), _lib.ptr(K), F, H, W, _lib.ptr(zbuf), _lib.stream()))
+    return zbuf
+
+
+def zbuf_depth(zbuf: torch.Tensor) -> torch.Tensor:
+    """float32 depth of a raster_depth buffer (inf where empty)."""
+    d = (zbuf >> 32).to(torch.int32).view(torch.float32)
+    return torch.where(zbuf == -1, torch.full_like(d, float("inf")), d)
+
+
+def vertex_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """Unit vertex normals float32 [V,3]: the sum of the cross products (b - a) x (c - a) (area-weighted face normals) of the faces
+    around each vertex, in fp64, as segment sums over the face corners sorted by vertex (stable sort: a fixed order, no float atomics,
+    bitwise reproducible), then normalised; 0 for a vertex in no face.  CPU or device tensors."""
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int64:
+        raise ValueError(f"vertex_normals: verts [V,3] and faces int64 [M,3], got {tuple(verts.shape)} and {faces.dtype} "
+                         f"{tuple(faces.shape)}")
+    v = verts.double()
+    nv = v.shape[0]
+    fn = torch.linalg.cross(v[faces[:, 1]] - v[faces[:, 0]], v[faces[:, 2]] - v[faces[:, 0]])
+    corner = faces.reshape(-1)
+    order = torch.sort(corner, stable=True).indices
+    counts = torch.bincount(corner, minlength=nv)
+    per = fn.repeat_interleave(3, dim=0)[order]
+    n = torch.segment_reduce(per, "sum", lengths=counts, axis=0, unsafe=True) if nv else per.new_zeros(0, 3)
+    norm = n.norm(dim=1, keepdim=True)
+    return torch.where(norm > 0, n / norm.clamp(min=1e-300), torch.zeros_like(n)).float()
+
+
+def usable_map(label: torch.Tensor, erode_px: int) -> torch.Tensor:
+    """u8 [F,H,W]: 1 on object pixels (label 1) whose (2 erode_px + 1)^2 window, clipped to the image, holds only object pixels."""
+    not_obj = (label != 1).to(torch.int8)
+    return 1 - dilate_labels(not_obj, int(erode_px))
+
+
+def bake_vertex_colors(verts, faces, dataset, erode_px: int = 1, min_cos: float = 0.1, depth_eps: float = 0.01, frame_chunk: int = 16,
+                       normals=None):
+    """(colors f32 [V,3], weight [V], n_views int32 [V]) from the dataset's frames with its current poses (Dataset.R / T, refined in
+    place by pose refinement): colors = sum(c rgb/255) / sum(c) over the contributing frames (module docstring), weight = sum(c); NaN
+    colour where no frame contributes.  Frames go in chunks of `frame_chunk`, so the z-buffer holds frame_chunk * H * W * 8 bytes;
+    the per-vertex sums run over the frames in order whatever the chunking, so the result is bitwise the same for every chunk size.
+    normals: unit vertex normals (default: vertex_normals(verts, faces))."""
+    verts = _verts("bake_vertex_colors", verts)
+    faces = _faces("bake_vertex_colors", faces)
+    if int(erode_px) < 0 or int(frame_chunk) < 1 or not float(depth_eps) >= 0 or float(min_cos) != float(min_cos):
+        raise ValueError(f"bake_vertex_colors: erode_px >= 0, frame_chunk >= 1, depth_eps >= 0, min_cos a number; got {erode_px}, "
+                         f"{frame_chunk}, {depth_eps}, {min_cos}")
+    if normals is None:
+        normals = vertex_normals(verts, faces)
+    normals = _device_tensor("bake_vertex_colors", "normals", normals, torch.float32, lambda s: s == tuple(verts.shape), "[V,3]")
+    ds = dataset
+    F, H, W = ds.n_images, ds.H, ds.W
+    R, T, K = _cams("bake_vertex_colors", F, ds.R, ds.T, ds.K, verts.device)
+    rgb = _device_tensor("bake_vertex_colors", "dataset.rgb", ds.rgb, torch.uint8, lambda s: s == (F, H, W, 3), f"[{F},{H},{W},3]")
+    nv = verts.shape[0]
+    acc = torch.zeros(nv, 4, dtype=torch.float32, device=verts.device)
+    n_views = torch.zeros(nv, dtype=torch.int32, device=verts.device)
+    L = _lib.lib()
+    with torch.cuda.device(verts.device):
+        for f0 in range(0, F, int(frame_chunk)):
+            f1 = min(F, f0 + int(frame_chunk))
+            Rc, Tc = R[f0:f1].contiguous(), T[f0:f1].contiguous()
+            zbuf = raster_depth(verts, faces, Rc, Tc, K, H, W)
+            usable = usable_map(ds.label[f0:f1].contiguous(), erode_px)
+            _lib.check(L.dh_mesh_bake_colors(_lib.ptr(verts), _lib.ptr(normals), nv, _lib.ptr(rgb[f0:f1]), _lib.ptr(usable),
+                                             _lib.ptr(zbuf), _lib.ptr(Rc), _lib.ptr(Tc), _lib.ptr(K), f1 - f0, H, W,
+                                             float(depth_eps), float(min_cos), _lib.ptr(acc), _lib.ptr(n_views), _lib.stream()))
+            del zbuf, usable
+    w = acc[:, 3]
+    colors = torch.where((n_views > 0)[:, None], acc[:, :3] / w[:, None], torch.full_like(acc[:, :3], float("nan")))
+    return colors, w, n_views
+
+
+@torch.no_grad()
+def network_vertex_colors(renderer, verts, normals=None):
+    """Colour network at every vertex f32 [V,3], viewed along -n: n = normals (unit) if given, else the normalised SDF gradient at the
+    vertex.  Runs the renderer's family hooks (_net_forward, one sample per "ray", forward-only workspace) in chunks of at most 2^20
+    points: a first pass for the gradient, a second for the colour with the direction.  Non-finite output (split_f16 range exceeded,
+    or a diverged network) raises DynhorHipError."""
+    verts = _verts("network_vertex_colors", verts)
+    if normals is not None:
+        normals = _device_tensor("network_vertex_colors", "normals", normals, torch.float32, lambda s: s == tuple(verts.shape), "[V,3]")
+    dev = verts.device
+    packed = renderer.store.ensure_packed(renderer._arith())
+    out = torch.empty(verts.shape[0], 3, dtype=torch.float32, device=dev)
+    for s0 in range(0, verts.shape[0], NET_CHUNK):
+        pts = verts[s0:s0 + NET_CHUNK]
+        P = pts.shape[0]
+        s = SimpleNamespace(B=P, n=1, pts=pts, infer_only=True, ray_grads=False, ws=renderer._workspace(P, infer_only=True),
+                            sdf=torch.empty(P, device=dev), normals=torch.empty(P, 3, device=dev), colors=torch.empty(P, 3, device=dev))
+        if normals is None:
+            s.rays_d = torch.zeros(P, 3, device=dev)
+            renderer._net_forward(s, packed)
+            n = torch.nn.functional.normalize(s.normals, dim=1)
+        else:
+            n = normals[s0:s0 + P]
+        s.rays_d = (-n).contiguous()
+        renderer._net_forward(s, packed)
+        if not bool(torch.isfinite(s.colors).all()) or not bool(torch.isfinite(s.normals).all()):
+            raise _lib.DynhorHipError("network_vertex_colors: non-finite network output at the mesh vertices (split_f16 range "
+                                      "exceeded, or the network has diverged); use arithmetic 'split_bf16'")
+        out[s0:s0 + P] = s.colors
+    return out
+
+
+def color_mesh(verts, faces, mode: str, dataset=None, renderer=None, erode_px: int = 1, min_cos: float = 0.1, depth_eps: float = 0.01,
+               frame_chunk: int = 16):
+    """(colors u8 [V,3] or None for mode "none", stats).  "views": bake_vertex_colors, unseen vertices 0.5 grey; "network":
+    network_vertex_colors; "views+network": the views, unseen vertices the network colour.  stats: mode, verts_in, unseen_verts (no
+    contributing view), mean_views (mean n_views over the seen vertices; 0.0 when none is seen)."""
+    if mode not in MODES:
+        raise ValueError(f"color_mesh: mode must be one of {MODES}, got {mode!r}")
+    verts = _verts("color_mesh", verts)
+    faces = _faces("color_mesh", faces)
+    stats = {"mode": mode, "verts_in": int(verts.shape[0])}
+    if mode == "none":
+        return None, stats
+    if "views" in mode and dataset is None:
+        raise ValueError(f"color_mesh: mode {mode!r} needs the dataset")
+    if "network" in mode and renderer is None:
+        raise ValueError(f"color_mesh: mode {mode!r} needs the renderer")
+    if "views" in mode:
+        col, _, n_views = bake_vertex_colors(verts, faces, dataset, erode_px=erode_px, min_cos=min_cos, depth_eps=depth_eps,
+                                             frame_chunk=frame_chunk)
+        seen = n_views > 0
+        n_seen = int(seen.sum())
+        stats.update(unseen_verts=int(verts.shape[0] - n_seen),
+                     mean_views=float(n_views[seen].double().sum()) / n_seen if n_seen else 0.0)
+        if mode == "views+network":
+            if n_seen < verts.shape[0]:
+                col[~seen] = network_vertex_colors(renderer, verts[~seen].contiguous())
+        else:
+            col[~seen] = 0.5
+    else:
+        col = network_vertex_colors(renderer, verts)
+        stats.update(unseen_verts=int(verts.shape[0]), mean_views=0.0)
+    colors = (col.clamp(0.0, 1.0) * 255.0).round().to(torch.uint8)
+    return colors, stats

@@ -4,6 +4,7 @@
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --gpus 8        # frames shard 8-way data-parallel (RCCL)
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode evaluate_mesh --is_continue   # Chamfer / F-score, one JSON line
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode evaluate_mesh --is_continue --mesh_clean mask+largest
+    python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode validate_mesh --is_continue --mesh_color views+network
 
 With --gpus N > 1 this process starts N ranks (one per GPU) through dynhor_amd.launch before it touches the GPU and exits
 with their code; under an external `torch.distributed.run` (WORLD_SIZE set) it is one of the ranks.
@@ -30,6 +31,8 @@ def main():
     ap.add_argument("--mesh_resolution", type=int, default=None, help="evaluate_mesh: marching-cubes grid of the reconstruction")
     ap.add_argument("--mesh_clean", type=str, default=None, choices=["none", "mask", "largest", "mask+largest"],
                     help="validate_mesh / evaluate_mesh: clean the extracted mesh (default: the config's mesh_clean.mode, else none)")
+    ap.add_argument("--mesh_color", type=str, default=None, choices=["none", "views", "network", "views+network"],
+                    help="validate_mesh: colour the mesh and also write <iter>_color.ply (default: the config's mesh_color.mode, else none)")
     args = ap.parse_args()
 
     from . import launch
@@ -67,11 +70,15 @@ def main():
             import json
             print(json.dumps(res), flush=True)
     else:
-        print("surface crossings", runner.validate_mesh(clean=args.mesh_clean)[1])
+        print("surface crossings", runner.validate_mesh(clean=args.mesh_clean, color=args.mesh_color)[1])
         st = runner.last_clean_stats
         if st is not None:
             print(f"mesh_clean {st['mode']}: removed {st['removed_verts']} of {st['verts_in']} vertices, {st['removed_faces']} of "
                   f"{st['faces_in']} faces ({st['components']} components)", flush=True)
+        cs = runner.last_color_stats
+        if cs is not None and runner.rank == 0:
+            print(f"mesh_color {cs['mode']}: {cs['verts_in']} vertices, {cs['unseen_verts']} seen by no view, "
+                  f"{cs['mean_views']:.2f} views per seen vertex", flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -58,6 +58,9 @@ DEFAULT_CONF = {
 # none at 1, 2 or 3 px (MI355X; tests/test_gpu_mesh_clean.py::test_default_dilation_culls_no_object_vertex prints the sweep)
 MESH_CLEAN_DEFAULTS = {"mode": "none", "dilate_px": 2, "min_bg_votes": 1, "min_area_frac": None}
 
+# the optional mesh_color: block of the YAML (validate_mesh; dynhor_amd/mesh_color.py)
+MESH_COLOR_DEFAULTS = {"mode": "none", "erode_px": 1, "min_cos": 0.1, "depth_eps": 0.01}
+
 
 def _merge(base, over):
     out = dict(base)
@@ -151,6 +154,8 @@ class Runner:
         self.scalars = []
         self._board = None
         self.last_clean_stats = None     # validate_mesh / evaluate_mesh with cleaning: mesh_clean.clean_mesh's counts
+        self.last_mesh_colors = None     # validate_mesh with colouring: mesh_color.color_mesh's u8 [V,3] colours and its stats
+        self.last_color_stats = None
         if is_continue:
             ck_dir = os.path.join(self.base_exp_dir, "checkpoints")
             ck = sorted(f for f in os.listdir(ck_dir) if f.endswith(".pth")) if os.path.isdir(ck_dir) else []
@@ -414,13 +419,16 @@ class Runner:
         return psnr
 
     @torch.no_grad()
-    def validate_mesh(self, resolution=64, threshold=0.0, world_space=False, save=True, clean=None):
+    def validate_mesh(self, resolution=64, threshold=0.0, world_space=False, save=True, clean=None, color=None):
         """Upstream Runner.validate_mesh / NeuSRenderer.extract_geometry: -sdf on a regular grid over
         the object bounding box (HIP no-grad SDF kernel, 64^3-point chunks), iso-surface by marching cubes (model.mesh_method: 'cubes' | 'tetrahedra')
         (dynhor_amd/mesh.py; mcubes is not available), written as meshes/<iter>.ply.  Returns (vertices, triangles).
         clean: a mesh_clean.clean_mesh mode (None: the config's mesh_clean.mode, default "none").  With a mode other than "none" the raw
         mesh is still written as <iter>.ply, the cleaned one as <iter>_clean.ply, and the cleaned mesh is returned (its counts in
-        self.last_clean_stats)."""
+        self.last_clean_stats).
+        color: a mesh_color.color_mesh mode (None: the config's mesh_color.mode, default "none").  With a mode other than "none" the
+        returned mesh is coloured and additionally written as <iter>_color.ply (colours and stats in self.last_mesh_colors /
+        self.last_color_stats); <iter>.ply and <iter>_clean.ply are unchanged."""
         from .mesh import write_ply
         bmin, bmax = self.dataset.object_bbox_min, self.dataset.object_bbox_max
         verts, faces = self.renderer.extract_geometry(bmin, bmax, resolution=resolution, threshold=threshold,
@@ -434,7 +442,27 @@ class Runner:
             verts, faces = self._clean_mesh(verts, faces, clean)
             if save and self.rank == 0:
                 write_ply(os.path.join(d, "{:0>8d}_clean.ply".format(self.iter_step)), verts, faces)
+        cc = self._color_conf(color)
+        if cc["mode"] != "none":
+            from .mesh_color import color_mesh
+            self.last_mesh_colors, self.last_color_stats = color_mesh(
+                verts, faces, cc["mode"], dataset=self.dataset, renderer=self.renderer, erode_px=int(cc["erode_px"]),
+                min_cos=float(cc["min_cos"]), depth_eps=float(cc["depth_eps"]))
+            if save and self.rank == 0:
+                os.makedirs(d, exist_ok=True)
+                write_ply(os.path.join(d, "{:0>8d}_color.ply".format(self.iter_step)), verts, faces, colors=self.last_mesh_colors)
         return verts, faces
+
+    def _color_conf(self, mode=None):
+        """The YAML's optional mesh_color: block over MESH_COLOR_DEFAULTS; `mode` (when not None) overrides its mode."""
+        from .mesh_color import MODES
+        c = dict(MESH_COLOR_DEFAULTS)
+        c.update(self.conf.get("mesh_color") or {})
+        if mode is not None:
+            c["mode"] = mode
+        if c["mode"] not in MODES:
+            raise ValueError(f"mesh_color mode must be one of {MODES}, got {c['mode']!r}")
+        return c
 
     def _clean_conf(self, mode=None):
         """The YAML's optional mesh_clean: block over MESH_CLEAN_DEFAULTS; `mode` (when not None) overrides its mode."""

@@ -423,6 +423,36 @@ int dh_mesh_mask_votes(const float* verts, int64_t nv, const uint8_t* keep, cons
                        int64_t n_frames, int H, int W, int32_t* bg_votes, int32_t* seen, void* stream);
 int dh_mesh_components(const int64_t* faces, int64_t nf, int64_t nv, int32_t* labels, void* stream);
 
+/* ---- mesh colouring (dynhor_amd/mesh_color.py: vertex colours from the frames that see each vertex) ----
+ * Both entry points project as dh_mesh_mask_votes does: x_cam = R_f v + T_f (R [n_frames,9] row-major, T [n_frames,3]), then
+ * u = (K0 . x_cam) / z, w = (K1 . x_cam) / z with K [3,3] row-major, in fp32 in the order c_r = fma(R_r2, z, fma(R_r1, y, R_r0 x)) + T_r;
+ * u = fma(K02, c2, fma(K01, c1, K00 c0)) / c2.  Pixel centres sit at integer (u, w).
+ *
+ * dh_mesh_raster_depth: z-buffer zbuf u64 [n_frames,H,W] of the mesh verts [nv,3] / faces int64 [nf,3].  The caller fills zbuf with
+ * UINT64_MAX ("empty") before the call; each covered pixel centre is combined by a 64-bit atomic minimum with the key
+ * (float_bits(z) << 32) | face, z the perspective-correct camera depth z = 1 / sum_i(b_i / z_i), b_i the screen-space barycentrics.
+ * Coverage is double-sided and inclusive: the three fp32 edge functions edge(a, b, p) = fma(b.u - a.u, p.w - a.w, -((b.w - a.w) *
+ * (p.u - a.u))) of (v1,v2), (v2,v0), (v0,v1) all >= 0 or all <= 0; the depth is computed as (e0 + e1 + e2) / fma(e2, 1/z2, fma(e1,
+ * 1/z1, e0 / z0)).  A face is skipped when a vertex has z <= 1e-3, when its screen area edge(v0, v1, v2) is 0, or when an index lies
+ * outside [0, nv).  The minimum does not depend on scheduling: the buffer is bitwise reproducible, and a depth tie goes to the smaller
+ * face index.  Faces whose clipped pixel box exceeds 32 px in width or height are rasterised by a whole wave.  nf == 0 or
+ * n_frames == 0: no-op.  DH_ERR_BAD_ARG: null pointer, negative count, H or W < 1.  DH_ERR_UNSUPPORTED: nf >= 2^32,
+ * n_frames >= 2^31, H or W > 2^24.
+ *
+ * dh_mesh_bake_colors: for each vertex v (unit normal n, normals [nv,3]) and frame f in ascending order, the frame contributes when
+ * z > 1e-3, the nearest pixel (floor(u + 0.5), floor(w + 0.5)) lies in the image (range-checked in fp32), usable u8 [n_frames,H,W] is
+ * set there, zbuf is not empty there and z <= depth(zbuf) + depth_eps, and c = <n, normalize(C_f - v)> >= min_cos with C_f = -R_f^T
+ * T_f the camera centre.  A contributing frame ADDS acc[v] += (c rgb / 255, c) (acc f32 [nv,4], rgb u8 [n_frames,H,W,3]) and
+ * n_views[v] += 1 (int32): the caller zeroes both once and issues frame chunks in order on one stream, so every vertex's sum is a fixed
+ * sequential fp32 sum (rgb terms as fma(c, rgb / 255, acc)), bitwise reproducible whatever the chunking.  nv == 0 or n_frames == 0:
+ * no-op.  DH_ERR_BAD_ARG: null pointer, negative count, H or W < 1, depth_eps negative or NaN, min_cos NaN.  DH_ERR_UNSUPPORTED:
+ * nv >= 2^31, H or W > 2^24. */
+int dh_mesh_raster_depth(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* R, const float* T,
+                         const float* K, int64_t n_frames, int H, int W, uint64_t* zbuf, void* stream);
+int dh_mesh_bake_colors(const float* verts, const float* normals, int64_t nv, const uint8_t* rgb, const uint8_t* usable,
+                        const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
+                        float depth_eps, float min_cos, float* acc, int32_t* n_views, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
