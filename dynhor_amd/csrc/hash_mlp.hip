@@ -818,7 +818,6 @@ __global__ __launch_bounds__(64) void hash_fold_kernel(const float* __restrict__
 }
 
 // ---------------------------------------------------------------- launchers
-static inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
 
 int64_t hash_num_params() { return make_hash_param_off(hashgrid_entries()).total; }
 HashParamOff hash_param_off() { return make_hash_param_off(hashgrid_entries()); }

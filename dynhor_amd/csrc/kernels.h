@@ -14,6 +14,14 @@ int hash_scatter_mode();
 
 int launch_pack_weights(const float* params, float* packed, int arith_mask, hipStream_t stream);
 
+// status of the launches just enqueued: 0, or DH_ERR_LAUNCH (include/dynhor_hip.h) when the runtime reports an error
+inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
+// grid of a tile-resident chain launch: one workgroup per TM-point tile, at most `grid` (the workgroups loop over the rest)
+inline int grid_for(int64_t npts, int grid) {
+    const int64_t ntiles = (npts + TM - 1) / TM;
+    return (int)(ntiles < grid ? ntiles : grid);
+}
+
 // MLP chains (kernels_mlp.hip).  npts is padded by the caller to a multiple of 128 for saved buffers.
 int launch_sdf_nograd(const float* packed, const float* pts, int64_t npts, float* sdf, int grid, int arith, hipStream_t stream);
 int launch_sdf_nograd_t(const float* packed, const float* pts, int64_t npts, float* sdf, bool h2, hipStream_t stream);   // chain_t.hip
@@ -108,7 +116,7 @@ int launch_corr_loss(const float* rays_o, const float* rays_d, const float* z, c
 // backward chains (kernels_mlp_bwd.hip) and weight gradients (dw.hip)
 int launch_color_bwd(const float* packed, const float* colors, const float* d_colors, int64_t npts, const float* cact,
                      float* czbar, float* featbar, float* d_normals, float* tpart, float* absmax, int grid, int arith, hipStream_t st);
-// pose-refinement variants (split-bf16 arithmetic only): additionally the adjoints w.r.t. the sample points / view directions
+// pose-refinement variants (every arithmetic): additionally the adjoints w.r.t. the sample points / view directions
 int launch_color_bwd_rays(const float* packed, const float* colors, const float* d_colors, const float* dirs, int n_per_ray,
                           int64_t npts, const float* cact, float* czbar, float* featbar, float* d_normals, float* tpart,
                           float* d_pts, float* d_dirs_pts, float* absmax, int grid, int arith, hipStream_t st);

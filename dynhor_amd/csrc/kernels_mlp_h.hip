@@ -728,11 +728,6 @@ __global__ __launch_bounds__(256, 2) void sdf_bwd_h_kernel(SdfHPtrs P, const flo
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
-static inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
-static inline int grid_for(int64_t npts, int grid) {
-    const int64_t ntiles = (npts + TM - 1) / TM;
-    return (int)(ntiles < grid ? ntiles : grid);
-}
 int launch_sdf_grad_h(const float* packed, const float* pts, int64_t npts, const float* act, float* asave, float* normals,
                       int save, float* gesave, unsigned* absmax, int grid, hipStream_t stream) {
     hipLaunchKernelGGL(sdf_grad_h_kernel, dim3(grid_for(npts, grid)), dim3(256), 0, stream, make_sdfh_ptrs(packed), pts, npts, act,

@@ -450,7 +450,6 @@ __global__ __launch_bounds__(256) void render_bwd_kernel(const float* __restrict
 }
 
 // ================================================================ launchers
-static inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
 
 int launch_gen_rays(const uint8_t* rgb, const int8_t* label, const uint8_t* normal, const float* R, const float* T,
                     const float* Kinv, int H, int W, int frame, const int64_t* px, const int64_t* py, int64_t B,

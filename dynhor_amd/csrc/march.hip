@@ -85,7 +85,6 @@ __global__ __launch_bounds__(256) void march_kernel(const float* __restrict__ ra
     if (!EMIT && lane == 0) cnt[ray] = c < max_samples ? c : max_samples;
 }
 
-static inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
 
 int launch_march_count(const float* o, const float* d, const float* near, const float* far, const float* u, const uint8_t* occ,
                        int res, float radius, float step, float half_step, int max_samples, int64_t B, int32_t* cnt,
