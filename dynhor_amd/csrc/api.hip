@@ -626,5 +626,20 @@ int dh_mesh_bake_colors(const float* verts, const float* normals, int64_t nv, co
     return launch_mesh_bake_colors(verts, normals, nv, rgb, usable, zbuf, R, T, K, n_frames, H, W, depth_eps, min_cos, acc, n_views,
                                    static_cast<hipStream_t>(stream));
 }
+int dh_mesh_shade(const float* verts, const float* normals, const uint8_t* colors, int64_t nv, const int64_t* faces, int64_t nf,
+                  const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
+                  const uint8_t* rgb, const int8_t* label, float alpha, uint8_t* out, int64_t* counts, void* stream) {
+    if (nv < 0 || nf < 0 || n_frames < 0 || H <= 0 || W <= 0) return DH_ERR_BAD_ARG;
+    if (alpha != alpha || alpha < 0.f || alpha > 1.f || (label == nullptr) != (counts == nullptr)) return DH_ERR_BAD_ARG;
+    if (nf >= ((int64_t)1 << 32) || n_frames >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;   // the z-buffer's limits
+    if (H > (1 << 24) || W > (1 << 24)) return DH_ERR_UNSUPPORTED;
+    if (n_frames > (((int64_t)1 << 62) / H) / W) return DH_ERR_UNSUPPORTED;                        // pixel indices in int64
+    if (n_frames == 0) return DH_OK;
+    if (!zbuf || !R || !T || !K || !out || (nf > 0 && (!verts || !normals || !faces))) return DH_ERR_BAD_ARG;
+    const int64_t bytes = n_frames * H * W * 3;
+    if (rgb && rgb < out + bytes && out < rgb + bytes) return DH_ERR_BAD_ARG;                     // out must not overlap rgb
+    return launch_mesh_shade(verts, normals, colors, nv, faces, nf, zbuf, R, T, K, n_frames, H, W, rgb, label, alpha, out, counts,
+                             static_cast<hipStream_t>(stream));
+}
 
 }  // extern "C"

@@ -176,5 +176,9 @@ int launch_mesh_raster_depth(const float* verts, int64_t nv, const int64_t* face
 int launch_mesh_bake_colors(const float* verts, const float* normals, int64_t nv, const uint8_t* rgb, const uint8_t* usable,
                             const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
                             float depth_eps, float min_cos, float* acc, int32_t* n_views, hipStream_t st);
+// mesh overlay (mesh_vis.hip): the z-buffer's faces shaded and composited over the frames, silhouette counts against the labels
+int launch_mesh_shade(const float* verts, const float* normals, const uint8_t* colors, int64_t nv, const int64_t* faces, int64_t nf,
+                      const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
+                      const uint8_t* rgb, const int8_t* label, float alpha, uint8_t* out, int64_t* counts, hipStream_t st);
 
 }  // namespace dh

@@ -4,7 +4,7 @@
 // Projection, in fp32 and in this order (the order of dh_mesh_mask_votes, csrc/mesh_clean.hip):
 //   c_r = fma(R_r2, z, fma(R_r1, y, R_r0 * x)) + T_r            (r = 0, 1, 2: x_cam = R v + T)
 //   u = fma(K02, c_2, fma(K01, c_1, K00 * c_0)) / c_2,   w = fma(K12, c_2, fma(K11, c_1, K10 * c_0)) / c_2
-// Pixel centres sit at integer (u, w).
+// Pixel centres sit at integer (u, w).  mk_project and mk_edge (below) live in mesh_raster.h, shared with csrc/mesh_vis.hip.
 //
 // mesh_raster_kernel: one lane per (frame, face), frame-major.  A face is skipped when a vertex has c_2 <= 1e-3 or a non-finite
 // (u, w), when its screen area is 0, or when its box of pixel centres, clipped to the image, is empty.  Edge functions in fp32:
@@ -30,36 +30,17 @@
 #include <math.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "mesh_raster.h"
 
 namespace dh {
 
 namespace {
 constexpr int MK_THREADS = 256;
 constexpr int MK_SMALL_BOX = 32;
-constexpr uint64_t MK_EMPTY = ~(uint64_t)0;
 
 inline unsigned mk_grid(int64_t n) {
     const int64_t b = (n + MK_THREADS - 1) / MK_THREADS;
     return (unsigned)(b < (1 << 20) ? b : (1 << 20));      // grid-stride loops cover the rest
-}
-
-struct Cam {
-    float c0, c1, c2, u, w;
-};
-
-__device__ inline Cam mk_project(const float* Rf, const float* Tf, float k00, float k01, float k02, float k10, float k11, float k12,
-                                 float x, float y, float z) {
-    Cam c;
-    c.c0 = __builtin_fmaf(Rf[2], z, __builtin_fmaf(Rf[1], y, Rf[0] * x)) + Tf[0];
-    c.c1 = __builtin_fmaf(Rf[5], z, __builtin_fmaf(Rf[4], y, Rf[3] * x)) + Tf[1];
-    c.c2 = __builtin_fmaf(Rf[8], z, __builtin_fmaf(Rf[7], y, Rf[6] * x)) + Tf[2];
-    c.u = __builtin_fmaf(k02, c.c2, __builtin_fmaf(k01, c.c1, k00 * c.c0)) / c.c2;
-    c.w = __builtin_fmaf(k12, c.c2, __builtin_fmaf(k11, c.c1, k10 * c.c0)) / c.c2;
-    return c;
-}
-
-__device__ inline float mk_edge(float au, float aw, float bu, float bw, float pu, float pw) {
-    return __builtin_fmaf(bu - au, pw - aw, -((bw - aw) * (pu - au)));
 }
 
 // The screen-space face one lane (or, in the wave phase, the whole wave) rasterises.

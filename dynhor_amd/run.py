@@ -5,6 +5,7 @@
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode evaluate_mesh --is_continue   # Chamfer / F-score, one JSON line
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode evaluate_mesh --is_continue --mesh_clean mask+largest
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode validate_mesh --is_continue --mesh_color views+network
+    python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode visualize_mesh --is_continue --turntable 36   # overlays, IoU
 
 With --gpus N > 1 this process starts N ranks (one per GPU) through dynhor_amd.launch before it touches the GPU and exits
 with their code; under an external `torch.distributed.run` (WORLD_SIZE set) it is one of the ranks.
@@ -17,7 +18,8 @@ import sys
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config_path", type=str, required=True)
-    ap.add_argument("--mode", type=str, default="train", choices=["train", "validate_image", "validate_mesh", "evaluate_mesh"])
+    ap.add_argument("--mode", type=str, default="train",
+                    choices=["train", "validate_image", "validate_mesh", "evaluate_mesh", "visualize_mesh"])
     ap.add_argument("--is_continue", action="store_true")
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks on this node (one process per GPU)")
@@ -28,11 +30,19 @@ def main():
     ap.add_argument("--gt_mesh", type=str, default=None, help="evaluate_mesh: ground-truth mesh (.obj / .ply)")
     ap.add_argument("--gt_normalize", type=str, default=None, choices=["none", "reference"],
                     help="evaluate_mesh: 'reference' = bring the ground truth into the canonical frame (mean 0, max vertex norm 0.5)")
-    ap.add_argument("--mesh_resolution", type=int, default=None, help="evaluate_mesh: marching-cubes grid of the reconstruction")
+    ap.add_argument("--mesh_resolution", type=int, default=None,
+                    help="evaluate_mesh / visualize_mesh: marching-cubes grid of the reconstruction")
     ap.add_argument("--mesh_clean", type=str, default=None, choices=["none", "mask", "largest", "mask+largest"],
-                    help="validate_mesh / evaluate_mesh: clean the extracted mesh (default: the config's mesh_clean.mode, else none)")
+                    help="validate_mesh / evaluate_mesh / visualize_mesh: clean the mesh (default: the config's mesh_clean.mode, "
+                         "else none)")
     ap.add_argument("--mesh_color", type=str, default=None, choices=["none", "views", "network", "views+network"],
-                    help="validate_mesh: colour the mesh and also write <iter>_color.ply (default: the config's mesh_color.mode, else none)")
+                    help="validate_mesh: colour the mesh and also write <iter>_color.ply; visualize_mesh: shade with the vertex colours "
+                         "(default: the config's mesh_color.mode, else none)")
+    # visualize_mesh only (defaults: the config's mesh_vis: block, else the reconstruction at --mesh_resolution, no turntable)
+    ap.add_argument("--vis_mesh", type=str, default=None, help="visualize_mesh: draw this mesh (.ply / .obj) instead of the reconstruction")
+    ap.add_argument("--vis_normalize", type=str, default=None, choices=["none", "reference"],
+                    help="visualize_mesh: 'reference' = bring --vis_mesh into the canonical frame (mean 0, max vertex norm 0.5)")
+    ap.add_argument("--turntable", type=int, default=None, help="visualize_mesh: frames of render_res/<iter>/turntable.gif (0: none)")
     args = ap.parse_args()
 
     from . import launch
@@ -68,6 +78,14 @@ def main():
                                    clean=args.mesh_clean)
         if runner.rank == 0:
             import json
+            print(json.dumps(res), flush=True)
+    elif args.mode == "visualize_mesh":
+        res = runner.visualize_mesh(mesh=args.vis_mesh, normalize=args.vis_normalize, resolution=args.mesh_resolution,
+                                    clean=args.mesh_clean, color=args.mesh_color, turntable=args.turntable)
+        if runner.rank == 0:
+            import json
+            res = {k: v for k, v in res.items() if k != "frames"}
+            res["dir"] = runner.last_vis_dir
             print(json.dumps(res), flush=True)
     else:
         print("surface crossings", runner.validate_mesh(clean=args.mesh_clean, color=args.mesh_color)[1])

@@ -61,6 +61,11 @@ MESH_CLEAN_DEFAULTS = {"mode": "none", "dilate_px": 2, "min_bg_votes": 1, "min_a
 # the optional mesh_color: block of the YAML (validate_mesh; dynhor_amd/mesh_color.py)
 MESH_COLOR_DEFAULTS = {"mode": "none", "erode_px": 1, "min_cos": 0.1, "depth_eps": 0.01}
 
+# the optional mesh_vis: block of the YAML (visualize_mesh; dynhor_amd/mesh_vis.py): mesh None = the reconstruction at `resolution`;
+# normalize "none" | "reference" for a mesh file; turntable = frames of the orbit GIF (0: none)
+MESH_VIS_DEFAULTS = {"mesh": None, "normalize": "none", "resolution": 512, "alpha": 0.6, "turntable": 0}
+VIS_WRITERS = 8                  # JPEG writer threads of visualize_mesh (a fixed pool: JPEG encoding is host work)
+
 
 def _merge(base, over):
     out = dict(base)
@@ -156,6 +161,7 @@ class Runner:
         self.last_clean_stats = None     # validate_mesh / evaluate_mesh with cleaning: mesh_clean.clean_mesh's counts
         self.last_mesh_colors = None     # validate_mesh with colouring: mesh_color.color_mesh's u8 [V,3] colours and its stats
         self.last_color_stats = None
+        self.last_vis_dir = None         # visualize_mesh: the render_res/<iter> directory it wrote
         if is_continue:
             ck_dir = os.path.join(self.base_exp_dir, "checkpoints")
             ck = sorted(f for f in os.listdir(ck_dir) if f.endswith(".pth")) if os.path.isdir(ck_dir) else []
@@ -540,6 +546,91 @@ class Runner:
             for k, v in res.items():
                 if k != "iter" and isinstance(v, (int, float)):
                     self._board.add_scalar("eval/" + k, float(v), self.iter_step)
+            self._board.flush()
+        return res
+
+    @torch.no_grad()
+    def visualize_mesh(self, mesh=None, normalize=None, resolution=None, clean=None, color=None, alpha=None, turntable=None, save=True):
+        """The mesh drawn over every frame at the dataset's current poses (refined ones included) and its silhouette IoU against the
+        object labels, hand pixels excluded (dynhor_amd/mesh_vis.py).  The mesh: the reconstruction, extracted as validate_mesh
+        extracts it at `resolution` (no .ply written), or the .ply / .obj file `mesh` (metrics.load_mesh), taken as in the canonical
+        frame (normalize "none") or normalised as the reference normalises its prior (normalize "reference").  clean / color: the
+        mesh_clean / mesh_color modes of validate_mesh (None: the config's blocks), applied to whichever mesh is drawn; with a colour
+        mode the shading uses the vertex colours.  Arguments left at None take the YAML's optional mesh_vis: block over
+        MESH_VIS_DEFAULTS.  Rank 0 writes render_res/<iter:08d>/<stem>.jpg for every frame (quality 95), silhouette.json (the summary
+        plus iter, mesh, clean, color, alpha), turntable.gif when turntable > 0 (orbit_cameras, 100 ms per frame, looping), and logs
+        vis/iou_mean, vis/iou_median, vis/iou_min to <exp>/board.  Returns the mesh_vis.silhouette_summary dict with those keys (the
+        other ranks return None)."""
+        from . import metrics
+        from .mesh_vis import orbit_cameras, overlay_frames, silhouette_summary, turntable as render_turntable
+        if self.rank != 0:
+            return None
+        vc = dict(MESH_VIS_DEFAULTS)
+        vc.update(self.conf.get("mesh_vis") or {})
+        pick = lambda v, key: v if v is not None else vc[key]
+        mesh, normalize = pick(mesh, "mesh"), pick(normalize, "normalize")
+        resolution, alpha, n_turn = int(pick(resolution, "resolution")), float(pick(alpha, "alpha")), int(pick(turntable, "turntable"))
+        if normalize not in ("none", "reference"):
+            raise ValueError(f"visualize_mesh: normalize must be 'none' or 'reference', got {normalize!r}")
+        if mesh is None:
+            verts, faces = self.validate_mesh(resolution=resolution, save=False, clean="none", color="none")
+            name = f"reconstruction@{resolution}"
+        else:
+            verts, faces = metrics.load_mesh(str(mesh))
+            if normalize == "reference":
+                verts = metrics.normalize_like_reference(verts)[0]
+            verts, faces = verts.to(self.device).contiguous(), faces.to(self.device).contiguous()
+            name = str(mesh)
+        cmode = self._clean_conf(clean)["mode"]
+        if cmode != "none":
+            verts, faces = self._clean_mesh(verts, faces, clean)
+        cc = self._color_conf(color)
+        colors = None
+        if cc["mode"] != "none":
+            from .mesh_color import color_mesh
+            colors, self.last_color_stats = color_mesh(verts, faces, cc["mode"], dataset=self.dataset, renderer=self.renderer,
+                                                       erode_px=int(cc["erode_px"]), min_cos=float(cc["min_cos"]),
+                                                       depth_eps=float(cc["depth_eps"]))
+        ds = self.dataset
+        stems = list(ds.stems) if ds.stems is not None else ["{:04d}".format(i) for i in range(ds.n_images)]
+        d = os.path.join(self.base_exp_dir, "render_res", "{:0>8d}".format(self.iter_step))
+        sink, pool, pending = None, None, []
+        if save:
+            from concurrent.futures import ThreadPoolExecutor
+            from PIL import Image
+            os.makedirs(d, exist_ok=True)
+            pool = ThreadPoolExecutor(max_workers=VIS_WRITERS)
+
+            def write(path, img):
+                Image.fromarray(img).save(path, quality=95)
+
+            def sink(f0, out):
+                host = out.cpu().numpy()
+                pending.extend(pool.submit(write, os.path.join(d, stems[f0 + k] + ".jpg"), host[k]) for k in range(host.shape[0]))
+        try:
+            counts = overlay_frames(verts, faces, ds, colors=colors, alpha=alpha, sink=sink)
+            res = silhouette_summary(counts.cpu(), stems)
+            res.update(iter=self.iter_step, mesh=name, clean=cmode, color=cc["mode"], alpha=alpha)
+            if save and n_turn > 0:
+                Ro, To = orbit_cameras(ds.R, ds.T, n_turn)
+                imgs = render_turntable(verts, faces, ds.K, ds.H, ds.W, Ro, To, colors=colors).cpu().numpy()
+                frames = [Image.fromarray(im) for im in imgs]
+                frames[0].save(os.path.join(d, "turntable.gif"), save_all=True, append_images=frames[1:], duration=100, loop=0)
+        finally:
+            for fut in pending:
+                fut.result()
+            if pool is not None:
+                pool.shutdown()
+        if save:
+            with open(os.path.join(d, "silhouette.json"), "w") as f:
+                json.dump(res, f, indent=1)
+            self.last_vis_dir = d
+            if self._board is None:
+                from .tb_events import make_writer
+                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+            for k in ("iou_mean", "iou_median", "iou_min"):
+                if res[k] is not None:
+                    self._board.add_scalar("vis/" + k, float(res[k]), self.iter_step)
             self._board.flush()
         return res
 

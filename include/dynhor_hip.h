@@ -453,6 +453,26 @@ int dh_mesh_bake_colors(const float* verts, const float* normals, int64_t nv, co
                         const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
                         float depth_eps, float min_cos, float* acc, int32_t* n_views, void* stream);
 
+/* ---- mesh overlay (dynhor_amd/mesh_vis.py: the mesh drawn over every frame, silhouette agreement with the object labels) ----
+ * dh_mesh_shade: for each pixel of n_frames frames of H x W, out u8 [n_frames,H,W,3].  zbuf u64 [n_frames,H,W] is the buffer
+ * dh_mesh_raster_depth left for the same mesh, cameras and image size.  A pixel is covered when its key is not UINT64_MAX, its face
+ * i = key & 0xffffffff is < nf and the three vertex indices of faces[i] lie in [0, nv); only then is the face read.  A covered pixel
+ * centre (x, y) of frame f: the face's vertices are projected as above and the three edge functions of dh_mesh_raster_depth give
+ * e0, e1, e2 at (x, y) (the rasteriser's own fp32 code: coverage and barycentrics agree with the z-buffer bit for bit); the weights are
+ * l_j = (e_j / z_j) / sum_m (e_m / z_m), the normal n = sum_j l_j normals_j (normals [nv,3], unit, object frame) and the shading term
+ * s = |(R_f n).z| / |n| (0 when |n| is 0).  base = colors ? sum_j l_j colors_j / 255 (colors u8 [nv,3]) : (0.8, 0.46, 0.51);
+ * c = min(1, base (0.3 + 0.7 s)) -- a double-sided headlight along the optical axis; o = alpha c + (1 - alpha) bg with bg = rgb / 255
+ * (rgb u8 [n_frames,H,W,3]; 1 when rgb is null); out = floor(255 o + 0.5).  An uncovered pixel copies rgb byte for byte (255 without
+ * rgb).  The mesh is drawn over hand pixels too.  label i8 [n_frames,H,W] (1 object, 0 background, -1 hand) and counts int64
+ * [n_frames,3] go together: over the pixels with label >= 0 the call ADDS to counts[f] (tp, fp, fn) = (covered and label 1, covered and
+ * label 0, uncovered and label 1); the caller zeroes counts.  Integer atomics after a per-wave reduction: output and counts are bitwise
+ * reproducible.  out must not overlap rgb.  With nf == 0 every pixel is uncovered and verts, normals, faces may be null; n_frames == 0:
+ * no-op.  DH_ERR_BAD_ARG: null required pointer, negative count, H or W < 1, alpha NaN or outside [0, 1], exactly one of label / counts
+ * null, out overlapping rgb.  DH_ERR_UNSUPPORTED: nf >= 2^32, n_frames >= 2^31, H or W > 2^24, n_frames H W >= 2^62. */
+int dh_mesh_shade(const float* verts, const float* normals, const uint8_t* colors, int64_t nv, const int64_t* faces, int64_t nf,
+                  const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
+                  const uint8_t* rgb, const int8_t* label, float alpha, uint8_t* out, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
