@@ -93,6 +93,9 @@ SIGNATURES = {
     "dh_mesh_raster_depth": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "dh_mesh_bake_colors": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _vp, _vp, _vp]),
     "dh_mesh_shade": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "dh_mc_block_points": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp]),
+    "dh_mc_count": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dh_mc_emit": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _i64, _vp, _vp, _vp]),
 }
 
 

@@ -642,4 +642,41 @@ int dh_mesh_shade(const float* verts, const float* normals, const uint8_t* color
                              static_cast<hipStream_t>(stream));
 }
 
+// shared argument rules of the three dh_mc_* entry points: 2 <= N <= 2^20 grid points per axis, 1 <= B <= 16 cells per block edge,
+// fewer than 2^31 blocks per call (one workgroup each)
+static int mc_args(int64_t nb, int N, int B) {
+    if (nb < 0 || N < 2 || B < 1) return DH_ERR_BAD_ARG;
+    if (N > (1 << 20) || B > 16 || nb >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;
+    return DH_OK;
+}
+
+int dh_mc_block_points(const float* ax, const float* ay, const float* az, int N, const int32_t* blocks, int64_t nb, int B, float* pts,
+                       void* stream) {
+    const int rc = mc_args(nb, N, B);
+    if (rc != DH_OK || nb == 0) return rc;
+    if (!ax || !ay || !az || !blocks || !pts) return DH_ERR_BAD_ARG;
+    return launch_mc_block_points(ax, ay, az, N, blocks, nb, B, pts, static_cast<hipStream_t>(stream));
+}
+
+int dh_mc_count(const float* vals, const int32_t* blocks, int64_t nb, int N, int B, float threshold, const uint8_t* table,
+                const int32_t* block_map, int32_t* counts, int32_t* cut_faces, int32_t* nonfinite, void* stream) {
+    const int rc = mc_args(nb, N, B);
+    if (rc != DH_OK) return rc;
+    if (threshold != threshold) return DH_ERR_BAD_ARG;
+    if (nb == 0) return DH_OK;
+    if (!vals || !blocks || !table || !block_map || !counts || !cut_faces || !nonfinite) return DH_ERR_BAD_ARG;
+    return launch_mc_count(vals, blocks, nb, N, B, threshold, table, block_map, counts, cut_faces, nonfinite,
+                           static_cast<hipStream_t>(stream));
+}
+
+int dh_mc_emit(const float* vals, const int32_t* blocks, int64_t nb, int N, int B, float threshold, const uint8_t* table,
+               const int64_t* offsets, int64_t n_tri, int64_t* keys, float* pos, void* stream) {
+    const int rc = mc_args(nb, N, B);
+    if (rc != DH_OK) return rc;
+    if (threshold != threshold || n_tri < 0) return DH_ERR_BAD_ARG;
+    if (nb == 0 || n_tri == 0) return DH_OK;
+    if (!vals || !blocks || !table || !offsets || !keys || !pos) return DH_ERR_BAD_ARG;
+    return launch_mc_emit(vals, blocks, nb, N, B, threshold, table, offsets, n_tri, keys, pos, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -181,4 +181,12 @@ int launch_mesh_shade(const float* verts, const float* normals, const uint8_t* c
                       const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
                       const uint8_t* rgb, const int8_t* label, float alpha, uint8_t* out, int64_t* counts, hipStream_t st);
 
+// block-sparse marching cubes (mesh_extract.hip): sample points of the listed blocks, triangles and cut faces per block, triangle emit
+int launch_mc_block_points(const float* ax, const float* ay, const float* az, int N, const int32_t* blocks, int64_t nb, int B, float* pts,
+                           hipStream_t st);
+int launch_mc_count(const float* vals, const int32_t* blocks, int64_t nb, int N, int B, float threshold, const uint8_t* table,
+                    const int32_t* block_map, int32_t* counts, int32_t* cut_faces, int32_t* nonfinite, hipStream_t st);
+int launch_mc_emit(const float* vals, const int32_t* blocks, int64_t nb, int N, int B, float threshold, const uint8_t* table,
+                   const int64_t* offsets, int64_t n_tri, int64_t* keys, float* pos, hipStream_t st);
+
 }  // namespace dh

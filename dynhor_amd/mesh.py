@@ -13,14 +13,25 @@ _CORNERS = torch.tensor([[0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0], [0, 0, 1], 
 _TETS = torch.tensor([[0, 1, 3, 7], [0, 3, 2, 7], [0, 2, 6, 7], [0, 6, 4, 7], [0, 4, 5, 7], [0, 5, 1, 7]])
 
 
+# the dense weld key min * N^3 + max of two linear grid indices (< N^3 each) is below N^6: 1448^6 < 2^63 < 1449^6
+MAX_DENSE_RESOLUTION = 1448
+
+
+def _check_weld_key_range(fn, N):
+    if N > MAX_DENSE_RESOLUTION:
+        raise ValueError(f"{fn}: resolution {N} > {MAX_DENSE_RESOLUTION}: the edge keys min * N^3 + max overflow int64 (vertices would be "
+                         "welded by wrapped keys); use the sparse extraction mode (dynhor_amd/mesh_extract.py), whose keys fit at any N")
+
+
 def marching_tetrahedra(u: torch.Tensor, threshold: float, bound_min, bound_max):
     """u [N,N,N] scalar field (upstream convention: u = -sdf, inside > threshold).  Returns (vertices [V,3] float32 in
     world units, triangles [T,3] int64).  A surface vertex lies on a grid EDGE and is identified by that edge (the pair of corner
     indices): every tetrahedron sharing the edge computes the same position from the same end, and vertices are welded by that
     key -- the mesh is watertight by construction (round 4: welding by quantised positions left a few cracks where the two ends'
-    roundings differed; tests/test_cpu_mesh.py)."""
+    roundings differed; tests/test_cpu_mesh.py).  N <= 1448 (MAX_DENSE_RESOLUTION): the key min * N^3 + max must fit int64."""
     dev = u.device
     N = u.shape[0]
+    _check_weld_key_range("marching_tetrahedra", N)
     bmin = torch.as_tensor(bound_min, dtype=torch.float32, device=dev)
     bmax = torch.as_tensor(bound_max, dtype=torch.float32, device=dev)
     # active cells first (8 shifted views of the grid: no per-cell index tensors for the empty 99 % of the volume)
@@ -211,9 +222,12 @@ def marching_cubes_table():
 
 def marching_cubes(u: torch.Tensor, threshold: float, bound_min, bound_max):
     """Table-driven marching cubes on u [N,N,N] (u = -sdf, inside > threshold): same interface, vertex welding (by grid edge) and
-    orientation as marching_tetrahedra; about a third of its triangles."""
+    orientation as marching_tetrahedra; about a third of its triangles.  N <= 1448 (MAX_DENSE_RESOLUTION: the weld key min * N^3 +
+    max of an edge's two linear indices must fit int64; ValueError beyond).  mesh_extract.sparse_marching_cubes builds the same mesh
+    from the blocks near the surface with a key that fits at any N."""
     dev = u.device
     N = u.shape[0]
+    _check_weld_key_range("marching_cubes", N)
     bmin = torch.as_tensor(bound_min, dtype=torch.float32, device=dev)
     bmax = torch.as_tensor(bound_max, dtype=torch.float32, device=dev)
     f = u - threshold

@@ -125,6 +125,7 @@ class NeuSRenderer:
         self._ws = None
         self._ws_token = 0
         self.timer = StageTimer()
+        self.last_extract_stats = None   # extract_geometry(mode="sparse"): mesh_extract.sparse_marching_cubes' counts
         # the arithmetic of this renderer's MLP stages (_lib.ARITH_SPLIT_F16 / ARITH_SPLIT_BF16 / ARITH_FP32_MFMA), passed with
         # every launch through the `_ex` entry points: no process-global word is read, so renderers with different arithmetics
         # can run side by side, also from different host threads.  None = the library's default at the time of each call.
@@ -228,16 +229,30 @@ class NeuSRenderer:
 
     # ------------------------------------------------------------------ geometry extraction (upstream extract_geometry)
     @torch.no_grad()
-    def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, method="cubes"):
+    def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, method="cubes", mode="dense", block=8, lipschitz=None):
         """Upstream NeuSRenderer.extract_geometry(bound_min, bound_max, resolution, threshold): -sdf on a regular grid
         (HIP no-grad SDF kernel, 64^3-point chunks), iso-surface at `threshold`.  Returns (vertices [V,3], triangles [F,3])
         as device tensors.  method "cubes" (default since round 5): table-driven marching cubes, upstream's algorithm
         (mcubes.marching_cubes; PyMCubes itself is not installable here, the case table is generated in dynhor_amd/mesh.py);
-        "tetrahedra": marching tetrahedra (rounds 1-4), three times the triangles."""
+        "tetrahedra": marching tetrahedra (rounds 1-4), three times the triangles.
+        mode "dense" (default) queries every grid point, and its weld keys limit it to resolution <= 1448; "sparse" queries only the
+        blocks of `block`^3 cells whose centre value is within lipschitz x the block radius of the threshold and triangulates them in
+        HIP (dynhor_amd/mesh_extract.py: the same mesh for the same field values, no resolution limit; lipschitz None =
+        mesh_extract.DEFAULT_LIPSCHITZ; marching cubes only).  The counts of a sparse run are left in self.last_extract_stats."""
         from .mesh import marching_cubes, marching_tetrahedra
         if method not in ("cubes", "tetrahedra"):
             raise ValueError("extract_geometry: method must be 'cubes' or 'tetrahedra'")
+        if mode not in ("dense", "sparse"):
+            raise ValueError("extract_geometry: mode must be 'dense' or 'sparse'")
+        if mode == "sparse" and method != "cubes":
+            raise ValueError("extract_geometry: mode 'sparse' triangulates by marching cubes only (method 'cubes')")
         dev = self.store.device
+        if mode == "sparse":
+            from . import mesh_extract
+            verts, faces, self.last_extract_stats = mesh_extract.sparse_marching_cubes(
+                lambda p: -self.sdf(p), resolution, bound_min, bound_max, threshold=threshold, block=block,
+                lipschitz=mesh_extract.DEFAULT_LIPSCHITZ if lipschitz is None else lipschitz, device=dev)
+            return verts, faces
         N = int(resolution)
         ax = [torch.linspace(float(bound_min[i]), float(bound_max[i]), N, device=dev) for i in range(3)]
         u = torch.empty(N, N, N, device=dev)

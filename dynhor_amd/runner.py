@@ -22,6 +22,7 @@ from . import dist as dh_dist
 from . import schedules
 from .dataset import Dataset
 from .fields import ParamStore, RenderingNetwork, SDFNetwork, SingleVarianceNetwork
+from .mesh_extract import DEFAULT_LIPSCHITZ
 from .renderer import NeuSRenderer
 
 DEFAULT_CONF = {
@@ -60,6 +61,11 @@ MESH_CLEAN_DEFAULTS = {"mode": "none", "dilate_px": 2, "min_bg_votes": 1, "min_a
 
 # the optional mesh_color: block of the YAML (validate_mesh; dynhor_amd/mesh_color.py)
 MESH_COLOR_DEFAULTS = {"mode": "none", "erode_px": 1, "min_cos": 0.1, "depth_eps": 0.01}
+
+# the optional mesh_extract: block of the YAML (validate_mesh / evaluate_mesh / visualize_mesh; dynhor_amd/mesh_extract.py): mode "dense"
+# queries the whole grid; "sparse" only the blocks of `block`^3 cells whose centre value lies within lipschitz x the block radius of the
+# threshold (the same mesh, no resolution limit).  lipschitz: mesh_extract.DEFAULT_LIPSCHITZ says where the number comes from
+MESH_EXTRACT_DEFAULTS = {"mode": "dense", "block": 8, "lipschitz": DEFAULT_LIPSCHITZ}
 
 # the optional mesh_vis: block of the YAML (visualize_mesh; dynhor_amd/mesh_vis.py): mesh None = the reconstruction at `resolution`;
 # normalize "none" | "reference" for a mesh file; turntable = frames of the orbit GIF (0: none)
@@ -161,6 +167,7 @@ class Runner:
         self.last_clean_stats = None     # validate_mesh / evaluate_mesh with cleaning: mesh_clean.clean_mesh's counts
         self.last_mesh_colors = None     # validate_mesh with colouring: mesh_color.color_mesh's u8 [V,3] colours and its stats
         self.last_color_stats = None
+        self.last_extract_stats = None   # validate_mesh / evaluate_mesh / visualize_mesh with sparse extraction: its counts
         self.last_vis_dir = None         # visualize_mesh: the render_res/<iter> directory it wrote
         if is_continue:
             ck_dir = os.path.join(self.base_exp_dir, "checkpoints")
@@ -425,7 +432,7 @@ class Runner:
         return psnr
 
     @torch.no_grad()
-    def validate_mesh(self, resolution=64, threshold=0.0, world_space=False, save=True, clean=None, color=None):
+    def validate_mesh(self, resolution=64, threshold=0.0, world_space=False, save=True, clean=None, color=None, extract=None):
         """Upstream Runner.validate_mesh / NeuSRenderer.extract_geometry: -sdf on a regular grid over
         the object bounding box (HIP no-grad SDF kernel, 64^3-point chunks), iso-surface by marching cubes (model.mesh_method: 'cubes' | 'tetrahedra')
         (dynhor_amd/mesh.py; mcubes is not available), written as meshes/<iter>.ply.  Returns (vertices, triangles).
@@ -434,11 +441,18 @@ class Runner:
         self.last_clean_stats).
         color: a mesh_color.color_mesh mode (None: the config's mesh_color.mode, default "none").  With a mode other than "none" the
         returned mesh is coloured and additionally written as <iter>_color.ply (colours and stats in self.last_mesh_colors /
-        self.last_color_stats); <iter>.ply and <iter>_clean.ply are unchanged."""
+        self.last_color_stats); <iter>.ply and <iter>_clean.ply are unchanged.
+        extract: "dense" | "sparse" (None: the config's mesh_extract.mode, default "dense"): how the grid is queried
+        (NeuSRenderer.extract_geometry's mode; block and lipschitz from the config's mesh_extract: block).  Sparse gives the same mesh
+        from far fewer SDF queries and leaves its counts in self.last_extract_stats."""
         from .mesh import write_ply
         bmin, bmax = self.dataset.object_bbox_min, self.dataset.object_bbox_max
+        ec = self._extract_conf(extract)
         verts, faces = self.renderer.extract_geometry(bmin, bmax, resolution=resolution, threshold=threshold,
-                                                      method=self.conf.get("model", {}).get("mesh_method", "cubes"))
+                                                      method=self.conf.get("model", {}).get("mesh_method", "cubes"),
+                                                      mode=ec["mode"], block=int(ec["block"]), lipschitz=float(ec["lipschitz"]))
+        self.last_extract_stats = dict(self.renderer.last_extract_stats, mode="sparse", block=int(ec["block"]),
+                                       lipschitz=float(ec["lipschitz"])) if ec["mode"] == "sparse" else None
         d = os.path.join(self.base_exp_dir, "meshes")
         if save and self.rank == 0:
             os.makedirs(d, exist_ok=True)
@@ -470,6 +484,21 @@ class Runner:
             raise ValueError(f"mesh_color mode must be one of {MODES}, got {c['mode']!r}")
         return c
 
+    def _extract_conf(self, mode=None):
+        """The YAML's optional mesh_extract: block over MESH_EXTRACT_DEFAULTS; `mode` (when not None) overrides its mode."""
+        from .mesh_extract import MAX_BLOCK, MODES
+        c = dict(MESH_EXTRACT_DEFAULTS)
+        c.update(self.conf.get("mesh_extract") or {})
+        if mode is not None:
+            c["mode"] = mode
+        if c["mode"] not in MODES:
+            raise ValueError(f"mesh_extract mode must be one of {MODES}, got {c['mode']!r}")
+        if isinstance(c["block"], bool) or not isinstance(c["block"], int) or not 1 <= c["block"] <= MAX_BLOCK:
+            raise ValueError(f"mesh_extract block must be an integer in [1, {MAX_BLOCK}], got {c['block']!r}")
+        if isinstance(c["lipschitz"], bool) or not isinstance(c["lipschitz"], (int, float)) or not c["lipschitz"] > 0:
+            raise ValueError(f"mesh_extract lipschitz must be a number > 0, got {c['lipschitz']!r}")
+        return c
+
     def _clean_conf(self, mode=None):
         """The YAML's optional mesh_clean: block over MESH_CLEAN_DEFAULTS; `mode` (when not None) overrides its mode."""
         from .mesh_clean import MODES
@@ -491,7 +520,7 @@ class Runner:
 
     @torch.no_grad()
     def evaluate_mesh(self, gt_mesh=None, gt_normalize=None, resolution=None, n_samples=None, taus=None, seed=0, save=True,
-                      gt_resolution=None, clean=None):
+                      gt_resolution=None, clean=None, extract=None):
         """Geometry metrics of the current reconstruction against a ground-truth surface (dynhor_amd/metrics.py: Chamfer distance,
         F-score, normal consistency; definitions in its docstring).  The mesh is extracted as validate_mesh does (renderer
         extract_geometry over the object bounding box, model.mesh_method) at `resolution`, then scored by metrics.mesh_metrics.
@@ -504,6 +533,9 @@ class Runner:
         (0.005, 0.01, 0.02).  data_info.obj_path is NOT ground truth (the reference's stage-1 shape prior) and is never used.
         clean: a mesh_clean.clean_mesh mode (None: the config's mesh_clean.mode, default "none"); with a mode other than "none" the
         cleaned mesh is scored and the dict gains clean, clean_removed_verts, clean_removed_faces and clean_components.
+        extract: validate_mesh's extraction mode (None: the config's mesh_extract.mode).  With "sparse" the reconstruction AND the
+        analytic ground truth are extracted sparsely (the ground truth at lipschitz 1, exact for that field) and the dict gains
+        extract, extract_block, extract_lipschitz, extract_blocks, extract_active_blocks, extract_samples and extract_dense_samples.
         Rank 0 writes meshes/<iter:08d>_eval.json and logs every number as eval/<key> to <exp>/board.  Returns the dict."""
         from . import metrics
         ev = self.conf.get("eval") or {}
@@ -518,13 +550,13 @@ class Runner:
             gt_v, gt_f = metrics.load_mesh(gt_mesh)
             gt_name = str(gt_mesh)
         elif getattr(self.dataset, "synthetic", False):
-            gt_v, gt_f = self._scene_gt_mesh(gt_resolution)
+            gt_v, gt_f = self._scene_gt_mesh(gt_resolution, mode=self._extract_conf(extract)["mode"])
             gt_name = f"scene_sdf@{gt_resolution}"
             gt_normalize = "none"                      # the analytic scene is defined in the canonical frame
         else:
             raise ValueError("evaluate_mesh: no ground truth -- pass gt_mesh (or set eval.gt_mesh in the config); only a synthetic "
                              "dataset has one built in")
-        verts, faces = self.validate_mesh(resolution=resolution, save=False, clean="none")
+        verts, faces = self.validate_mesh(resolution=resolution, save=False, clean="none", extract=extract)
         mode = self._clean_conf(clean)["mode"]
         if mode != "none":
             verts, faces = self._clean_mesh(verts, faces, clean)
@@ -535,6 +567,11 @@ class Runner:
             st = self.last_clean_stats
             res.update(clean=mode, clean_removed_verts=st["removed_verts"], clean_removed_faces=st["removed_faces"],
                        clean_components=st["components"])
+        es = self.last_extract_stats
+        if es is not None:
+            res.update(extract="sparse", extract_block=es["block"], extract_lipschitz=es["lipschitz"], extract_blocks=es["blocks"],
+                       extract_active_blocks=es["active_blocks"], extract_samples=es["samples"],
+                       extract_dense_samples=es["dense_samples"])
         if save and self.rank == 0:
             d = os.path.join(self.base_exp_dir, "meshes")
             os.makedirs(d, exist_ok=True)
@@ -550,14 +587,15 @@ class Runner:
         return res
 
     @torch.no_grad()
-    def visualize_mesh(self, mesh=None, normalize=None, resolution=None, clean=None, color=None, alpha=None, turntable=None, save=True):
+    def visualize_mesh(self, mesh=None, normalize=None, resolution=None, clean=None, color=None, alpha=None, turntable=None, save=True,
+                       extract=None):
         """The mesh drawn over every frame at the dataset's current poses (refined ones included) and its silhouette IoU against the
         object labels, hand pixels excluded (dynhor_amd/mesh_vis.py).  The mesh: the reconstruction, extracted as validate_mesh
         extracts it at `resolution` (no .ply written), or the .ply / .obj file `mesh` (metrics.load_mesh), taken as in the canonical
         frame (normalize "none") or normalised as the reference normalises its prior (normalize "reference").  clean / color: the
         mesh_clean / mesh_color modes of validate_mesh (None: the config's blocks), applied to whichever mesh is drawn; with a colour
-        mode the shading uses the vertex colours.  Arguments left at None take the YAML's optional mesh_vis: block over
-        MESH_VIS_DEFAULTS.  Rank 0 writes render_res/<iter:08d>/<stem>.jpg for every frame (quality 95), silhouette.json (the summary
+        mode the shading uses the vertex colours.  extract: validate_mesh's extraction mode for the reconstruction.  Arguments left at
+        None take the YAML's optional mesh_vis: block over MESH_VIS_DEFAULTS.  Rank 0 writes render_res/<iter:08d>/<stem>.jpg for every frame (quality 95), silhouette.json (the summary
         plus iter, mesh, clean, color, alpha), turntable.gif when turntable > 0 (orbit_cameras, 100 ms per frame, looping), and logs
         vis/iou_mean, vis/iou_median, vis/iou_min to <exp>/board.  Returns the mesh_vis.silhouette_summary dict with those keys (the
         other ranks return None)."""
@@ -573,7 +611,7 @@ class Runner:
         if normalize not in ("none", "reference"):
             raise ValueError(f"visualize_mesh: normalize must be 'none' or 'reference', got {normalize!r}")
         if mesh is None:
-            verts, faces = self.validate_mesh(resolution=resolution, save=False, clean="none", color="none")
+            verts, faces = self.validate_mesh(resolution=resolution, save=False, clean="none", color="none", extract=extract)
             name = f"reconstruction@{resolution}"
         else:
             verts, faces = metrics.load_mesh(str(mesh))
@@ -634,12 +672,19 @@ class Runner:
             self._board.flush()
         return res
 
-    def _scene_gt_mesh(self, resolution, chunk=1 << 22):
+    def _scene_gt_mesh(self, resolution, chunk=1 << 22, mode="dense"):
         """Zero level set of the synthetic scene's analytic SDF (scene.scene_sdf) by mesh.marching_cubes over [-0.55, 0.55]^3
-        (the object lies inside the radius-0.5 ball), the SDF evaluated on the device in chunks.  Cached per resolution."""
+        (the object lies inside the radius-0.5 ball), the SDF evaluated on the device in chunks.  mode "sparse": by
+        mesh_extract.sparse_marching_cubes at lipschitz 1 (a distance field's exact constant), block 8.  Cached per resolution and mode."""
         from .mesh import marching_cubes
         from .scene import scene_sdf
         cache = self.__dict__.setdefault("_gt_meshes", {})
+        if mode == "sparse":
+            if (resolution, mode) not in cache:
+                from .mesh_extract import sparse_marching_cubes
+                cache[(resolution, mode)] = sparse_marching_cubes(lambda p: -scene_sdf(p), int(resolution), [-0.55] * 3, [0.55] * 3,
+                                                                  lipschitz=1.0, device=self.device)[:2]
+            return cache[(resolution, mode)]
         if resolution not in cache:
             N = int(resolution)
             ax = torch.linspace(-0.55, 0.55, N, device=self.device)

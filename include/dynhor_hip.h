@@ -473,6 +473,33 @@ int dh_mesh_shade(const float* verts, const float* normals, const uint8_t* color
                   const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
                   const uint8_t* rgb, const int8_t* label, float alpha, uint8_t* out, int64_t* counts, void* stream);
 
+/* ---- block-sparse marching cubes (dynhor_amd/mesh_extract.py: the iso-surface from the blocks near it only) ----
+ * The grid has N points per axis, cut into nbk = ceil((N - 1) / B) blocks of B cells per axis; block (bx, by, bz) of blocks int32 [nb,3]
+ * covers the grid indices [b B, min(b B + B, N - 1)] and carries P^3 samples, P = B + 1, sample (i, j, k) of block n at row n P^3 +
+ * (i P + j) P + k; samples of a clipped end block beyond N - 1 are padding.  table u8 [256,16]: row = case (bit n = corner n above the
+ * threshold, corners (0,0,0) (1,0,0) (1,1,0) (0,1,0) (0,0,1) (1,0,1) (1,1,1) (0,1,1)), bytes 0..14 the edge ids of up to five
+ * triangles (edge e joins the corners 01 12 23 30 45 56 67 74 04 15 26 37), byte 15 their number.  No state is kept.
+ * dh_mc_block_points: pts f32 [nb P^3,3] = (ax[gx], ay[gy], az[gz]), READ from the axis arrays f32 [N] (the bits of a dense grid meshed
+ * from them); padding repeats index N - 1.
+ * dh_mc_count: vals f32 [nb P^3] = the field at those samples.  counts[n] (int32) = the triangles of block n: over its cells (indices
+ * < N - 1) the table's count for the case of u - threshold > 0.  *cut_faces (int32, zeroed by the caller, integer atomic) gains the
+ * cell faces on a block's boundary whose four corners disagree and whose neighbour block lies inside the grid with block_map < 0
+ * (block_map int32 [nbk,nbk,nbk], >= 0 for every listed block).  *nonfinite (int32, zeroed by the caller) becomes 1 when a value is NaN
+ * or infinite.  A block outside [0, nbk)^3 counts nothing.
+ * dh_mc_emit: offsets int64 [nb] = the exclusive prefix sum of counts, n_tri their total.  Triangle offsets[n] + m of block n is the
+ * m-th in (cell (i, j, k) lexicographic, table) order; row r = 3 (offsets[n] + m) + c of its corner c receives keys[r] (int64) =
+ * lin(g) 3 + a and pos f32 [r,3]: the corner lies on the grid edge from g (the end with the smaller lin = (gx N + gy) N + gz) along
+ * z / y / x for a = 0 / 1 / 2; v0 = u(g) - threshold, v1 the other end's, t = min(max(v0 / (v0 - v1), 0), 1) in fp32 with IEEE
+ * division, pos = g in grid units with t added along the edge.  No atomics: bitwise reproducible.  Rows >= 3 n_tri are never written.
+ * nb == 0 (or n_tri == 0): no-op.  DH_ERR_BAD_ARG: null pointer, negative count, N < 2, B < 1, NaN threshold.  DH_ERR_UNSUPPORTED:
+ * N > 2^20, B > 16, nb >= 2^31. */
+int dh_mc_block_points(const float* ax, const float* ay, const float* az, int N, const int32_t* blocks, int64_t nb, int B, float* pts,
+                       void* stream);
+int dh_mc_count(const float* vals, const int32_t* blocks, int64_t nb, int N, int B, float threshold, const uint8_t* table,
+                const int32_t* block_map, int32_t* counts, int32_t* cut_faces, int32_t* nonfinite, void* stream);
+int dh_mc_emit(const float* vals, const int32_t* blocks, int64_t nb, int N, int B, float threshold, const uint8_t* table,
+               const int64_t* offsets, int64_t n_tri, int64_t* keys, float* pos, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
