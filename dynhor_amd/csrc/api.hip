@@ -578,6 +578,48 @@ int dh_nearest_sqdist(const float* q, int64_t nq, const float* ref, int64_t nr, 
     return launch_nearest_sqdist(q, nq, ref, nr, d2, idx, ws, static_cast<hipStream_t>(stream));
 }
 
+// shared limits of the ICP entry points: the grid's y / z dimensions carry slabs and hypotheses (65535 each), indices are int32
+static int icp_args(int64_t n, int64_t m, int64_t h) {
+    if (n < 0 || m < 0 || h < 0) return DH_ERR_BAD_ARG;
+    if (m >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31) || h > 65535) return DH_ERR_UNSUPPORTED;
+    return DH_OK;
+}
+
+int64_t dh_icp_correspond_workspace(int64_t n, int64_t m, int64_t h) {
+    const int rc = icp_args(n, m, h);
+    if (rc != DH_OK) return rc;
+    return icp_correspond_workspace(n, m, h);
+}
+
+int dh_icp_correspond(const float* src, int64_t n, const float* tgt, int64_t m, const float* xf, int64_t h, float* d2, int32_t* idx,
+                      void* ws, void* stream) {
+    const int rc = icp_args(n, m, h);
+    if (rc != DH_OK) return rc;
+    if (n == 0 || h == 0) return DH_OK;
+    if (!src || !tgt || !xf || !d2 || !idx || m == 0 || misaligned16(ws)) return DH_ERR_BAD_ARG;
+    return launch_icp_correspond(src, n, tgt, m, xf, h, d2, idx, ws, static_cast<hipStream_t>(stream));
+}
+
+int dh_icp_moments_sums(int plane) { return icp_moments_sums(plane != 0); }
+
+int64_t dh_icp_moments_workspace(int64_t n, int64_t h, int plane) {
+    const int rc = icp_args(n, 0, h);
+    if (rc != DH_OK) return rc;
+    return icp_moments_workspace(n, h, plane != 0);
+}
+
+int dh_icp_moments(const float* src, const float* tgt, const float* tgt_normals, const float* xf, const int32_t* idx, const float* d2,
+                   const float* thr, const float* origin_src, const float* origin_tgt, int64_t n, int64_t m, int64_t h, double* out,
+                   void* ws, void* stream) {
+    const int rc = icp_args(n, m, h);
+    if (rc != DH_OK) return rc;
+    if (h == 0) return DH_OK;
+    // n == 0 still zeroes out (the sums of no pairs); every pointer is needed either way
+    if (!src || !tgt || !xf || !idx || !d2 || !thr || !origin_src || !origin_tgt || !out || !ws || misaligned16(ws)) return DH_ERR_BAD_ARG;
+    return launch_icp_moments(src, tgt, tgt_normals, xf, idx, d2, thr, origin_src, origin_tgt, n, m, h, out, ws,
+                              static_cast<hipStream_t>(stream));
+}
+
 int dh_label_dilate(const int8_t* label, int64_t n_frames, int H, int W, int radius, uint8_t* tmp, uint8_t* keep, void* stream) {
     if (n_frames < 0 || H <= 0 || W <= 0 || radius < 0) return DH_ERR_BAD_ARG;
     if (n_frames == 0) return DH_OK;

@@ -1,0 +1,148 @@
+// Moment sums of trimmed ICP (dynhor_amd/mesh_align.py): for every hypothesis h and every source sample i whose correspondence
+// (idx[h,i], d2[h,i]; icp_correspond_kernel in nn.hip) passes the trim threshold d2 <= thr[h], the sums the closed-form update needs.
+//
+// Point-to-point (no target normals), ICP_POINT_SUMS = 19 per hypothesis, with p = src_i - origin_src (the source as given, NOT
+// transformed: the update is the absolute similarity) and q = tgt[idx] - origin_tgt:
+//   [0] count  [1..3] sum p  [4..6] sum q  [7..15] sum q p^T (row-major: entry 7 + 3 r + c = sum q_r p_c)  [16] sum |p|^2
+//   [17] sum |q|^2  [18] sum sqrt(d2)
+// Point-to-plane (target normals given), ICP_PLANE_SUMS = 36: with x = A_h src_i + t_h (fp64 arithmetic on the fp32 transform),
+// y = x - origin_tgt, q as above, n the target sample's normal, the Jacobian row J = (y x n, n, n . y) of the residual n . (y - q)
+// linearised in (rotation vector, translation, log-scale) about origin_tgt, and b = -n . (y - q):
+//   [0..27] the upper triangle of sum J^T J, row by row (00 01 .. 06 11 12 .. 66)  [28..34] sum J^T b  [35] count
+//
+// Everything is accumulated in fp64.  Determinism: workgroup g of a hypothesis owns the samples g * 256 + t + k * (256 * blocks), each
+// lane adds its own in ascending order, the 64 lanes of a wave fold by a fixed xor butterfly, the four waves are added in order, and the
+// workgroup STORES its partial; icp_moments_reduce_kernel then adds the partials in block order.  No atomics: a launch is bitwise
+// reproducible.  The products are small because both clouds are centred on the origins the caller passes (their centroids).
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include "kernels.h"
+
+namespace dh {
+
+namespace {
+constexpr int ICP_THREADS = 256;
+constexpr int ICP_POINT_SUMS = 19;
+constexpr int ICP_PLANE_SUMS = 36;
+constexpr int64_t ICP_MAX_BLOCKS = 128;        // workgroups per hypothesis (each sample is read once; the partials stay few)
+
+int64_t icp_blocks(int64_t n) {
+    const int64_t b = (n + ICP_THREADS - 1) / ICP_THREADS;
+    return b < 1 ? 1 : (b < ICP_MAX_BLOCKS ? b : ICP_MAX_BLOCKS);
+}
+}  // namespace
+
+// grid (blocks, hypotheses); partial [H, blocks, K] doubles
+template <bool PLANE>
+__global__ __launch_bounds__(ICP_THREADS) void icp_moments_kernel(const float* __restrict__ src, const float* __restrict__ tgt,
+                                                                  const float* __restrict__ nrm, const float* __restrict__ xf,
+                                                                  const int32_t* __restrict__ idx, const float* __restrict__ d2,
+                                                                  const float* __restrict__ thr, const float* __restrict__ osrc,
+                                                                  const float* __restrict__ otgt, int64_t n, int64_t m,
+                                                                  double* __restrict__ partial) {
+    constexpr int K = PLANE ? ICP_PLANE_SUMS : ICP_POINT_SUMS;
+    __shared__ double wave_sum[ICP_THREADS / 64][K];
+    const int h = blockIdx.y;
+    const float limit = thr[h];
+    const float* a = xf + 12 * (int64_t)h;
+    const double os[3] = {osrc[0], osrc[1], osrc[2]}, ot[3] = {otgt[0], otgt[1], otgt[2]};
+    double acc[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * ICP_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * ICP_THREADS + threadIdx.x; i < n; i += stride) {
+        const float d = d2[(int64_t)h * n + i];
+        const int32_t j = idx[(int64_t)h * n + i];
+        // a NaN distance fails the comparison; an index outside the target (a search that found nothing: -1) is never read
+        if (!(d <= limit) || j < 0 || j >= m) continue;
+        const double p[3] = {src[i * 3 + 0], src[i * 3 + 1], src[i * 3 + 2]};
+        const double q[3] = {tgt[(int64_t)j * 3 + 0] - ot[0], tgt[(int64_t)j * 3 + 1] - ot[1], tgt[(int64_t)j * 3 + 2] - ot[2]};
+        if (!PLANE) {
+            const double pc[3] = {p[0] - os[0], p[1] - os[1], p[2] - os[2]};
+            acc[0] += 1.0;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                acc[1 + r] += pc[r];
+                acc[4 + r] += q[r];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[7 + 3 * r + c] += q[r] * pc[c];
+            }
+            acc[16] += pc[0] * pc[0] + pc[1] * pc[1] + pc[2] * pc[2];
+            acc[17] += q[0] * q[0] + q[1] * q[1] + q[2] * q[2];
+            acc[18] += sqrt((double)d);
+        } else {
+            double y[3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+                y[r] = (double)a[3 * r] * p[0] + (double)a[3 * r + 1] * p[1] + (double)a[3 * r + 2] * p[2] + (double)a[9 + r] - ot[r];
+            const double nv[3] = {nrm[(int64_t)j * 3 + 0], nrm[(int64_t)j * 3 + 1], nrm[(int64_t)j * 3 + 2]};
+            double J[7];
+            J[0] = y[1] * nv[2] - y[2] * nv[1];
+            J[1] = y[2] * nv[0] - y[0] * nv[2];
+            J[2] = y[0] * nv[1] - y[1] * nv[0];
+            J[3] = nv[0]; J[4] = nv[1]; J[5] = nv[2];
+            J[6] = nv[0] * y[0] + nv[1] * y[1] + nv[2] * y[2];
+            const double b = -(nv[0] * (y[0] - q[0]) + nv[1] * (y[1] - q[1]) + nv[2] * (y[2] - q[2]));
+            int e = 0;
+#pragma unroll
+            for (int r = 0; r < 7; ++r)
+#pragma unroll
+                for (int c = r; c < 7; ++c) acc[e++] += J[r] * J[c];
+#pragma unroll
+            for (int r = 0; r < 7; ++r) acc[28 + r] += J[r] * b;
+            acc[35] += 1.0;
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double v = acc[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) wave_sum[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < K) {
+        double v = wave_sum[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < ICP_THREADS / 64; ++w) v += wave_sum[w][threadIdx.x];
+        partial[((int64_t)h * gridDim.x + blockIdx.x) * K + threadIdx.x] = v;
+    }
+}
+
+// grid (hypotheses), K threads: out[h, k] = the partials of hypothesis h added in block order
+__global__ void icp_moments_reduce_kernel(const double* __restrict__ partial, int blocks, int K, double* __restrict__ out) {
+    const int k = threadIdx.x;
+    if (k >= K) return;
+    const double* p = partial + (int64_t)blockIdx.x * blocks * K + k;
+    double v = 0.0;
+    for (int b = 0; b < blocks; ++b) v += p[(int64_t)b * K];
+    out[(int64_t)blockIdx.x * K + k] = v;
+}
+
+int icp_moments_sums(int plane) { return plane ? ICP_PLANE_SUMS : ICP_POINT_SUMS; }
+
+int64_t icp_moments_workspace(int64_t n, int64_t h, int plane) {
+    return h * icp_blocks(n) * icp_moments_sums(plane) * (int64_t)sizeof(double);
+}
+
+int launch_icp_moments(const float* src, const float* tgt, const float* nrm, const float* xf, const int32_t* idx, const float* d2,
+                       const float* thr, const float* osrc, const float* otgt, int64_t n, int64_t m, int64_t h, double* out, void* ws,
+                       hipStream_t st) {
+    const int64_t blocks = icp_blocks(n);
+    double* partial = static_cast<double*>(ws);
+    const dim3 grid((unsigned)blocks, (unsigned)h);
+    if (nrm)
+        hipLaunchKernelGGL((icp_moments_kernel<true>), grid, dim3(ICP_THREADS), 0, st, src, tgt, nrm, xf, idx, d2, thr, osrc, otgt, n, m,
+                           partial);
+    else
+        hipLaunchKernelGGL((icp_moments_kernel<false>), grid, dim3(ICP_THREADS), 0, st, src, tgt, nrm, xf, idx, d2, thr, osrc, otgt, n, m,
+                           partial);
+    if (hipGetLastError() != hipSuccess) return -3;
+    const int K = icp_moments_sums(nrm != nullptr);
+    hipLaunchKernelGGL(icp_moments_reduce_kernel, dim3((unsigned)h), dim3(64), 0, st, partial, (int)blocks, K, out);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+}  // namespace dh

@@ -164,6 +164,18 @@ int launch_hash_weight_grads(const float* params, const float* hp, int64_t n, fl
 int64_t nearest_sqdist_workspace(int64_t nq, int64_t nr);
 int launch_nearest_sqdist(const float* q, int64_t nq, const float* ref, int64_t nr, float* d2, int32_t* idx, void* ws, hipStream_t st);
 
+// similarity ICP (dynhor_amd/mesh_align.py).  Correspondences (nn.hip): the sweep of launch_nearest_sqdist for h hypotheses at once,
+// the source transformed on load by xf [h,12]; ws = icp_correspond_workspace(n, m, h) bytes, or null (one slab).  Moment sums of the
+// pairs inside the trim threshold (icp.hip): icp_moments_sums(plane) doubles per hypothesis, ws = icp_moments_workspace(n, h, plane) bytes
+int64_t icp_correspond_workspace(int64_t n, int64_t m, int64_t h);
+int launch_icp_correspond(const float* src, int64_t n, const float* tgt, int64_t m, const float* xf, int64_t h, float* d2, int32_t* idx,
+                          void* ws, hipStream_t st);
+int icp_moments_sums(int plane);
+int64_t icp_moments_workspace(int64_t n, int64_t h, int plane);
+int launch_icp_moments(const float* src, const float* tgt, const float* nrm, const float* xf, const int32_t* idx, const float* d2,
+                       const float* thr, const float* osrc, const float* otgt, int64_t n, int64_t m, int64_t h, double* out, void* ws,
+                       hipStream_t st);
+
 // mesh cleaning (mesh_clean.hip): label dilation, silhouette votes per vertex, connected components by union-find
 int launch_label_dilate(const int8_t* label, int64_t n_frames, int H, int W, int radius, uint8_t* tmp, uint8_t* keep, hipStream_t st);
 int launch_mesh_mask_votes(const float* verts, int64_t nv, const uint8_t* keep, const float* R, const float* T, const float* K,

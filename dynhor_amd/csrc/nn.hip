@@ -10,6 +10,8 @@
 // Small query counts (e.g. 37 x 10^6) would leave most CUs idle: the reference range is then cut into S slabs (grid.y), each slab
 // writes its (d, idx) pair into the caller's scratch, and nn_merge_kernel takes the lexicographic minimum over the slabs in ascending
 // order -- the same pair the one-slab sweep finds, bit for bit.
+// The sweep is one body, nn_sweep<XF>: nn_sqdist_kernel is its plain form; icp_correspond_kernel (dynhor_amd/mesh_align.py: the
+// correspondence search of similarity ICP) is the same sweep for H hypotheses in grid.z, each transforming the query point on load.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -32,8 +34,9 @@ struct NnPlan {
     int64_t slabs, slab_len;
 };
 
-NnPlan nn_plan(int64_t nq, int64_t nr) {
-    const int64_t qb = (nq + NN_QPB - 1) / NN_QPB;
+// h: launches of the same sweep side by side (grid.z: the hypotheses of icp_correspond_kernel; 1 for nn_sqdist_kernel)
+NnPlan nn_plan(int64_t nq, int64_t nr, int64_t h = 1) {
+    const int64_t qb = (nq + NN_QPB - 1) / NN_QPB * h;
     int64_t s = 1;
     if (qb > 0 && qb < NN_TARGET_BLOCKS && nr > 0) {
         s = (NN_TARGET_BLOCKS + qb - 1) / qb;
@@ -48,12 +51,14 @@ NnPlan nn_plan(int64_t nq, int64_t nr) {
 }
 }  // namespace
 
-// grid (query blocks, slabs).  Slab s covers references [s * slab_len, min(nr, (s + 1) * slab_len)) and writes its pairs at
-// d2 + s * out_stride / idx + s * out_stride (idx may be null: distances only).
-__global__ __launch_bounds__(NN_THREADS) void nn_sqdist_kernel(const float* __restrict__ q, int64_t nq, const float* __restrict__ ref,
-                                                               int64_t nr, int64_t slab_len, float* __restrict__ d2,
-                                                               int32_t* __restrict__ idx, int64_t out_stride) {
-    __shared__ float4 tile[NN_TILE];
+// The sweep of one workgroup: NN_QPB queries against the references of slab blockIdx.y, [s * slab_len, min(nr, (s + 1) * slab_len)); the
+// pairs go to od / oi (oi may be null: distances only).  XF: the query is x = A p + t of the point p read from q, with xf = A row-major
+// (9) then t (3), in fp32 and in this order for every row r: x_r = fma(A_r2, p.z, fma(A_r1, p.y, fma(A_r0, p.x, t_r))).  Both kernels
+// below are this one body, so a transformed sweep gives the bits nn_sqdist_kernel gives on points transformed by that formula.
+template <bool XF>
+__device__ __forceinline__ void nn_sweep(float4* __restrict__ tile, const float* __restrict__ q, int64_t nq, const float* __restrict__ ref,
+                                         int64_t nr, int64_t slab_len, const float* __restrict__ xf, float* __restrict__ od,
+                                         int32_t* __restrict__ oi) {
     const int t = threadIdx.x;
     const int64_t q0 = (int64_t)blockIdx.x * NN_QPB + t;
     float qx[NN_K], qy[NN_K], qz[NN_K], best[NN_K];
@@ -65,6 +70,12 @@ __global__ __launch_bounds__(NN_THREADS) void nn_sqdist_kernel(const float* __re
         qx[k] = in ? q[i * 3 + 0] : 0.f;
         qy[k] = in ? q[i * 3 + 1] : 0.f;
         qz[k] = in ? q[i * 3 + 2] : 0.f;
+        if (XF) {
+            const float px = qx[k], py = qy[k], pz = qz[k];
+            qx[k] = __builtin_fmaf(xf[2], pz, __builtin_fmaf(xf[1], py, __builtin_fmaf(xf[0], px, xf[9])));
+            qy[k] = __builtin_fmaf(xf[5], pz, __builtin_fmaf(xf[4], py, __builtin_fmaf(xf[3], px, xf[10])));
+            qz[k] = __builtin_fmaf(xf[8], pz, __builtin_fmaf(xf[7], py, __builtin_fmaf(xf[6], px, xf[11])));
+        }
         best[k] = INFINITY;
         bi[k] = -1;
     }
@@ -98,8 +109,6 @@ __global__ __launch_bounds__(NN_THREADS) void nn_sqdist_kernel(const float* __re
             }
         }
     }
-    float* od = d2 + (int64_t)blockIdx.y * out_stride;
-    int32_t* oi = idx ? idx + (int64_t)blockIdx.y * out_stride : nullptr;
 #pragma unroll
     for (int k = 0; k < NN_K; ++k) {
         const int64_t i = q0 + (int64_t)k * NN_THREADS;
@@ -110,12 +119,34 @@ __global__ __launch_bounds__(NN_THREADS) void nn_sqdist_kernel(const float* __re
     }
 }
 
+// grid (query blocks, slabs).  Slab s writes its pairs at d2 + s * out_stride / idx + s * out_stride (idx may be null).
+__global__ __launch_bounds__(NN_THREADS) void nn_sqdist_kernel(const float* __restrict__ q, int64_t nq, const float* __restrict__ ref,
+                                                               int64_t nr, int64_t slab_len, float* __restrict__ d2,
+                                                               int32_t* __restrict__ idx, int64_t out_stride) {
+    __shared__ float4 tile[NN_TILE];
+    nn_sweep<false>(tile, q, nq, ref, nr, slab_len, nullptr, d2 + (int64_t)blockIdx.y * out_stride,
+                    idx ? idx + (int64_t)blockIdx.y * out_stride : nullptr);
+}
+
+// ICP correspondences (dynhor_amd/mesh_align.py): grid (source blocks, slabs, hypotheses).  Hypothesis h transforms the source by
+// xf + 12 h on load and writes slab s at d2 + (h * gridDim.y + s) * n (one slab: the caller's [H,N] arrays themselves).
+__global__ __launch_bounds__(NN_THREADS) void icp_correspond_kernel(const float* __restrict__ src, int64_t n, const float* __restrict__ tgt,
+                                                                    int64_t m, int64_t slab_len, const float* __restrict__ xf,
+                                                                    float* __restrict__ d2, int32_t* __restrict__ idx) {
+    __shared__ float4 tile[NN_TILE];
+    const int64_t o = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * n;
+    nn_sweep<true>(tile, src, n, tgt, m, slab_len, xf + 12 * (int64_t)blockIdx.z, d2 + o, idx + o);
+}
+
 // lexicographic minimum of the slabs' (d, idx) pairs, slabs in ascending order with a strict `<`: ties keep the lower slab, whose
 // indices are the smaller ones
 __global__ __launch_bounds__(256) void nn_merge_kernel(const float* __restrict__ pd, const int32_t* __restrict__ pi, int64_t nq, int slabs,
                                                        float* __restrict__ d2, int32_t* __restrict__ idx) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= nq) return;
+    // blockIdx.y: the hypothesis of an ICP launch (its slabs lie together); 0 for dh_nearest_sqdist
+    pd += (int64_t)blockIdx.y * slabs * nq;
+    pi += (int64_t)blockIdx.y * slabs * nq;
     float b = pd[i];
     int32_t bi = pi[i];
     for (int s = 1; s < slabs; ++s) {
@@ -125,8 +156,8 @@ __global__ __launch_bounds__(256) void nn_merge_kernel(const float* __restrict__
             bi = pi[(int64_t)s * nq + i];
         }
     }
-    d2[i] = b;
-    if (idx) idx[i] = bi;
+    d2[(int64_t)blockIdx.y * nq + i] = b;
+    if (idx) idx[(int64_t)blockIdx.y * nq + i] = bi;
 }
 
 int64_t nearest_sqdist_workspace(int64_t nq, int64_t nr) {
@@ -148,6 +179,30 @@ int launch_nearest_sqdist(const float* q, int64_t nq, const float* ref, int64_t 
                        pi, nq);
     if (hipGetLastError() != hipSuccess) return -3;
     hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, pd, pi, nq, (int)p.slabs, d2, idx);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int64_t icp_correspond_workspace(int64_t n, int64_t m, int64_t h) {
+    const NnPlan p = nn_plan(n, m, h);
+    return p.slabs > 1 ? h * p.slabs * n * (int64_t)(sizeof(float) + sizeof(int32_t)) : 0;
+}
+
+int launch_icp_correspond(const float* src, int64_t n, const float* tgt, int64_t m, const float* xf, int64_t h, float* d2, int32_t* idx,
+                          void* ws, hipStream_t st) {
+    const int64_t qb = (n + NN_QPB - 1) / NN_QPB;
+    const NnPlan p = ws ? nn_plan(n, m, h) : NnPlan{1, m};
+    if (p.slabs == 1) {
+        hipLaunchKernelGGL((icp_correspond_kernel), dim3((unsigned)qb, 1, (unsigned)h), dim3(NN_THREADS), 0, st, src, n, tgt, m, m, xf, d2,
+                           idx);
+        return hipGetLastError() == hipSuccess ? 0 : -3;
+    }
+    // scratch: the slabs' distances [h, slabs, n] floats, then their indices [h, slabs, n] int32
+    float* pd = static_cast<float*>(ws);
+    int32_t* pi = reinterpret_cast<int32_t*>(pd + h * p.slabs * n);
+    hipLaunchKernelGGL((icp_correspond_kernel), dim3((unsigned)qb, (unsigned)p.slabs, (unsigned)h), dim3(NN_THREADS), 0, st, src, n, tgt, m,
+                       p.slab_len, xf, pd, pi);
+    if (hipGetLastError() != hipSuccess) return -3;
+    hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)h), dim3(256), 0, st, pd, pi, n, (int)p.slabs, d2, idx);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

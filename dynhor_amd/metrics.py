@@ -14,7 +14,8 @@ The definitions are those of the NeuS / HHOR line of papers, on point samples of
 Distances are in the frame the meshes are given in -- for this project the canonical object frame (the object inside the
 radius-0.5 ball; dataset.py ``_load_from_disk``).  ``normalize_like_reference`` brings a ground-truth mesh in its own units into
 that frame the way the reference normalises its shape prior; the metrics then carry ``gt_scale``, the factor from canonical
-back to ground-truth units.
+back to ground-truth units.  That fixes no rotation and depends on the scan's tessellation: ``mesh_metrics(gt_align=...)`` registers
+the ground truth to the prediction by trimmed similarity ICP first (dynhor_amd/mesh_align.py; off by default).
 """
 from __future__ import annotations
 
@@ -212,6 +213,23 @@ def normalize_like_reference(verts: torch.Tensor):
     return ((v - center) * scale).to(verts.dtype), center.to(verts.dtype), scale
 
 
+def check_align_args(fn, gt_align, gt_align_init):
+    """ValueError unless gt_align is none | rigid | similarity and gt_align_init is identity | global."""
+    if gt_align not in ("none", "rigid", "similarity"):
+        raise ValueError(f"{fn}: gt_align must be 'none', 'rigid' or 'similarity', got {gt_align!r}")
+    if gt_align_init not in ("identity", "global"):
+        raise ValueError(f"{fn}: gt_align_init must be 'identity' or 'global', got {gt_align_init!r}")
+
+
+def aligned_ground_truth(gt_v: torch.Tensor, res: dict, gt_normalize: str = "none") -> torch.Tensor:
+    """The ground-truth vertices in the prediction's frame, from the file's vertices and a mesh_metrics result that carries an
+    alignment: normalize_like_reference first when gt_normalize is "reference", then align_scale align_R x + align_t (fp64)."""
+    from .mesh_align import apply_transform
+    if gt_normalize == "reference":
+        gt_v = normalize_like_reference(gt_v)[0]
+    return apply_transform(gt_v, res["align_scale"], res["align_R"], res["align_t"])
+
+
 # ------------------------------------------------------------------------------------------------ surface sampling
 def sample_surface(verts: torch.Tensor, faces: torch.Tensor, n: int, generator, return_faces: bool = False):
     """n points on the mesh, on the device of `verts`: a triangle is drawn with probability proportional to its area (CDF in
@@ -267,15 +285,24 @@ def distance_metrics(d2_pg: torch.Tensor, d2_gp: torch.Tensor, taus=(0.005, 0.01
 
 
 def mesh_metrics(pred_v, pred_f, gt_v, gt_f, n_samples: int = 1_000_000, taus=(0.005, 0.01, 0.02), seed: int = 0,
-                 gt_normalize: str = "none", device=None) -> dict:
+                 gt_normalize: str = "none", device=None, gt_align: str = "none", gt_align_init: str = "identity",
+                 align_opts: dict | None = None) -> dict:
     """Score the predicted mesh (pred_v [V,3], pred_f [F,3]) against the ground truth (gt_v, gt_f); the metric definitions are in
     the module docstring.  n_samples points on each mesh, drawn from one generator seeded with `seed` (prediction first).
     gt_normalize "reference": the ground truth is first brought into the canonical frame by normalize_like_reference, and the
     result carries gt_scale (canonical -> ground-truth units) besides the metrics, n_samples, n_pred_faces and n_gt_faces.
     The sampling and the nearest-neighbour search run on `device` (default: the device of pred_v if it is one, else the current
-    one).  An empty predicted (or ground-truth) mesh raises ValueError."""
+    one).  An empty predicted (or ground-truth) mesh raises ValueError.
+    gt_align "rigid" | "similarity": the ground truth (after gt_normalize, which is then simply the initial guess) is first registered
+    to the prediction by trimmed ICP (mesh_align.align_meshes; gt_align_init "identity" starts there, "global" searches the rotations;
+    align_opts over mesh_align.ALIGN_DEFAULTS, n_align included) on samples of a generator of its own, so the scoring samples of the
+    prediction are the ones drawn without it.  The dict then gains gt_align, gt_align_init, align_scale, align_R (row-major list of
+    9), align_t (x' = align_scale align_R x + align_t takes the normalised ground truth into the prediction's frame), the registration's
+    stats prefixed align_, and gt_scale = 1 / (align_scale x normalisation scale), the total factor from canonical back to
+    ground-truth units.  With "none" (the default) nothing of this runs and the dict is what it always was."""
     if gt_normalize not in ("none", "reference"):
         raise ValueError(f"mesh_metrics: gt_normalize must be 'none' or 'reference', got {gt_normalize!r}")
+    check_align_args("mesh_metrics", gt_align, gt_align_init)
     if pred_f.shape[0] == 0 or pred_v.shape[0] == 0:
         raise ValueError("mesh_metrics: the predicted mesh is empty (no faces): the reconstruction has no surface to score "
                          "(is the zero level set inside the extraction box?)")
@@ -288,6 +315,14 @@ def mesh_metrics(pred_v, pred_f, gt_v, gt_f, n_samples: int = 1_000_000, taus=(0
     if gt_normalize == "reference":
         gt_v, _, scale = normalize_like_reference(gt_v)
         extra["gt_scale"] = 1.0 / scale
+    if gt_align != "none":
+        from . import mesh_align
+        a_s, a_R, a_t, st = mesh_align.align_meshes(gt_v, gt_f, pred_v, pred_f, mode=gt_align, init=gt_align_init, seed=seed,
+                                                    device=device, **(align_opts or {}))
+        gt_v = mesh_align.apply_transform(gt_v, a_s, a_R, a_t)
+        extra.update(gt_align=gt_align, gt_align_init=gt_align_init, align_scale=a_s, align_R=[float(x) for x in a_R.reshape(-1)],
+                     align_t=[float(x) for x in a_t], gt_scale=extra.get("gt_scale", 1.0) / a_s,
+                     **{"align_" + k: v for k, v in st.items()})
     g = torch.Generator(device=device).manual_seed(int(seed))
     p, pn = sample_surface(pred_v.to(device, torch.float32), pred_f, n_samples, g)
     q, qn = sample_surface(gt_v, gt_f, n_samples, g)

@@ -4,6 +4,7 @@
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --gpus 8        # frames shard 8-way data-parallel (RCCL)
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode evaluate_mesh --is_continue   # Chamfer / F-score, one JSON line
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode evaluate_mesh --is_continue --mesh_clean mask+largest
+    python -m dynhor_amd.run --config_path X.yaml --mode evaluate_mesh --is_continue --gt_mesh scan.ply --gt_align similarity --gt_align_init global
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode validate_mesh --is_continue --mesh_color views+network
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode validate_mesh --is_continue --mesh_extract sparse --mesh_resolution 1024
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode visualize_mesh --is_continue --turntable 36   # overlays, IoU
@@ -31,6 +32,12 @@ def main():
     ap.add_argument("--gt_mesh", type=str, default=None, help="evaluate_mesh: ground-truth mesh (.obj / .ply)")
     ap.add_argument("--gt_normalize", type=str, default=None, choices=["none", "reference"],
                     help="evaluate_mesh: 'reference' = bring the ground truth into the canonical frame (mean 0, max vertex norm 0.5)")
+    ap.add_argument("--gt_align", type=str, default=None, choices=["none", "rigid", "similarity"],
+                    help="evaluate_mesh: register the ground truth (after --gt_normalize) to the reconstruction by trimmed ICP before "
+                         "scoring it; also writes meshes/<iter>_gt_aligned.ply (default: the config's eval.gt_align, else none)")
+    ap.add_argument("--gt_align_init", type=str, default=None, choices=["identity", "global"],
+                    help="evaluate_mesh: start the registration where --gt_normalize leaves the ground truth, or search the rotations "
+                         "(default: the config's eval.gt_align_init, else identity)")
     ap.add_argument("--mesh_resolution", type=int, default=None,
                     help="validate_mesh / evaluate_mesh / visualize_mesh: marching-cubes grid of the reconstruction (validate_mesh: 64 "
                          "when unset)")
@@ -80,7 +87,8 @@ def main():
         print("psnr", runner.validate_image())
     elif args.mode == "evaluate_mesh":
         res = runner.evaluate_mesh(gt_mesh=args.gt_mesh, gt_normalize=args.gt_normalize, resolution=args.mesh_resolution,
-                                   clean=args.mesh_clean, extract=args.mesh_extract)
+                                   clean=args.mesh_clean, extract=args.mesh_extract, gt_align=args.gt_align,
+                                   gt_align_init=args.gt_align_init)
         if runner.rank == 0:
             import json
             print(json.dumps(res), flush=True)

@@ -520,7 +520,7 @@ class Runner:
 
     @torch.no_grad()
     def evaluate_mesh(self, gt_mesh=None, gt_normalize=None, resolution=None, n_samples=None, taus=None, seed=0, save=True,
-                      gt_resolution=None, clean=None, extract=None):
+                      gt_resolution=None, clean=None, extract=None, gt_align=None, gt_align_init=None, align_opts=None):
         """Geometry metrics of the current reconstruction against a ground-truth surface (dynhor_amd/metrics.py: Chamfer distance,
         F-score, normal consistency; definitions in its docstring).  The mesh is extracted as validate_mesh does (renderer
         extract_geometry over the object bounding box, model.mesh_method) at `resolution`, then scored by metrics.mesh_metrics.
@@ -536,6 +536,12 @@ class Runner:
         extract: validate_mesh's extraction mode (None: the config's mesh_extract.mode).  With "sparse" the reconstruction AND the
         analytic ground truth are extracted sparsely (the ground truth at lipschitz 1, exact for that field) and the dict gains
         extract, extract_block, extract_lipschitz, extract_blocks, extract_active_blocks, extract_samples and extract_dense_samples.
+        gt_align: "none" | "rigid" | "similarity" (None: eval.gt_align, default "none"), gt_align_init: "identity" | "global" (None:
+        eval.gt_align_init, default "identity"), align_opts: options over mesh_align.ALIGN_DEFAULTS (None: eval.align_opts).  With a mode
+        other than "none" the ground truth (after gt_normalize) is registered to the mesh that is scored -- the cleaned one when cleaning
+        is on -- by trimmed ICP before the metrics are taken (metrics.mesh_metrics says what the dict gains); rank 0 then also writes
+        meshes/<iter:08d>_gt_aligned.ply, the ground truth in the canonical frame: load it next to <iter>.ply to see the registration.
+        The analytic ground truth of a synthetic dataset accepts the flags too (it is aligned already: a self-check).
         Rank 0 writes meshes/<iter:08d>_eval.json and logs every number as eval/<key> to <exp>/board.  Returns the dict."""
         from . import metrics
         ev = self.conf.get("eval") or {}
@@ -546,6 +552,10 @@ class Runner:
         gt_resolution = int(pick(gt_resolution, "gt_resolution", 512))
         n_samples = int(pick(n_samples, "n_samples", 1_000_000))
         taus = tuple(float(t) for t in pick(taus, "taus", (0.005, 0.01, 0.02)))
+        gt_align = pick(gt_align, "gt_align", "none")
+        gt_align_init = pick(gt_align_init, "gt_align_init", "identity")
+        align_opts = pick(align_opts, "align_opts", None)
+        metrics.check_align_args("evaluate_mesh", gt_align, gt_align_init)
         if gt_mesh is not None:
             gt_v, gt_f = metrics.load_mesh(gt_mesh)
             gt_name = str(gt_mesh)
@@ -561,7 +571,7 @@ class Runner:
         if mode != "none":
             verts, faces = self._clean_mesh(verts, faces, clean)
         res = metrics.mesh_metrics(verts, faces, gt_v, gt_f, n_samples=n_samples, taus=taus, seed=seed, gt_normalize=gt_normalize,
-                                   device=self.device)
+                                   device=self.device, gt_align=gt_align, gt_align_init=gt_align_init, align_opts=align_opts)
         res.update(iter=self.iter_step, resolution=resolution, gt=gt_name)
         if mode != "none":
             st = self.last_clean_stats
@@ -577,6 +587,10 @@ class Runner:
             os.makedirs(d, exist_ok=True)
             with open(os.path.join(d, "{:0>8d}_eval.json".format(self.iter_step)), "w") as f:
                 json.dump(res, f, indent=1)
+            if gt_align != "none":
+                from .mesh import write_ply
+                write_ply(os.path.join(d, "{:0>8d}_gt_aligned.ply".format(self.iter_step)),
+                          metrics.aligned_ground_truth(gt_v, res, gt_normalize), gt_f)
             if self._board is None:
                 from .tb_events import make_writer
                 self._board = make_writer(os.path.join(self.base_exp_dir, "board"))

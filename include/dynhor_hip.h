@@ -397,6 +397,34 @@ int dh_hash_set_scatter_mode(int mode);
 int64_t dh_nearest_sqdist_workspace(int64_t nq, int64_t nr);
 int dh_nearest_sqdist(const float* q, int64_t nq, const float* ref, int64_t nr, float* d2, int32_t* idx, void* ws, void* stream);
 
+/* ---- similarity ICP (dynhor_amd/mesh_align.py: the ground-truth mesh registered to the reconstruction before it is scored) -------
+ * dh_icp_correspond: dh_nearest_sqdist for H hypotheses at once, the query transformed on load.  xf [H,12] fp32: A row-major (9), then
+ * t (3).  For source point p = src[i] and hypothesis h the query is, for every row r, x_r = fma(A_r2, p.z, fma(A_r1, p.y,
+ * fma(A_r0, p.x, t_r))) in fp32; d2[h,i] and idx[h,i] ([H,N], both required) are then exactly what dh_nearest_sqdist returns for the
+ * query x against tgt [M,3]: the same direct-form distance, the same smallest index among ties, the same -1 / +inf for a query without
+ * a finite distance, bit for bit, with or without the slab split.  ws: dh_icp_correspond_workspace(N, M, H) bytes (16-byte aligned),
+ * or NULL = one slab.  N == 0 or H == 0: no-op.
+ * DH_ERR_BAD_ARG: null pointer, negative count, M == 0 with work to do.  DH_ERR_UNSUPPORTED: N or M >= 2^31, H > 65535.
+ *
+ * dh_icp_moments: for every hypothesis the fp64 sums of the closed-form update over the pairs with d2[h,i] <= thr[h] (thr [H] fp32 on
+ * the device; a NaN distance or an index outside [0, M) is no pair).  origin_src, origin_tgt: [3] fp32 on the device (the clouds'
+ * centroids: the products stay small).  tgt_normals == NULL, point-to-point, out [H,19] with p = src[i] - origin_src (NOT transformed)
+ * and q = tgt[idx] - origin_tgt:  [0] count, [1..3] sum p, [4..6] sum q, [7..15] sum q p^T row-major, [16] sum |p|^2, [17] sum |q|^2,
+ * [18] sum sqrt(d2).  tgt_normals [M,3] given, point-to-plane, out [H,36]: y = A_h p + t_h - origin_tgt (fp64 arithmetic on the fp32
+ * xf), n the normal of target sample idx, J = (y x n, n, n . y), b = -n . (y - q):  [0..27] upper triangle of sum J^T J row by row,
+ * [28..34] sum J^T b, [35] count.  dh_icp_moments_sums(plane) returns 19 / 36.  ws: dh_icp_moments_workspace(N, H, plane) bytes, always
+ * required: every workgroup stores its partial there and a second kernel adds the partials in block order (no atomics: bitwise
+ * reproducible).  H == 0: no-op; N == 0: out is zeroed.
+ * DH_ERR_BAD_ARG: null pointer (ws included), negative count.  DH_ERR_UNSUPPORTED: as above. */
+int64_t dh_icp_correspond_workspace(int64_t n, int64_t m, int64_t h);
+int dh_icp_correspond(const float* src, int64_t n, const float* tgt, int64_t m, const float* xf, int64_t h, float* d2, int32_t* idx,
+                      void* ws, void* stream);
+int dh_icp_moments_sums(int plane);
+int64_t dh_icp_moments_workspace(int64_t n, int64_t h, int plane);
+int dh_icp_moments(const float* src, const float* tgt, const float* tgt_normals, const float* xf, const int32_t* idx, const float* d2,
+                   const float* thr, const float* origin_src, const float* origin_tgt, int64_t n, int64_t m, int64_t h, double* out,
+                   void* ws, void* stream);
+
 /* ---- mesh cleaning (dynhor_amd/mesh_clean.py: silhouette culling with the object masks of every view, connected components) ----
  * dh_label_dilate: label i8 [n_frames,H,W] (1 object / 0 background / -1 hand, Dataset.label) -> keep u8 [n_frames,H,W]:
  * keep[f,y,x] = 1 if any pixel of the square window of half-width `radius` about (x,y), clipped to the image, has label != 0 (object
