@@ -98,6 +98,12 @@ SIGNATURES = {
     "dh_mesh_raster_depth": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "dh_mesh_bake_colors": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _vp, _vp, _vp]),
     "dh_mesh_shade": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "dh_label_edt": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "dh_sil_nearest_workspace": (_i64, [_i64, _i32, _i32]),
+    "dh_sil_nearest": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "dh_sil_loss_sums": (_i32, []),
+    "dh_sil_loss_grad_workspace": (_i64, [_i64, _i32, _i32]),
+    "dh_sil_loss_grad": (_i32, [_vp, _vp, _i64, _vp, _i64] + [_vp] * 6 + [_i64, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp]),
     "dh_mc_block_points": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp]),
     "dh_mc_count": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dh_mc_emit": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _i64, _vp, _vp, _vp]),

@@ -721,4 +721,65 @@ int dh_mc_emit(const float* vals, const int32_t* blocks, int64_t nb, int N, int 
     return launch_mc_emit(vals, blocks, nb, N, B, threshold, table, offsets, n_tri, keys, pos, static_cast<hipStream_t>(stream));
 }
 
+// shared argument rules of the silhouette entry points (the z-buffer's limits; grid (rows, column blocks) / (blocks, frames))
+static int sil_args(int64_t n_frames, int H, int W) {
+    if (n_frames < 0 || H <= 0 || W <= 0) return DH_ERR_BAD_ARG;
+    if (H > (1 << 24) || W > (1 << 24) || n_frames >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;
+    if (n_frames > (((int64_t)1 << 58) / H) / W) return DH_ERR_UNSUPPORTED;
+    return DH_OK;
+}
+
+int dh_label_edt(const int8_t* label, int64_t n_frames, int H, int W, int value, int rmax, float* tmp, float* out, void* stream) {
+    const int rc = sil_args(n_frames, H, W);
+    if (rc != DH_OK) return rc;
+    if (rmax < 0 || value < -128 || value > 127) return DH_ERR_BAD_ARG;
+    if (n_frames == 0) return DH_OK;
+    if (!label || !tmp || !out) return DH_ERR_BAD_ARG;
+    if (n_frames * H >= ((int64_t)1 << 31) || W > 65535 * 256 || rmax > 2896) return DH_ERR_UNSUPPORTED;   // 2 rmax^2 < 2^24: exact in fp32
+    const int r = rmax < (H > W ? H : W) ? rmax : (H > W ? H : W);                                          // a wider window adds nothing
+    return launch_label_edt(label, n_frames, H, W, value, r, tmp, out, static_cast<hipStream_t>(stream));
+}
+
+int64_t dh_sil_nearest_workspace(int64_t n_frames, int H, int W) {
+    const int rc = sil_args(n_frames, H, W);
+    if (rc != DH_OK) return rc;
+    return sil_nearest_workspace(n_frames, H, W);
+}
+
+int dh_sil_nearest(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* R, const float* T, const float* K,
+                   int64_t n_frames, int H, int W, float rmax_px, uint64_t* near, void* ws, void* stream) {
+    if (nv < 0 || nf < 0) return DH_ERR_BAD_ARG;
+    const int rc = sil_args(n_frames, H, W);
+    if (rc != DH_OK) return rc;
+    if (!(rmax_px >= 0.f) || rmax_px > 4096.f) return DH_ERR_BAD_ARG;                                // NaN, negative, absurd
+    if (nf >= ((int64_t)1 << 32)) return DH_ERR_UNSUPPORTED;                                          // face ids are 32-bit key halves
+    if (nf == 0 || n_frames == 0) return DH_OK;
+    if (!verts || !faces || !R || !T || !K || !near || !ws) return DH_ERR_BAD_ARG;
+    return launch_sil_nearest(verts, nv, faces, nf, R, T, K, n_frames, H, W, rmax_px, near, ws, static_cast<hipStream_t>(stream));
+}
+
+int dh_sil_loss_sums(void) { return sil_loss_sums(); }
+
+int64_t dh_sil_loss_grad_workspace(int64_t n_frames, int H, int W) {
+    const int rc = sil_args(n_frames, H, W);
+    if (rc != DH_OK) return rc;
+    return sil_loss_grad_workspace(n_frames, H, W);
+}
+
+int dh_sil_loss_grad(const uint64_t* near, const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* R,
+                     const float* T, const float* K, const float* d2_obj, const float* d2_hand, const int8_t* label, int64_t n_frames,
+                     int H, int W, float sigma, float cut, float edge_offset, double* out, void* ws, void* stream) {
+    if (nv < 0 || nf < 0) return DH_ERR_BAD_ARG;
+    const int rc = sil_args(n_frames, H, W);
+    if (rc != DH_OK) return rc;
+    if (!(sigma > 0.f) || !(cut > 0.f) || !(edge_offset >= 0.f) || sigma > 4096.f || cut > 16.f || edge_offset > 4096.f)
+        return DH_ERR_BAD_ARG;
+    if (nf >= ((int64_t)1 << 32) || n_frames > 65535) return DH_ERR_UNSUPPORTED;                     // grid (blocks, frames)
+    if (n_frames == 0) return DH_OK;
+    if (!near || !R || !T || !K || !d2_obj || !d2_hand || !label || !out || !ws || misaligned16(ws) || (nf > 0 && (!verts || !faces)))
+        return DH_ERR_BAD_ARG;
+    return launch_sil_loss_grad(near, verts, nv, faces, nf, R, T, K, d2_obj, d2_hand, label, n_frames, H, W, sigma, cut, edge_offset, out,
+                                ws, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

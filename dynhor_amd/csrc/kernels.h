@@ -193,6 +193,18 @@ int launch_mesh_shade(const float* verts, const float* normals, const uint8_t* c
                       const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
                       const uint8_t* rgb, const int8_t* label, float alpha, uint8_t* out, int64_t* counts, hipStream_t st);
 
+// silhouette pose refinement (sil.hip): windowed exact distance transform of a label value, nearest face per pixel within rmax_px
+// (ws = sil_nearest_workspace bytes), loss / pose-gradient sums per frame (sil_loss_sums() doubles, ws = sil_loss_grad_workspace bytes)
+int launch_label_edt(const int8_t* label, int64_t n_frames, int H, int W, int value, int rmax, float* tmp, float* out, hipStream_t st);
+int64_t sil_nearest_workspace(int64_t n_frames, int H, int W);
+int launch_sil_nearest(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* R, const float* T, const float* K,
+                       int64_t n_frames, int H, int W, float rmax_px, uint64_t* near, void* ws, hipStream_t st);
+int sil_loss_sums();
+int64_t sil_loss_grad_workspace(int64_t n_frames, int H, int W);
+int launch_sil_loss_grad(const uint64_t* near, const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* R,
+                         const float* T, const float* K, const float* d2_obj, const float* d2_hand, const int8_t* label, int64_t n_frames,
+                         int H, int W, float sigma, float cut, float edge_offset, double* out, void* ws, hipStream_t st);
+
 // block-sparse marching cubes (mesh_extract.hip): sample points of the listed blocks, triangles and cut faces per block, triangle emit
 int launch_mc_block_points(const float* ax, const float* ay, const float* az, int N, const int32_t* blocks, int64_t nb, int B, float* pts,
                            hipStream_t st);

@@ -8,6 +8,8 @@
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode validate_mesh --is_continue --mesh_color views+network
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode validate_mesh --is_continue --mesh_extract sparse --mesh_resolution 1024
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode visualize_mesh --is_continue --turntable 36   # overlays, IoU
+    python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode refine_poses --is_continue --pose_frames worst:5   # silhouette fit
+    python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode export_poses --is_continue    # obj_infos/<stem>.npz of the poses
 
 With --gpus N > 1 this process starts N ranks (one per GPU) through dynhor_amd.launch before it touches the GPU and exits
 with their code; under an external `torch.distributed.run` (WORLD_SIZE set) it is one of the ranks.
@@ -21,7 +23,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config_path", type=str, required=True)
     ap.add_argument("--mode", type=str, default="train",
-                    choices=["train", "validate_image", "validate_mesh", "evaluate_mesh", "visualize_mesh"])
+                    choices=["train", "validate_image", "validate_mesh", "evaluate_mesh", "visualize_mesh", "refine_poses",
+                             "export_poses"])
     ap.add_argument("--is_continue", action="store_true")
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks on this node (one process per GPU)")
@@ -51,10 +54,15 @@ def main():
                     help="validate_mesh: colour the mesh and also write <iter>_color.ply; visualize_mesh: shade with the vertex colours "
                          "(default: the config's mesh_color.mode, else none)")
     # visualize_mesh only (defaults: the config's mesh_vis: block, else the reconstruction at --mesh_resolution, no turntable)
-    ap.add_argument("--vis_mesh", type=str, default=None, help="visualize_mesh: draw this mesh (.ply / .obj) instead of the reconstruction")
+    ap.add_argument("--vis_mesh", type=str, default=None,
+                    help="visualize_mesh: draw this mesh (.ply / .obj) instead of the reconstruction; refine_poses: fit the poses to it")
     ap.add_argument("--vis_normalize", type=str, default=None, choices=["none", "reference"],
                     help="visualize_mesh: 'reference' = bring --vis_mesh into the canonical frame (mean 0, max vertex norm 0.5)")
     ap.add_argument("--turntable", type=int, default=None, help="visualize_mesh: frames of render_res/<iter>/turntable.gif (0: none)")
+    # refine_poses only (defaults: the config's pose_sil: block; the mesh is chosen by --vis_mesh / --vis_normalize / --mesh_resolution)
+    ap.add_argument("--pose_frames", type=str, default=None,
+                    help="refine_poses: the frames that move: all (default), worst:N (the N lowest silhouette IoUs) or stems a,b,c")
+    ap.add_argument("--pose_dir", type=str, default=None, help="export_poses: write the .npz files here (default <exp>/poses/<iter>/obj_infos)")
     args = ap.parse_args()
 
     from . import launch
@@ -101,6 +109,18 @@ def main():
             res = {k: v for k, v in res.items() if k != "frames"}
             res["dir"] = runner.last_vis_dir
             print(json.dumps(res), flush=True)
+    elif args.mode == "refine_poses":
+        res = runner.refine_poses_silhouette(mesh=args.vis_mesh, normalize=args.vis_normalize, resolution=args.mesh_resolution,
+                                             clean=args.mesh_clean, extract=args.mesh_extract, frames=args.pose_frames)
+        runner.close()
+        if runner.rank == 0:
+            import json
+            print(json.dumps({k: v for k, v in res.items() if k not in ("stems", "curve")}), flush=True)
+    elif args.mode == "export_poses":
+        d = runner.export_poses(args.pose_dir)
+        if runner.rank == 0:
+            import json
+            print(json.dumps({"dir": d, "frames": runner.dataset.n_images, "iter": runner.iter_step}), flush=True)
     else:
         res = 64 if args.mesh_resolution is None else args.mesh_resolution
         print("surface crossings", runner.validate_mesh(resolution=res, clean=args.mesh_clean, color=args.mesh_color,

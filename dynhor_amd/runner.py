@@ -23,6 +23,7 @@ from . import schedules
 from .dataset import Dataset
 from .fields import ParamStore, RenderingNetwork, SDFNetwork, SingleVarianceNetwork
 from .mesh_extract import DEFAULT_LIPSCHITZ
+from .pose_sil import DEFAULTS as POSE_SIL_DEFAULTS
 from .renderer import NeuSRenderer
 
 DEFAULT_CONF = {
@@ -50,6 +51,9 @@ DEFAULT_CONF = {
               "hash_renderer": {"sampler": "hierarchical", "march_samples_per_ray": 512, "grid_res": 128, "grid_update_every": 16,
                                 "max_samples": 128, "reproducible_table_grad": True},
               "neus_renderer": {"n_samples": 64, "n_importance": 64, "n_outside": 0, "up_sample_steps": 4, "perturb": 1.0}},
+    # silhouette pose refinement (--mode refine_poses): dynhor_amd/pose_sil.py says what each number is, DESIGN_NEXT_ROWS.md section 13
+    # where it comes from; resolution = the marching-cubes grid of the reconstruction the poses are fitted to
+    "pose_sil": dict(POSE_SIL_DEFAULTS),
 }
 
 
@@ -169,6 +173,7 @@ class Runner:
         self.last_color_stats = None
         self.last_extract_stats = None   # validate_mesh / evaluate_mesh / visualize_mesh with sparse extraction: its counts
         self.last_vis_dir = None         # visualize_mesh: the render_res/<iter> directory it wrote
+        self.last_pose_dir = None        # refine_poses_silhouette / export_poses: the directory the .npz files went to
         if is_continue:
             ck_dir = os.path.join(self.base_exp_dir, "checkpoints")
             ck = sorted(f for f in os.listdir(ck_dir) if f.endswith(".pth")) if os.path.isdir(ck_dir) else []
@@ -601,29 +606,13 @@ class Runner:
         return res
 
     @torch.no_grad()
-    def visualize_mesh(self, mesh=None, normalize=None, resolution=None, clean=None, color=None, alpha=None, turntable=None, save=True,
-                       extract=None):
-        """The mesh drawn over every frame at the dataset's current poses (refined ones included) and its silhouette IoU against the
-        object labels, hand pixels excluded (dynhor_amd/mesh_vis.py).  The mesh: the reconstruction, extracted as validate_mesh
-        extracts it at `resolution` (no .ply written), or the .ply / .obj file `mesh` (metrics.load_mesh), taken as in the canonical
-        frame (normalize "none") or normalised as the reference normalises its prior (normalize "reference").  clean / color: the
-        mesh_clean / mesh_color modes of validate_mesh (None: the config's blocks), applied to whichever mesh is drawn; with a colour
-        mode the shading uses the vertex colours.  extract: validate_mesh's extraction mode for the reconstruction.  Arguments left at
-        None take the YAML's optional mesh_vis: block over MESH_VIS_DEFAULTS.  Rank 0 writes render_res/<iter:08d>/<stem>.jpg for every frame (quality 95), silhouette.json (the summary
-        plus iter, mesh, clean, color, alpha), turntable.gif when turntable > 0 (orbit_cameras, 100 ms per frame, looping), and logs
-        vis/iou_mean, vis/iou_median, vis/iou_min to <exp>/board.  Returns the mesh_vis.silhouette_summary dict with those keys (the
-        other ranks return None)."""
+    def _select_mesh(self, fn, mesh, normalize, resolution, clean, extract):
+        """(verts, faces, name, clean mode) of the mesh visualize_mesh draws and refine_poses_silhouette fits: the .ply / .obj file `mesh`
+        (metrics.load_mesh; normalize "none" | "reference"), else the reconstruction extracted as validate_mesh extracts it at
+        `resolution` (no .ply written); cleaned when `clean` (None: the config's mesh_clean.mode) says so."""
         from . import metrics
-        from .mesh_vis import orbit_cameras, overlay_frames, silhouette_summary, turntable as render_turntable
-        if self.rank != 0:
-            return None
-        vc = dict(MESH_VIS_DEFAULTS)
-        vc.update(self.conf.get("mesh_vis") or {})
-        pick = lambda v, key: v if v is not None else vc[key]
-        mesh, normalize = pick(mesh, "mesh"), pick(normalize, "normalize")
-        resolution, alpha, n_turn = int(pick(resolution, "resolution")), float(pick(alpha, "alpha")), int(pick(turntable, "turntable"))
         if normalize not in ("none", "reference"):
-            raise ValueError(f"visualize_mesh: normalize must be 'none' or 'reference', got {normalize!r}")
+            raise ValueError(f"{fn}: normalize must be 'none' or 'reference', got {normalize!r}")
         if mesh is None:
             verts, faces = self.validate_mesh(resolution=resolution, save=False, clean="none", color="none", extract=extract)
             name = f"reconstruction@{resolution}"
@@ -636,6 +625,30 @@ class Runner:
         cmode = self._clean_conf(clean)["mode"]
         if cmode != "none":
             verts, faces = self._clean_mesh(verts, faces, clean)
+        return verts, faces, name, cmode
+
+    @torch.no_grad()
+    def visualize_mesh(self, mesh=None, normalize=None, resolution=None, clean=None, color=None, alpha=None, turntable=None, save=True,
+                       extract=None):
+        """The mesh drawn over every frame at the dataset's current poses (refined ones included) and its silhouette IoU against the
+        object labels, hand pixels excluded (dynhor_amd/mesh_vis.py).  The mesh: the reconstruction, extracted as validate_mesh
+        extracts it at `resolution` (no .ply written), or the .ply / .obj file `mesh` (metrics.load_mesh), taken as in the canonical
+        frame (normalize "none") or normalised as the reference normalises its prior (normalize "reference").  clean / color: the
+        mesh_clean / mesh_color modes of validate_mesh (None: the config's blocks), applied to whichever mesh is drawn; with a colour
+        mode the shading uses the vertex colours.  extract: validate_mesh's extraction mode for the reconstruction.  Arguments left at
+        None take the YAML's optional mesh_vis: block over MESH_VIS_DEFAULTS.  Rank 0 writes render_res/<iter:08d>/<stem>.jpg for every frame (quality 95), silhouette.json (the summary
+        plus iter, mesh, clean, color, alpha), turntable.gif when turntable > 0 (orbit_cameras, 100 ms per frame, looping), and logs
+        vis/iou_mean, vis/iou_median, vis/iou_min to <exp>/board.  Returns the mesh_vis.silhouette_summary dict with those keys (the
+        other ranks return None)."""
+        from .mesh_vis import orbit_cameras, overlay_frames, silhouette_summary, turntable as render_turntable
+        if self.rank != 0:
+            return None
+        vc = dict(MESH_VIS_DEFAULTS)
+        vc.update(self.conf.get("mesh_vis") or {})
+        pick = lambda v, key: v if v is not None else vc[key]
+        mesh, normalize = pick(mesh, "mesh"), pick(normalize, "normalize")
+        resolution, alpha, n_turn = int(pick(resolution, "resolution")), float(pick(alpha, "alpha")), int(pick(turntable, "turntable"))
+        verts, faces, name, cmode = self._select_mesh("visualize_mesh", mesh, normalize, resolution, clean, extract)
         cc = self._color_conf(color)
         colors = None
         if cc["mode"] != "none":
@@ -683,6 +696,94 @@ class Runner:
             for k in ("iou_mean", "iou_median", "iou_min"):
                 if res[k] is not None:
                     self._board.add_scalar("vis/" + k, float(res[k]), self.iter_step)
+            self._board.flush()
+        return res
+
+    # ------------------------------------------------------------------ poses out (the reference's hand-off format)
+    def export_poses(self, dir=None):
+        """The dataset's CURRENT poses (photometrically or silhouette-refined ones included) as <dir>/<stem>.npz with R [3,3], T [1,3],
+        K [3,3] float32: the layout ObjTracker/run.py:172-179 writes and Dataset reads through data_info.obj_infos.  A frame that was
+        loaded with an obj_scale s != 1 gets T * s and obj_scale written back, so the file round-trips through Dataset._load_from_disk.
+        dir None: <exp>/poses/<iter:08d>/obj_infos.  Rank 0 writes; returns the directory."""
+        ds = self.dataset
+        d = dir if dir is not None else os.path.join(self.base_exp_dir, "poses", "{:0>8d}".format(self.iter_step), "obj_infos")
+        if self.rank == 0:
+            os.makedirs(d, exist_ok=True)
+            stems = list(ds.stems) if ds.stems is not None else ["{:04d}".format(i) for i in range(ds.n_images)]
+            R = ds.R.detach().cpu().numpy().astype(np.float32)
+            T = ds.T.detach().cpu().numpy().astype(np.float32)
+            K = ds.K.detach().cpu().numpy().astype(np.float32)
+            scale = ds.obj_scale.cpu().numpy().astype(np.float32) if ds.obj_scale is not None else None
+            for k, stem in enumerate(stems):
+                if scale is None or scale[k] == 1.0:
+                    np.savez(os.path.join(d, stem + ".npz"), R=R[k], T=T[k].reshape(1, 3), K=K)
+                else:
+                    np.savez(os.path.join(d, stem + ".npz"), R=R[k], T=(T[k] * scale[k]).reshape(1, 3), K=K, obj_scale=scale[k])
+        self.last_pose_dir = d
+        return d
+
+    def refine_poses_silhouette(self, mesh=None, normalize=None, resolution=None, clean=None, extract=None, frames=None, save=True,
+                                **overrides):
+        """Every frame's pose refined against a mesh by silhouette matching (dynhor_amd/pose_sil.py) and written into Dataset.R /
+        Dataset.T.  The mesh is chosen as visualize_mesh chooses it (_select_mesh; `mesh` and `normalize` left at None take the config's
+        mesh_vis: block): the .ply / .obj file `mesh` (normalize "none" | "reference"), else the reconstruction extracted at
+        `resolution` (default pose_sil.resolution, 128: a silhouette at pixel precision does not need the 512^3 mesh), cleaned when
+        mesh_clean says so.  frames: None / "all", "worst:N" (the N lowest silhouette IoUs before the
+        refinement) or stems "a,b,c": the frames that move; the others stay fixed.  overrides: any key of the config's pose_sil: block.
+        Rank 0 writes poses/<iter:08d>/obj_infos/<stem>.npz (export_poses) and poses/<iter:08d>/refine.json (settings, per-frame IoU
+        before / after, loss curve, mesh name), and logs pose_sil/* to <exp>/board.  With train.refine_poses on, the PoseRefiner is
+        re-seeded from the new poses (its Adam state starts afresh) and, when save is on, checkpoints/ckpt_<iter>.pth is written again
+        with it: load_checkpoint copies a checkpoint's PoseRefiner poses over Dataset.R / T, so that is what a later --is_continue run
+        starts from.  Without train.refine_poses, point data_info.obj_infos at the written folder.  Returns the dict of refine.json
+        plus dir (single process: run it on one rank)."""
+        from .pose_sil import refine_poses
+        if self.world > 1:
+            raise ValueError("refine_poses_silhouette runs on one rank (the poses of all frames are optimised jointly)")
+        pc = dict(POSE_SIL_DEFAULTS)
+        pc.update(self.conf.get("pose_sil") or {})
+        unknown = sorted(set(overrides) - set(POSE_SIL_DEFAULTS))
+        if unknown:
+            raise ValueError(f"refine_poses_silhouette: unknown pose_sil setting(s) {unknown}; known: {sorted(POSE_SIL_DEFAULTS)}")
+        pc.update({k: v for k, v in overrides.items() if v is not None})
+        vc = dict(MESH_VIS_DEFAULTS)
+        vc.update(self.conf.get("mesh_vis") or {})
+        mesh = mesh if mesh is not None else vc["mesh"]
+        normalize = normalize if normalize is not None else vc["normalize"]
+        resolution = int(resolution if resolution is not None else pc["resolution"])
+        verts, faces, name, cmode = self._select_mesh("refine_poses_silhouette", mesh, normalize, resolution, clean, extract)
+        if faces.shape[0] == 0:
+            raise ValueError(f"refine_poses_silhouette: the mesh {name} has no faces")
+        verts, faces = verts.to(torch.float32).contiguous(), faces.to(torch.int64).contiguous()
+        res = refine_poses(verts, faces, self.dataset, iters=pc["iters"], lr=pc["lr"], rot_lr_mult=pc["rot_lr_mult"],
+                           sigma_px=pc["sigma_px"], sigma_end_px=pc["sigma_end_px"], cut=pc["cut"], edge_offset_px=pc["edge_offset_px"],
+                           lw_sil=pc["lw_sil"], lw_smooth=pc["lw_smooth"], frame_chunk=pc["frame_chunk"], report_freq=pc["report_freq"],
+                           frames=frames)
+        res.pop("R"); res.pop("T")
+        res.update(iter=self.iter_step, mesh=name, clean=cmode, faces=int(faces.shape[0]))
+        if self.pose_refiner is not None:
+            from .pose import PoseRefiner
+            tr = self.conf["train"]
+            self.pose_refiner = PoseRefiner(self.dataset.R, self.dataset.T, lr=tr["pose_lr"], rot_lr_mult=tr["pose_rot_lr_mult"]).to(self.device)
+            if save:
+                # load_checkpoint copies the checkpoint's PoseRefiner poses over Dataset.R / T: without a checkpoint of the re-seeded
+                # refiner a later --is_continue run would bring the old poses back
+                res["checkpoint"] = self.save_checkpoint()
+        if save:
+            d = os.path.join(self.base_exp_dir, "poses", "{:0>8d}".format(self.iter_step))
+            self.export_poses(os.path.join(d, "obj_infos"))
+            with open(os.path.join(d, "refine.json"), "w") as f:
+                json.dump(res, f, indent=1)
+            res["dir"] = d
+            self.last_pose_dir = d
+            if self._board is None:
+                from .tb_events import make_writer
+                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+            for st in res["curve"]:
+                for k in ("loss", "loss_sil", "loss_smooth", "iou_mean", "iou_min", "sigma"):
+                    self._board.add_scalar("pose_sil/" + k, float(st[k]), int(st["iter"]))
+            for k in ("iou_mean_before", "iou_mean_after"):
+                if res[k] is not None:
+                    self._board.add_scalar("pose_sil/" + k, float(res[k]), self.iter_step)
             self._board.flush()
         return res
 

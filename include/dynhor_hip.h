@@ -501,6 +501,52 @@ int dh_mesh_shade(const float* verts, const float* normals, const uint8_t* color
                   const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
                   const uint8_t* rgb, const int8_t* label, float alpha, uint8_t* out, int64_t* counts, void* stream);
 
+/* ---- silhouette pose refinement (dynhor_amd/pose_sil.py: per-frame poses fitted to the object masks through a soft silhouette) ----
+ * Projection, pixel centres, edge function, coverage and the rule by which a face is skipped are dh_mesh_raster_depth's (the same
+ * fp32 code), so a pixel is "covered" here exactly where that z-buffer is not empty.
+ *
+ * dh_label_edt: label i8 [n_frames,H,W] -> out f32 [n_frames,H,W]: the exact squared Euclidean distance, in pixels, to the nearest pixel
+ * whose label == value, searched over the window |dx|, |dy| <= rmax clipped to the image; +inf where the window holds none.  Every
+ * result <= rmax^2 is the image's exact distance transform; a larger one only says "farther than rmax".  Two separable passes through
+ * the caller's tmp f32 [n_frames,H,W]; every value is an integer <= 2 rmax^2 < 2^24 (rmax <= 2896), exact in fp32.  n_frames == 0: no-op.
+ * DH_ERR_BAD_ARG: null pointer, negative n_frames or rmax, H or W < 1, value outside [-128, 127].  DH_ERR_UNSUPPORTED:
+ * n_frames * H >= 2^31, W > 65535 * 256, rmax > 2896, H or W > 2^24.
+ *
+ * dh_sil_nearest: near u64 [n_frames,H,W], filled with UINT64_MAX ("empty") by the caller, is combined by a 64-bit atomic minimum with
+ * (float_bits(d2) << 32) | face for every face and every pixel centre p with d2 <= rmax_px^2: d2 = 0 when the face covers p, else the
+ * squared distance from p to the nearest of the face's three edge segments, in fp32: for a segment a b, t = clamp(<p - a, b - a> /
+ * |b - a|^2, 0, 1), r = (p - a) - t (b - a), d2 = fma(r.w, r.w, r.u r.u); never below FLT_MIN for an uncovered p, so d2 == 0 marks
+ * exactly the covered pixels.  The minimum does not depend on scheduling: the buffer is bitwise reproducible and a tie goes to the
+ * smaller face.  A pixel farther than rmax_px from every face stays empty.  ws: dh_sil_nearest_workspace(n_frames, H, W) bytes (one
+ * byte per 16 x 16 pixel tile: whether it still holds an uncovered pixel after the covering pass; faces whose grown box touches no
+ * such tile are skipped).  nf == 0 or n_frames == 0: no-op.
+ * DH_ERR_BAD_ARG: null pointer (ws included), negative count, H or W < 1, rmax_px NaN, negative or > 4096.  DH_ERR_UNSUPPORTED:
+ * nf >= 2^32, n_frames >= 2^31, H or W > 2^24.
+ *
+ * dh_sil_loss_grad: out f64 [n_frames, dh_sil_loss_sums() = 17].  Per frame over its pixels, in fp64 from the fp32 inputs:
+ * cs2 = (cut sigma)^2 formed in fp32; halo(x) = x <= cs2 ? max(0, exp(-x / sigma^2) - exp(-cut^2)) / (1 - exp(-cut^2)) : 0;
+ * w = label >= 0 and not (d2_hand <= cs2); M = halo(max(0, sqrt(d2_obj) - edge_offset)^2); S = 1 where near's d2 bits are 0, 0 where near
+ * is empty (or names no face of this mesh), else halo(d2) with d2 recomputed in fp64 from near's face (its vertices projected in fp64;
+ * the nearest of the segments v0 v1, v1 v2, v2 v0, the first on a tie).  d2_obj, d2_hand f32 [n_frames,H,W]: dh_label_edt of the values
+ * 1 and -1 with rmax >= cut sigma + edge_offset.
+ *   [0] sum w (S - M)^2   [1] sum w   [2..10] d[0] / dR_f row-major   [11..13] d[0] / dT_f   [14..16] tp, fp, fn
+ * The gradient goes through the closest point q = a + t (b - a) of the winning segment: d d2 / da = -2 (1 - t)(p - q), d d2 / db =
+ * -2 t (p - q), then u = (K0 . x_cam) / z, x_cam = R_f v + T_f.  (tp, fp, fn) over label >= 0 = (covered and label 1, covered and
+ * label 0, uncovered and label 1): dh_mesh_shade's counts.  ws: dh_sil_loss_grad_workspace(n_frames, H, W) bytes, 16-byte aligned:
+ * every workgroup stores its partial and a second kernel adds them in block order (no float atomics); the workgroups of a frame
+ * depend on H W alone, so out is bitwise reproducible from launch to launch and for every split of the frames into calls.
+ * n_frames == 0: no-op.  DH_ERR_BAD_ARG: null pointer (ws included; verts, faces may be null with nf == 0), negative count, H or
+ * W < 1, sigma or cut not > 0, edge_offset negative, NaN.  DH_ERR_UNSUPPORTED: nf >= 2^32, n_frames > 65535, H or W > 2^24. */
+int dh_label_edt(const int8_t* label, int64_t n_frames, int H, int W, int value, int rmax, float* tmp, float* out, void* stream);
+int64_t dh_sil_nearest_workspace(int64_t n_frames, int H, int W);
+int dh_sil_nearest(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* R, const float* T, const float* K,
+                   int64_t n_frames, int H, int W, float rmax_px, uint64_t* near, void* ws, void* stream);
+int dh_sil_loss_sums(void);
+int64_t dh_sil_loss_grad_workspace(int64_t n_frames, int H, int W);
+int dh_sil_loss_grad(const uint64_t* near, const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* R,
+                     const float* T, const float* K, const float* d2_obj, const float* d2_hand, const int8_t* label, int64_t n_frames,
+                     int H, int W, float sigma, float cut, float edge_offset, double* out, void* ws, void* stream);
+
 /* ---- block-sparse marching cubes (dynhor_amd/mesh_extract.py: the iso-surface from the blocks near it only) ----
  * The grid has N points per axis, cut into nbk = ceil((N - 1) / B) blocks of B cells per axis; block (bx, by, bz) of blocks int32 [nb,3]
  * covers the grid indices [b B, min(b B + B, N - 1)] and carries P^3 samples, P = B + 1, sample (i, j, k) of block n at row n P^3 +
