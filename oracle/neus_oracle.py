@@ -229,7 +229,8 @@ class NeuSRenderer:
     def render_core(self, rays_o, rays_d, z_vals, sample_dist, background_rgb=None, cos_anneal_ratio=0.0):
         batch_size, n_samples = z_vals.shape
         dists = z_vals[..., 1:] - z_vals[..., :-1]
-        dists = torch.cat([dists, torch.full_like(dists[..., :1], sample_dist)], -1)
+        # (shaped after z_vals, not dists: a ray of ONE sample has no dists)
+        dists = torch.cat([dists, torch.full_like(z_vals[..., :1], sample_dist)], -1)
         mid_z_vals = z_vals + dists * 0.5
         pts = rays_o[:, None, :] + rays_d[:, None, :] * mid_z_vals[..., :, None]
         dirs = rays_d[:, None, :].expand(pts.shape)
