@@ -107,6 +107,12 @@ SIGNATURES = {
     "dh_mc_block_points": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp]),
     "dh_mc_count": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dh_mc_emit": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "dh_simplify_grid": (_i32, [ctypes.POINTER(_f32), ctypes.POINTER(_f32), _i64, ctypes.POINTER(_f32), ctypes.POINTER(_i32)]),
+    "dh_simplify_cells": (_i32, [_vp, _i64, ctypes.POINTER(_f32), _f32, ctypes.POINTER(_i32), _vp, _vp]),
+    "dh_simplify_sums": (_i32, []),
+    "dh_simplify_quadrics": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, ctypes.POINTER(_f32), _f32, ctypes.POINTER(_i32),
+                                    ctypes.c_double, _i32, _vp, _vp, _vp, _vp]),
+    "dh_simplify_faces": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
 }
 
 

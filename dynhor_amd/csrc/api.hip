@@ -782,4 +782,60 @@ int dh_sil_loss_grad(const uint64_t* near, const float* verts, int64_t nv, const
                                 ws, static_cast<hipStream_t>(stream));
 }
 
+// shared argument rules of the simplification entry points: a grid as dh_simplify_grid returns it
+static int simplify_grid_args(const float* lo, float h, const int32_t* dims) {
+    if (!lo || !dims || !(h >= 0.f) || !(h <= 3.0e38f)) return DH_ERR_BAD_ARG;
+    for (int a = 0; a < 3; ++a) {
+        if (!(lo[a] >= -3.4e38f && lo[a] <= 3.4e38f) || dims[a] < 1) return DH_ERR_BAD_ARG;
+        if (dims[a] > (1 << 20) + 1) return DH_ERR_UNSUPPORTED;
+    }
+    return DH_OK;
+}
+
+int dh_simplify_grid(const float* lo, const float* hi, int64_t cells, float* h, int32_t* dims) {
+    if (!lo || !hi || !h || !dims || cells < 1) return DH_ERR_BAD_ARG;
+    if (cells > ((int64_t)1 << 20)) return DH_ERR_UNSUPPORTED;
+    for (int a = 0; a < 3; ++a) {
+        const float e = hi[a] - lo[a];
+        if (!(e >= 0.f && e <= 3.0e38f)) return DH_ERR_BAD_ARG;                                  // NaN, inverted or overflowing box
+    }
+    simplify_grid(lo, hi, cells, h, dims);
+    return DH_OK;
+}
+
+int dh_simplify_cells(const float* verts, int64_t nv, const float* lo, float h, const int32_t* dims, int64_t* keys, void* stream) {
+    if (nv < 0) return DH_ERR_BAD_ARG;
+    const int rc = simplify_grid_args(lo, h, dims);
+    if (rc != DH_OK) return rc;
+    if (nv >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;
+    if (nv == 0) return DH_OK;
+    if (!verts || !keys) return DH_ERR_BAD_ARG;
+    return launch_simplify_cells(verts, nv, lo, h, dims, keys, static_cast<hipStream_t>(stream));
+}
+
+int dh_simplify_sums(void) { return simplify_sums(); }
+
+int dh_simplify_quadrics(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const int64_t* order,
+                         const int64_t* run_start, const int64_t* run_key, int64_t n_runs, const float* lo, float h, const int32_t* dims,
+                         double regularization, int placement, float* rep, int32_t* clamped, double* sums, void* stream) {
+    if (nv < 0 || nf < 0 || n_runs < 0) return DH_ERR_BAD_ARG;
+    const int rc = simplify_grid_args(lo, h, dims);
+    if (rc != DH_OK) return rc;
+    if (!(regularization > 0.0) || !(regularization <= 1.0e6) || (placement != 0 && placement != 1)) return DH_ERR_BAD_ARG;
+    if (nv >= ((int64_t)1 << 31) || nf >= ((int64_t)1 << 31) || n_runs > 3 * nf) return DH_ERR_UNSUPPORTED;
+    if (n_runs == 0) return DH_OK;
+    if (!verts || !faces || !order || !run_start || !run_key || !rep || !clamped) return DH_ERR_BAD_ARG;
+    return launch_simplify_quadrics(verts, nv, faces, nf, order, run_start, run_key, n_runs, lo, h, dims, regularization, placement, rep,
+                                    clamped, sums, static_cast<hipStream_t>(stream));
+}
+
+int dh_simplify_faces(const int64_t* faces, int64_t nf, const int32_t* vrank, int64_t nv, int64_t n_runs, int64_t* tri, uint8_t* keep,
+                      int64_t* key, void* stream) {
+    if (nv < 0 || nf < 0 || n_runs < 0) return DH_ERR_BAD_ARG;
+    if (nv >= ((int64_t)1 << 31) || nf >= ((int64_t)1 << 31) || n_runs >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;
+    if (nf == 0) return DH_OK;
+    if (!faces || !vrank || !tri || !keep || !key) return DH_ERR_BAD_ARG;
+    return launch_simplify_faces(faces, nf, vrank, nv, n_runs, tri, keep, key, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -213,4 +213,16 @@ int launch_mc_count(const float* vals, const int32_t* blocks, int64_t nb, int N,
 int launch_mc_emit(const float* vals, const int32_t* blocks, int64_t nb, int N, int B, float threshold, const uint8_t* table,
                    const int64_t* offsets, int64_t n_tri, int64_t* keys, float* pos, hipStream_t st);
 
+// mesh simplification by quadric vertex clustering (mesh_simplify.hip): the grid of a bounding box (host only), cell key per vertex,
+// per-cell sums / solve / representative over the sorted record runs (simplify_sums() doubles per run), faces remapped to cell ranks
+void simplify_grid(const float* lo, const float* hi, int64_t cells, float* h, int32_t* dims);
+int launch_simplify_cells(const float* verts, int64_t nv, const float* lo, float h, const int32_t* dims, int64_t* keys, hipStream_t st);
+int simplify_sums();
+int launch_simplify_quadrics(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const int64_t* order,
+                             const int64_t* run_start, const int64_t* run_key, int64_t n_runs, const float* lo, float h,
+                             const int32_t* dims, double lambda, int quadric, float* rep, int32_t* clamped, double* sums,
+                             hipStream_t st);
+int launch_simplify_faces(const int64_t* faces, int64_t nf, const int32_t* vrank, int64_t nv, int64_t n_runs, int64_t* tri, uint8_t* keep,
+                          int64_t* key, hipStream_t st);
+
 }  // namespace dh

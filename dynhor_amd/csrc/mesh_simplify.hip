@@ -1,0 +1,259 @@
+// Mesh simplification by vertex clustering with per-cell quadrics (dynhor_amd/mesh_simplify.py): Rossignac-Borrel cells, Lindstrom's
+// quadric placement with a Tikhonov pull towards the cell's centroid.
+//
+// Grid, in fp32 IEEE operations and in this order (simplify_grid on the host, simplify_cells_kernel on the device):
+//   ext_a = hi_a - lo_a                       (lo, hi: the per-axis minimum and maximum of the vertices)
+//   h = max(ext_x, ext_y, ext_z) / (float)N   (one division; h == 0: every vertex is in cell 0 and dims = 1, 1, 1)
+//   dims_a = max(1, (int)ceil(ext_a / h))
+//   i_a = min(dims_a - 1, (int)floor((v_a - lo_a) / h))    (the quotient is compared as a float before it is converted)
+//   key = i_x + dims_x * (i_y + dims_y * i_z)  in int64
+//
+// Records: (face f, corner k) is record 3 f + k of the cell of vertex faces[f,k].  The caller sorts the records stably by key, so a
+// cell's run lists its records in ascending order.  Per record, in fp64 from the fp32 inputs, every product and sum rounded on its own
+// (this file is compiled with floating-point contraction off), P_j = verts[faces[f,j]]:
+//   e1 = P_1 - P_0, e2 = P_2 - P_0, cr = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z, e1.x e2.y - e1.y e2.x)
+//   len = sqrt((cr.x cr.x + cr.y cr.y) + cr.z cr.z), a = 0.5 len, n = cr / len (a zero-area face: a = 0, n = 0)
+//   c_a = lo_a + (i_a + 0.5) h  (the cell's centre), q = P_k - c, d = (n.x (c.x - P_0.x) + n.y (c.y - P_0.y)) + n.z (c.z - P_0.z)
+//   g = a n;  the 17 terms:  [0..5] g_r n_s for rs = xx xy xz yy yz zz  [6..8] g_r d  [9] a  [10..12] a q_r  [13..15] q_r  [16] 1
+// simplify_quadrics_kernel: one wave per run.  Lane l adds the records l, l + 64, ... of the run in ascending order, the 64 lanes
+// fold by a fixed xor butterfly (all lanes active), and lane 0 solves and stores.  No atomics: bitwise reproducible.
+// Representative, relative to c: xbar = [10..12] / [9] (or [13..15] / [16] when [9] == 0).  With w = ([0] + [3] + [5]) / 3, when
+// [9] > 0 and w > 0 and the placement is "quadric": (A + lambda w I) y = -(A xbar + b) by a 3 x 3 Cholesky factorisation, x = xbar + y
+// clamped per axis to [-h/2, h/2] (clamped[run] = 1 when an axis moved); else x = xbar.  rep = (float)(c + x).
+//
+// simplify_faces_kernel: per face the ranks (run indices) of its three cells, rotated so that the smallest comes first (orientation
+// kept); keep = the three differ; key = first * n_runs + second (with the third rank: the face's sort key).
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include "kernels.h"
+
+#pragma clang fp contract(off)
+
+namespace dh {
+
+namespace {
+constexpr int SQ_THREADS = 256;
+constexpr int SQ_SUMS = 17;
+
+inline unsigned sq_grid(int64_t n) {
+    const int64_t b = (n + SQ_THREADS - 1) / SQ_THREADS;
+    return (unsigned)(b < 1 ? 1 : (b < (1 << 20) ? b : (1 << 20)));      // grid-stride loops cover the rest
+}
+
+struct SqGrid {
+    float lo[3];
+    float h;
+    int32_t dims[3];
+};
+
+__device__ inline int32_t sq_cell(float v, float lo, float h, int32_t dim) {
+    if (!(h > 0.f)) return 0;
+    const float q = floorf(__fdiv_rn(v - lo, h));
+    return q >= (float)(dim - 1) ? dim - 1 : (q > 0.f ? (int32_t)q : 0);
+}
+}  // namespace
+
+void simplify_grid(const float* lo, const float* hi, int64_t cells, float* h, int32_t* dims) {
+    volatile float ext[3];                       // volatile: every difference and quotient is rounded to fp32, whatever the host compiler
+    for (int a = 0; a < 3; ++a) ext[a] = hi[a] - lo[a];
+    float m = ext[0];
+    if (ext[1] > m) m = ext[1];
+    if (ext[2] > m) m = ext[2];
+    volatile float hh = m / (float)cells;
+    *h = hh;
+    for (int a = 0; a < 3; ++a) {
+        dims[a] = 1;
+        if (hh > 0.f) {
+            volatile float q = ext[a] / hh;
+            const float c = ceilf(q);
+            dims[a] = c > 1.f ? (int32_t)c : 1;
+        }
+    }
+}
+
+__global__ __launch_bounds__(SQ_THREADS) void simplify_cells_kernel(const float* __restrict__ verts, int64_t nv, SqGrid g,
+                                                                    int64_t* __restrict__ keys) {
+    const int64_t stride = (int64_t)gridDim.x * SQ_THREADS;
+    for (int64_t v = (int64_t)blockIdx.x * SQ_THREADS + threadIdx.x; v < nv; v += stride) {
+        const int64_t ix = sq_cell(verts[v * 3 + 0], g.lo[0], g.h, g.dims[0]);
+        const int64_t iy = sq_cell(verts[v * 3 + 1], g.lo[1], g.h, g.dims[1]);
+        const int64_t iz = sq_cell(verts[v * 3 + 2], g.lo[2], g.h, g.dims[2]);
+        keys[v] = ix + (int64_t)g.dims[0] * (iy + (int64_t)g.dims[1] * iz);
+    }
+}
+
+// grid-stride over runs, one wave per run
+__global__ __launch_bounds__(SQ_THREADS) void simplify_quadrics_kernel(const float* __restrict__ verts, int64_t nv,
+                                                                       const int64_t* __restrict__ faces, int64_t nf,
+                                                                       const int64_t* __restrict__ order,
+                                                                       const int64_t* __restrict__ run_start,
+                                                                       const int64_t* __restrict__ run_key, int64_t n_runs, SqGrid g,
+                                                                       double lambda, int quadric, float* __restrict__ rep,
+                                                                       int32_t* __restrict__ clamped, double* __restrict__ sums) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * SQ_THREADS + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * SQ_THREADS) >> 6;
+    const double h = g.h;
+    for (int64_t run = wave; run < n_runs; run += n_waves) {          // wave-uniform: every lane of a wave takes the same runs
+        const int64_t key = run_key[run];
+        const int64_t dx = g.dims[0], dy = g.dims[1];
+        const int64_t cell[3] = {key % dx, (key / dx) % dy, key / (dx * dy)};
+        double c[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) c[a] = (double)g.lo[a] + ((double)cell[a] + 0.5) * h;
+        double acc[SQ_SUMS];
+#pragma unroll
+        for (int k = 0; k < SQ_SUMS; ++k) acc[k] = 0.0;
+        const int64_t r0 = run_start[run], r1 = run_start[run + 1];
+        for (int64_t r = r0 + lane; r < r1; r += 64) {
+            const int64_t rec = order[r];
+            const int64_t f = rec / 3;
+            const int k = (int)(rec - 3 * f);
+            if (f < 0 || f >= nf) continue;
+            const int64_t i0 = faces[f * 3 + 0], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
+            if (i0 < 0 || i0 >= nv || i1 < 0 || i1 >= nv || i2 < 0 || i2 >= nv) continue;      // the caller refuses such faces
+            double P[3][3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                P[0][a] = verts[i0 * 3 + a];
+                P[1][a] = verts[i1 * 3 + a];
+                P[2][a] = verts[i2 * 3 + a];
+            }
+            const double e1[3] = {P[1][0] - P[0][0], P[1][1] - P[0][1], P[1][2] - P[0][2]};
+            const double e2[3] = {P[2][0] - P[0][0], P[2][1] - P[0][1], P[2][2] - P[0][2]};
+            const double cr[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+            const double len = sqrt((cr[0] * cr[0] + cr[1] * cr[1]) + cr[2] * cr[2]);
+            const double a = 0.5 * len;
+            double n[3] = {0.0, 0.0, 0.0};
+            if (len > 0.0) {
+                n[0] = cr[0] / len; n[1] = cr[1] / len; n[2] = cr[2] / len;
+            }
+            const double d = (n[0] * (c[0] - P[0][0]) + n[1] * (c[1] - P[0][1])) + n[2] * (c[2] - P[0][2]);
+            const double gv[3] = {a * n[0], a * n[1], a * n[2]};
+            const double q[3] = {P[k][0] - c[0], P[k][1] - c[1], P[k][2] - c[2]};
+            acc[0] += gv[0] * n[0]; acc[1] += gv[0] * n[1]; acc[2] += gv[0] * n[2];
+            acc[3] += gv[1] * n[1]; acc[4] += gv[1] * n[2]; acc[5] += gv[2] * n[2];
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                acc[6 + t] += gv[t] * d;
+                acc[10 + t] += a * q[t];
+                acc[13 + t] += q[t];
+            }
+            acc[9] += a;
+            acc[16] += 1.0;
+        }
+        // every lane is here (the loop above has no early exit of the run): reduce first, branch after
+#pragma unroll
+        for (int k = 0; k < SQ_SUMS; ++k) {
+            double v = acc[k];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            acc[k] = v;
+        }
+        if (sums != nullptr && lane < SQ_SUMS) {
+            double v = acc[0];
+#pragma unroll
+            for (int k = 1; k < SQ_SUMS; ++k) v = lane == k ? acc[k] : v;
+            sums[run * SQ_SUMS + lane] = v;
+        }
+        if (lane == 0) {
+            double x[3] = {0.0, 0.0, 0.0};
+            if (acc[9] > 0.0) {
+                x[0] = acc[10] / acc[9]; x[1] = acc[11] / acc[9]; x[2] = acc[12] / acc[9];
+            } else if (acc[16] > 0.0) {
+                x[0] = acc[13] / acc[16]; x[1] = acc[14] / acc[16]; x[2] = acc[15] / acc[16];
+            }
+            int moved = 0;
+            const double w = ((acc[0] + acc[3]) + acc[5]) / 3.0;
+            if (quadric && acc[9] > 0.0 && w > 0.0) {
+                const double s = lambda * w;
+                const double m00 = acc[0] + s, m01 = acc[1], m02 = acc[2], m11 = acc[3] + s, m12 = acc[4], m22 = acc[5] + s;
+                const double b0 = -(((acc[0] * x[0] + acc[1] * x[1]) + acc[2] * x[2]) + acc[6]);
+                const double b1 = -(((acc[1] * x[0] + acc[3] * x[1]) + acc[4] * x[2]) + acc[7]);
+                const double b2 = -(((acc[2] * x[0] + acc[4] * x[1]) + acc[5] * x[2]) + acc[8]);
+                // M = L L^T; positive definite because s > 0 is added to a positive semi-definite A
+                const double l00 = sqrt(m00);
+                const double l10 = m01 / l00, l20 = m02 / l00;
+                const double l11 = sqrt(m11 - l10 * l10);
+                const double l21 = (m12 - l20 * l10) / l11;
+                const double l22 = sqrt(m22 - (l20 * l20 + l21 * l21));
+                const double z0 = b0 / l00;
+                const double z1 = (b1 - l10 * z0) / l11;
+                const double z2 = (b2 - (l20 * z0 + l21 * z1)) / l22;
+                const double y2 = z2 / l22;
+                const double y1 = (z1 - l21 * y2) / l11;
+                const double y0 = (z0 - (l10 * y1 + l20 * y2)) / l00;
+                const double y[3] = {y0, y1, y2};
+                const double half = 0.5 * h;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    double v = x[a] + y[a];
+                    if (!(v >= -half)) { v = -half; moved = 1; }        // a NaN (it cannot arise from finite sums) lands on the box too
+                    if (v > half) { v = half; moved = 1; }
+                    x[a] = v;
+                }
+            }
+#pragma unroll
+            for (int a = 0; a < 3; ++a) rep[run * 3 + a] = (float)(c[a] + x[a]);
+            clamped[run] = moved;
+        }
+    }
+}
+
+__global__ __launch_bounds__(SQ_THREADS) void simplify_faces_kernel(const int64_t* __restrict__ faces, int64_t nf,
+                                                                    const int32_t* __restrict__ vrank, int64_t nv, int64_t n_runs,
+                                                                    int64_t* __restrict__ tri, uint8_t* __restrict__ keep,
+                                                                    int64_t* __restrict__ key) {
+    const int64_t stride = (int64_t)gridDim.x * SQ_THREADS;
+    for (int64_t f = (int64_t)blockIdx.x * SQ_THREADS + threadIdx.x; f < nf; f += stride) {
+        const int64_t i0 = faces[f * 3 + 0], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
+        int64_t a = 0, b = 0, c = 0;
+        bool ok = i0 >= 0 && i0 < nv && i1 >= 0 && i1 < nv && i2 >= 0 && i2 < nv;
+        if (ok) {
+            a = vrank[i0]; b = vrank[i1]; c = vrank[i2];
+            ok = a >= 0 && a < n_runs && b >= 0 && b < n_runs && c >= 0 && c < n_runs && a != b && b != c && a != c;
+        }
+        if (!ok) {
+            a = b = c = 0;
+        } else if (b < a && b < c) {                 // rotate the smallest rank to the front: (a, b, c) -> (b, c, a) or (c, a, b)
+            const int64_t t = a; a = b; b = c; c = t;
+        } else if (c < a && c < b) {
+            const int64_t t = c; c = b; b = a; a = t;
+        }
+        tri[f * 3 + 0] = a; tri[f * 3 + 1] = b; tri[f * 3 + 2] = c;
+        keep[f] = ok ? 1 : 0;
+        key[f] = a * n_runs + b;
+    }
+}
+
+int launch_simplify_cells(const float* verts, int64_t nv, const float* lo, float h, const int32_t* dims, int64_t* keys, hipStream_t st) {
+    SqGrid g;
+    for (int a = 0; a < 3; ++a) { g.lo[a] = lo[a]; g.dims[a] = dims[a]; }
+    g.h = h;
+    hipLaunchKernelGGL(simplify_cells_kernel, dim3(sq_grid(nv)), dim3(SQ_THREADS), 0, st, verts, nv, g, keys);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int simplify_sums() { return SQ_SUMS; }
+
+int launch_simplify_quadrics(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const int64_t* order,
+                             const int64_t* run_start, const int64_t* run_key, int64_t n_runs, const float* lo, float h,
+                             const int32_t* dims, double lambda, int quadric, float* rep, int32_t* clamped, double* sums,
+                             hipStream_t st) {
+    SqGrid g;
+    for (int a = 0; a < 3; ++a) { g.lo[a] = lo[a]; g.dims[a] = dims[a]; }
+    g.h = h;
+    const int64_t blocks = (n_runs + SQ_THREADS / 64 - 1) / (SQ_THREADS / 64);                    // one wave per run
+    hipLaunchKernelGGL(simplify_quadrics_kernel, dim3((unsigned)(blocks < (1 << 16) ? blocks : (1 << 16))), dim3(SQ_THREADS), 0, st,
+                       verts, nv, faces, nf, order, run_start, run_key, n_runs, g, lambda, quadric, rep, clamped, sums);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int launch_simplify_faces(const int64_t* faces, int64_t nf, const int32_t* vrank, int64_t nv, int64_t n_runs, int64_t* tri, uint8_t* keep,
+                          int64_t* key, hipStream_t st) {
+    hipLaunchKernelGGL(simplify_faces_kernel, dim3(sq_grid(nf)), dim3(SQ_THREADS), 0, st, faces, nf, vrank, nv, n_runs, tri, keep, key);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+}  // namespace dh

@@ -7,6 +7,7 @@
     python -m dynhor_amd.run --config_path X.yaml --mode evaluate_mesh --is_continue --gt_mesh scan.ply --gt_align similarity --gt_align_init global
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode validate_mesh --is_continue --mesh_color views+network
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode validate_mesh --is_continue --mesh_extract sparse --mesh_resolution 1024
+    python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode validate_mesh --is_continue --mesh_resolution 512 --mesh_simplify faces:12000
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode visualize_mesh --is_continue --turntable 36   # overlays, IoU
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode refine_poses --is_continue --pose_frames worst:5   # silhouette fit
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode export_poses --is_continue    # obj_infos/<stem>.npz of the poses
@@ -53,6 +54,10 @@ def main():
     ap.add_argument("--mesh_color", type=str, default=None, choices=["none", "views", "network", "views+network"],
                     help="validate_mesh: colour the mesh and also write <iter>_color.ply; visualize_mesh: shade with the vertex colours "
                          "(default: the config's mesh_color.mode, else none)")
+    ap.add_argument("--mesh_simplify", type=str, default=None,
+                    help="validate_mesh / evaluate_mesh / visualize_mesh / refine_poses: none | cells:N | faces:T -- simplify the "
+                         "(cleaned) mesh by quadric vertex clustering on N cells along its longest axis, or to at most T faces; "
+                         "validate_mesh also writes <iter>_simple.ply (default: the config's mesh_simplify.mode, else none)")
     # visualize_mesh only (defaults: the config's mesh_vis: block, else the reconstruction at --mesh_resolution, no turntable)
     ap.add_argument("--vis_mesh", type=str, default=None,
                     help="visualize_mesh: draw this mesh (.ply / .obj) instead of the reconstruction; refine_poses: fit the poses to it")
@@ -96,14 +101,14 @@ def main():
     elif args.mode == "evaluate_mesh":
         res = runner.evaluate_mesh(gt_mesh=args.gt_mesh, gt_normalize=args.gt_normalize, resolution=args.mesh_resolution,
                                    clean=args.mesh_clean, extract=args.mesh_extract, gt_align=args.gt_align,
-                                   gt_align_init=args.gt_align_init)
+                                   gt_align_init=args.gt_align_init, simplify=args.mesh_simplify)
         if runner.rank == 0:
             import json
             print(json.dumps(res), flush=True)
     elif args.mode == "visualize_mesh":
         res = runner.visualize_mesh(mesh=args.vis_mesh, normalize=args.vis_normalize, resolution=args.mesh_resolution,
                                     clean=args.mesh_clean, color=args.mesh_color, turntable=args.turntable,
-                                    extract=args.mesh_extract)
+                                    extract=args.mesh_extract, simplify=args.mesh_simplify)
         if runner.rank == 0:
             import json
             res = {k: v for k, v in res.items() if k != "frames"}
@@ -111,7 +116,8 @@ def main():
             print(json.dumps(res), flush=True)
     elif args.mode == "refine_poses":
         res = runner.refine_poses_silhouette(mesh=args.vis_mesh, normalize=args.vis_normalize, resolution=args.mesh_resolution,
-                                             clean=args.mesh_clean, extract=args.mesh_extract, frames=args.pose_frames)
+                                             clean=args.mesh_clean, extract=args.mesh_extract, frames=args.pose_frames,
+                                             simplify=args.mesh_simplify)
         runner.close()
         if runner.rank == 0:
             import json
@@ -124,7 +130,7 @@ def main():
     else:
         res = 64 if args.mesh_resolution is None else args.mesh_resolution
         print("surface crossings", runner.validate_mesh(resolution=res, clean=args.mesh_clean, color=args.mesh_color,
-                                                        extract=args.mesh_extract)[1])
+                                                        extract=args.mesh_extract, simplify=args.mesh_simplify)[1])
         xs = runner.last_extract_stats
         if xs is not None and runner.rank == 0:
             print(f"mesh_extract sparse: {xs['active_blocks']} of {xs['blocks']} blocks of {xs['block']}^3 cells active at lipschitz "
@@ -134,6 +140,12 @@ def main():
         if st is not None:
             print(f"mesh_clean {st['mode']}: removed {st['removed_verts']} of {st['verts_in']} vertices, {st['removed_faces']} of "
                   f"{st['faces_in']} faces ({st['components']} components)", flush=True)
+        ss = runner.last_simplify_stats
+        if ss is not None and runner.rank == 0:
+            print(f"mesh_simplify {ss['mode']}: {ss['cells']} cells of edge {ss['cell_size']:.6g}, {ss['n_verts_in']} -> "
+                  f"{ss['n_verts_out']} vertices, {ss['n_faces_in']} -> {ss['n_faces_out']} faces ({ss['n_collapsed']} collapsed, "
+                  f"{ss['n_duplicate']} duplicate, {ss['n_clamped']} cells clamped, {ss['n_boundary_edges']} boundary and "
+                  f"{ss['n_nonmanifold_edges']} non-manifold edges)", flush=True)
         cs = runner.last_color_stats
         if cs is not None and runner.rank == 0:
             print(f"mesh_color {cs['mode']}: {cs['verts_in']} vertices, {cs['unseen_verts']} seen by no view, "

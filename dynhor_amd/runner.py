@@ -71,6 +71,11 @@ MESH_COLOR_DEFAULTS = {"mode": "none", "erode_px": 1, "min_cos": 0.1, "depth_eps
 # threshold (the same mesh, no resolution limit).  lipschitz: mesh_extract.DEFAULT_LIPSCHITZ says where the number comes from
 MESH_EXTRACT_DEFAULTS = {"mode": "dense", "block": 8, "lipschitz": DEFAULT_LIPSCHITZ}
 
+# the optional mesh_simplify: block of the YAML (validate_mesh / evaluate_mesh / visualize_mesh / refine_poses; dynhor_amd/mesh_simplify.py):
+# mode none | cells:N (N cells along the bounding box's longest axis) | faces:T (the finest grid of at most cells_max cells that leaves at
+# most T faces); regularization = the Tikhonov pull of the quadric placement towards the cell's centroid
+MESH_SIMPLIFY_DEFAULTS = {"mode": "none", "regularization": 1e-3, "cells_max": 1024}
+
 # the optional mesh_vis: block of the YAML (visualize_mesh; dynhor_amd/mesh_vis.py): mesh None = the reconstruction at `resolution`;
 # normalize "none" | "reference" for a mesh file; turntable = frames of the orbit GIF (0: none)
 MESH_VIS_DEFAULTS = {"mesh": None, "normalize": "none", "resolution": 512, "alpha": 0.6, "turntable": 0}
@@ -171,6 +176,7 @@ class Runner:
         self.last_clean_stats = None     # validate_mesh / evaluate_mesh with cleaning: mesh_clean.clean_mesh's counts
         self.last_mesh_colors = None     # validate_mesh with colouring: mesh_color.color_mesh's u8 [V,3] colours and its stats
         self.last_color_stats = None
+        self.last_simplify_stats = None  # validate_mesh / evaluate_mesh / _select_mesh with simplification: mesh_simplify's counts
         self.last_extract_stats = None   # validate_mesh / evaluate_mesh / visualize_mesh with sparse extraction: its counts
         self.last_vis_dir = None         # visualize_mesh: the render_res/<iter> directory it wrote
         self.last_pose_dir = None        # refine_poses_silhouette / export_poses: the directory the .npz files went to
@@ -437,7 +443,8 @@ class Runner:
         return psnr
 
     @torch.no_grad()
-    def validate_mesh(self, resolution=64, threshold=0.0, world_space=False, save=True, clean=None, color=None, extract=None):
+    def validate_mesh(self, resolution=64, threshold=0.0, world_space=False, save=True, clean=None, color=None, extract=None,
+                      simplify=None):
         """Upstream Runner.validate_mesh / NeuSRenderer.extract_geometry: -sdf on a regular grid over
         the object bounding box (HIP no-grad SDF kernel, 64^3-point chunks), iso-surface by marching cubes (model.mesh_method: 'cubes' | 'tetrahedra')
         (dynhor_amd/mesh.py; mcubes is not available), written as meshes/<iter>.ply.  Returns (vertices, triangles).
@@ -449,7 +456,10 @@ class Runner:
         self.last_color_stats); <iter>.ply and <iter>_clean.ply are unchanged.
         extract: "dense" | "sparse" (None: the config's mesh_extract.mode, default "dense"): how the grid is queried
         (NeuSRenderer.extract_geometry's mode; block and lipschitz from the config's mesh_extract: block).  Sparse gives the same mesh
-        from far fewer SDF queries and leaves its counts in self.last_extract_stats."""
+        from far fewer SDF queries and leaves its counts in self.last_extract_stats.
+        simplify: none | cells:N | faces:T (None: the config's mesh_simplify.mode, default "none"; mesh_simplify.simplify_mesh).  With a
+        mode other than "none" the (cleaned) mesh is simplified before it is coloured, written as <iter>_simple.ply and returned (its
+        counts in self.last_simplify_stats); <iter>.ply and <iter>_clean.ply are unchanged and <iter>_color.ply is the simplified mesh."""
         from .mesh import write_ply
         bmin, bmax = self.dataset.object_bbox_min, self.dataset.object_bbox_max
         ec = self._extract_conf(extract)
@@ -467,6 +477,12 @@ class Runner:
             verts, faces = self._clean_mesh(verts, faces, clean)
             if save and self.rank == 0:
                 write_ply(os.path.join(d, "{:0>8d}_clean.ply".format(self.iter_step)), verts, faces)
+        self.last_simplify_stats = None
+        if self._simplify_conf(simplify)["mode"] != "none":
+            verts, faces = self._simplify_mesh(verts, faces, simplify)
+            if save and self.rank == 0:
+                os.makedirs(d, exist_ok=True)
+                write_ply(os.path.join(d, "{:0>8d}_simple.ply".format(self.iter_step)), verts, faces)
         cc = self._color_conf(color)
         if cc["mode"] != "none":
             from .mesh_color import color_mesh
@@ -504,6 +520,31 @@ class Runner:
             raise ValueError(f"mesh_extract lipschitz must be a number > 0, got {c['lipschitz']!r}")
         return c
 
+    def _simplify_conf(self, mode=None):
+        """The YAML's optional mesh_simplify: block over MESH_SIMPLIFY_DEFAULTS; `mode` (when not None) overrides its mode."""
+        from .mesh_simplify import MAX_CELLS, parse_mode
+        c = dict(MESH_SIMPLIFY_DEFAULTS)
+        c.update(self.conf.get("mesh_simplify") or {})
+        if mode is not None:
+            c["mode"] = mode
+        c["mode"] = "none" if c["mode"] is None else c["mode"]
+        parse_mode(c["mode"])
+        if isinstance(c["regularization"], bool) or not isinstance(c["regularization"], (int, float)) or not 0 < c["regularization"] <= 1e6:
+            raise ValueError(f"mesh_simplify regularization must be a number in (0, 1e6], got {c['regularization']!r}")
+        if isinstance(c["cells_max"], bool) or not isinstance(c["cells_max"], int) or not 1 <= c["cells_max"] <= MAX_CELLS:
+            raise ValueError(f"mesh_simplify cells_max must be an integer in [1, {MAX_CELLS}], got {c['cells_max']!r}")
+        return c
+
+    def _simplify_mesh(self, verts, faces, mode=None):
+        """mesh_simplify.simplify_by_mode with the config's parameters; the counts go to self.last_simplify_stats."""
+        from .mesh_simplify import simplify_by_mode
+        c = self._simplify_conf(mode)
+        verts, faces, self.last_simplify_stats = simplify_by_mode(
+            verts.to(self.device, torch.float32).contiguous(), faces.to(self.device, torch.int64).contiguous(), c["mode"],
+            regularization=float(c["regularization"]), cells_max=int(c["cells_max"]))
+        self.last_simplify_stats["mode"] = c["mode"]
+        return verts, faces
+
     def _clean_conf(self, mode=None):
         """The YAML's optional mesh_clean: block over MESH_CLEAN_DEFAULTS; `mode` (when not None) overrides its mode."""
         from .mesh_clean import MODES
@@ -525,7 +566,7 @@ class Runner:
 
     @torch.no_grad()
     def evaluate_mesh(self, gt_mesh=None, gt_normalize=None, resolution=None, n_samples=None, taus=None, seed=0, save=True,
-                      gt_resolution=None, clean=None, extract=None, gt_align=None, gt_align_init=None, align_opts=None):
+                      gt_resolution=None, clean=None, extract=None, gt_align=None, gt_align_init=None, align_opts=None, simplify=None):
         """Geometry metrics of the current reconstruction against a ground-truth surface (dynhor_amd/metrics.py: Chamfer distance,
         F-score, normal consistency; definitions in its docstring).  The mesh is extracted as validate_mesh does (renderer
         extract_geometry over the object bounding box, model.mesh_method) at `resolution`, then scored by metrics.mesh_metrics.
@@ -547,6 +588,8 @@ class Runner:
         is on -- by trimmed ICP before the metrics are taken (metrics.mesh_metrics says what the dict gains); rank 0 then also writes
         meshes/<iter:08d>_gt_aligned.ply, the ground truth in the canonical frame: load it next to <iter>.ply to see the registration.
         The analytic ground truth of a synthetic dataset accepts the flags too (it is aligned already: a self-check).
+        simplify: validate_mesh's simplification mode (None: the config's mesh_simplify.mode).  With a mode other than "none" the
+        (cleaned) mesh is simplified before it is scored and the dict gains `simplify`: the mode and mesh_simplify.simplify_mesh's stats.
         Rank 0 writes meshes/<iter:08d>_eval.json and logs every number as eval/<key> to <exp>/board.  Returns the dict."""
         from . import metrics
         ev = self.conf.get("eval") or {}
@@ -571,10 +614,13 @@ class Runner:
         else:
             raise ValueError("evaluate_mesh: no ground truth -- pass gt_mesh (or set eval.gt_mesh in the config); only a synthetic "
                              "dataset has one built in")
-        verts, faces = self.validate_mesh(resolution=resolution, save=False, clean="none", extract=extract)
+        verts, faces = self.validate_mesh(resolution=resolution, save=False, clean="none", extract=extract, simplify="none")
         mode = self._clean_conf(clean)["mode"]
         if mode != "none":
             verts, faces = self._clean_mesh(verts, faces, clean)
+        smode = self._simplify_conf(simplify)["mode"]
+        if smode != "none":
+            verts, faces = self._simplify_mesh(verts, faces, simplify)
         res = metrics.mesh_metrics(verts, faces, gt_v, gt_f, n_samples=n_samples, taus=taus, seed=seed, gt_normalize=gt_normalize,
                                    device=self.device, gt_align=gt_align, gt_align_init=gt_align_init, align_opts=align_opts)
         res.update(iter=self.iter_step, resolution=resolution, gt=gt_name)
@@ -582,6 +628,8 @@ class Runner:
             st = self.last_clean_stats
             res.update(clean=mode, clean_removed_verts=st["removed_verts"], clean_removed_faces=st["removed_faces"],
                        clean_components=st["components"])
+        if smode != "none":
+            res.update(simplify=dict(self.last_simplify_stats))
         es = self.last_extract_stats
         if es is not None:
             res.update(extract="sparse", extract_block=es["block"], extract_lipschitz=es["lipschitz"], extract_blocks=es["blocks"],
@@ -606,15 +654,17 @@ class Runner:
         return res
 
     @torch.no_grad()
-    def _select_mesh(self, fn, mesh, normalize, resolution, clean, extract):
+    def _select_mesh(self, fn, mesh, normalize, resolution, clean, extract, simplify=None):
         """(verts, faces, name, clean mode) of the mesh visualize_mesh draws and refine_poses_silhouette fits: the .ply / .obj file `mesh`
         (metrics.load_mesh; normalize "none" | "reference"), else the reconstruction extracted as validate_mesh extracts it at
-        `resolution` (no .ply written); cleaned when `clean` (None: the config's mesh_clean.mode) says so."""
+        `resolution` (no .ply written); cleaned when `clean` (None: the config's mesh_clean.mode) says so, then simplified when
+        `simplify` (None: the config's mesh_simplify.mode) says so -- a mesh from a file too."""
         from . import metrics
         if normalize not in ("none", "reference"):
             raise ValueError(f"{fn}: normalize must be 'none' or 'reference', got {normalize!r}")
         if mesh is None:
-            verts, faces = self.validate_mesh(resolution=resolution, save=False, clean="none", color="none", extract=extract)
+            verts, faces = self.validate_mesh(resolution=resolution, save=False, clean="none", color="none", extract=extract,
+                                              simplify="none")
             name = f"reconstruction@{resolution}"
         else:
             verts, faces = metrics.load_mesh(str(mesh))
@@ -625,17 +675,20 @@ class Runner:
         cmode = self._clean_conf(clean)["mode"]
         if cmode != "none":
             verts, faces = self._clean_mesh(verts, faces, clean)
+        if self._simplify_conf(simplify)["mode"] != "none":
+            verts, faces = self._simplify_mesh(verts, faces, simplify)
         return verts, faces, name, cmode
 
     @torch.no_grad()
     def visualize_mesh(self, mesh=None, normalize=None, resolution=None, clean=None, color=None, alpha=None, turntable=None, save=True,
-                       extract=None):
+                       extract=None, simplify=None):
         """The mesh drawn over every frame at the dataset's current poses (refined ones included) and its silhouette IoU against the
         object labels, hand pixels excluded (dynhor_amd/mesh_vis.py).  The mesh: the reconstruction, extracted as validate_mesh
         extracts it at `resolution` (no .ply written), or the .ply / .obj file `mesh` (metrics.load_mesh), taken as in the canonical
         frame (normalize "none") or normalised as the reference normalises its prior (normalize "reference").  clean / color: the
         mesh_clean / mesh_color modes of validate_mesh (None: the config's blocks), applied to whichever mesh is drawn; with a colour
-        mode the shading uses the vertex colours.  extract: validate_mesh's extraction mode for the reconstruction.  Arguments left at
+        mode the shading uses the vertex colours.  extract: validate_mesh's extraction mode for the reconstruction.  simplify:
+        validate_mesh's simplification mode, applied after cleaning (silhouette.json then carries `simplify`).  Arguments left at
         None take the YAML's optional mesh_vis: block over MESH_VIS_DEFAULTS.  Rank 0 writes render_res/<iter:08d>/<stem>.jpg for every frame (quality 95), silhouette.json (the summary
         plus iter, mesh, clean, color, alpha), turntable.gif when turntable > 0 (orbit_cameras, 100 ms per frame, looping), and logs
         vis/iou_mean, vis/iou_median, vis/iou_min to <exp>/board.  Returns the mesh_vis.silhouette_summary dict with those keys (the
@@ -648,7 +701,8 @@ class Runner:
         pick = lambda v, key: v if v is not None else vc[key]
         mesh, normalize = pick(mesh, "mesh"), pick(normalize, "normalize")
         resolution, alpha, n_turn = int(pick(resolution, "resolution")), float(pick(alpha, "alpha")), int(pick(turntable, "turntable"))
-        verts, faces, name, cmode = self._select_mesh("visualize_mesh", mesh, normalize, resolution, clean, extract)
+        verts, faces, name, cmode = self._select_mesh("visualize_mesh", mesh, normalize, resolution, clean, extract, simplify)
+        smode = self._simplify_conf(simplify)["mode"]
         cc = self._color_conf(color)
         colors = None
         if cc["mode"] != "none":
@@ -676,6 +730,8 @@ class Runner:
             counts = overlay_frames(verts, faces, ds, colors=colors, alpha=alpha, sink=sink)
             res = silhouette_summary(counts.cpu(), stems)
             res.update(iter=self.iter_step, mesh=name, clean=cmode, color=cc["mode"], alpha=alpha)
+            if smode != "none":
+                res.update(simplify=smode, faces=int(faces.shape[0]))
             if save and n_turn > 0:
                 Ro, To = orbit_cameras(ds.R, ds.T, n_turn)
                 imgs = render_turntable(verts, faces, ds.K, ds.H, ds.W, Ro, To, colors=colors).cpu().numpy()
@@ -723,12 +779,13 @@ class Runner:
         return d
 
     def refine_poses_silhouette(self, mesh=None, normalize=None, resolution=None, clean=None, extract=None, frames=None, save=True,
-                                **overrides):
+                                simplify=None, **overrides):
         """Every frame's pose refined against a mesh by silhouette matching (dynhor_amd/pose_sil.py) and written into Dataset.R /
         Dataset.T.  The mesh is chosen as visualize_mesh chooses it (_select_mesh; `mesh` and `normalize` left at None take the config's
         mesh_vis: block): the .ply / .obj file `mesh` (normalize "none" | "reference"), else the reconstruction extracted at
         `resolution` (default pose_sil.resolution, 128: a silhouette at pixel precision does not need the 512^3 mesh), cleaned when
-        mesh_clean says so.  frames: None / "all", "worst:N" (the N lowest silhouette IoUs before the
+        mesh_clean says so and simplified when `simplify` / mesh_simplify says so (a fine extraction reduced to a few thousand faces
+        keeps the detail a coarse extraction rounds off; refine.json then carries `simplify`).  frames: None / "all", "worst:N" (the N lowest silhouette IoUs before the
         refinement) or stems "a,b,c": the frames that move; the others stay fixed.  overrides: any key of the config's pose_sil: block.
         Rank 0 writes poses/<iter:08d>/obj_infos/<stem>.npz (export_poses) and poses/<iter:08d>/refine.json (settings, per-frame IoU
         before / after, loss curve, mesh name), and logs pose_sil/* to <exp>/board.  With train.refine_poses on, the PoseRefiner is
@@ -750,7 +807,8 @@ class Runner:
         mesh = mesh if mesh is not None else vc["mesh"]
         normalize = normalize if normalize is not None else vc["normalize"]
         resolution = int(resolution if resolution is not None else pc["resolution"])
-        verts, faces, name, cmode = self._select_mesh("refine_poses_silhouette", mesh, normalize, resolution, clean, extract)
+        verts, faces, name, cmode = self._select_mesh("refine_poses_silhouette", mesh, normalize, resolution, clean, extract, simplify)
+        smode = self._simplify_conf(simplify)["mode"]
         if faces.shape[0] == 0:
             raise ValueError(f"refine_poses_silhouette: the mesh {name} has no faces")
         verts, faces = verts.to(torch.float32).contiguous(), faces.to(torch.int64).contiguous()
@@ -760,6 +818,8 @@ class Runner:
                            frames=frames)
         res.pop("R"); res.pop("T")
         res.update(iter=self.iter_step, mesh=name, clean=cmode, faces=int(faces.shape[0]))
+        if smode != "none":
+            res.update(simplify=smode)
         if self.pose_refiner is not None:
             from .pose import PoseRefiner
             tr = self.conf["train"]

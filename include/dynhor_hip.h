@@ -574,6 +574,42 @@ int dh_mc_count(const float* vals, const int32_t* blocks, int64_t nb, int N, int
 int dh_mc_emit(const float* vals, const int32_t* blocks, int64_t nb, int N, int B, float threshold, const uint8_t* table,
                const int64_t* offsets, int64_t n_tri, int64_t* keys, float* pos, void* stream);
 
+/* ---- mesh simplification (dynhor_amd/mesh_simplify.py: vertex clustering with per-cell quadrics) ----
+ * dh_simplify_grid (host only, no GPU): the grid of the bounding box lo, hi (float[3] each, host memory) cut into `cells` cells along
+ * its longest axis, in fp32 IEEE operations: ext_a = hi_a - lo_a, *h = max_a ext_a / (float)cells, dims[a] = max(1, (int)ceil(ext_a /
+ * h)); a box of extent 0 gives h = 0 and dims 1, 1, 1.  DH_ERR_BAD_ARG: null pointer, cells < 1, a NaN, inverted or overflowing box.
+ * DH_ERR_UNSUPPORTED: cells > 2^20.
+ * The three device entry points take that grid by value (lo float[3] and dims int32[3] in HOST memory, h); they keep no state and need
+ * no workspace.
+ * dh_simplify_cells: keys[v] (int64) = i_x + dims_x (i_y + dims_y i_z) with i_a = min(dims_a - 1, (int)floor((v_a - lo_a) / h)) in
+ * fp32 (subtraction, IEEE division, floor; compared as a float before the conversion); h == 0: every key is 0.  Correct beyond 2^31.
+ * The vertices must be finite and inside the box.  nv == 0: no-op.
+ * dh_simplify_quadrics: record 3 f + k is corner k of face f (faces int64 [nf,3]) and belongs to the cell of its vertex.  order int64
+ * [3 nf]: the records sorted stably by cell key; run r = order[run_start[r] .. run_start[r + 1]) (run_start int64 [n_runs + 1]) holds the
+ * records of the cell run_key[r] in ascending order.  Per run, one wave: every lane adds its records (l, l + 64, ...) in ascending order,
+ * the lanes fold by a fixed xor butterfly -- no atomics, bitwise reproducible -- into dh_simplify_sums() = 17 fp64 sums, all relative
+ * to the cell centre c_a = lo_a + (i_a + 0.5) h, with n the face's unit normal, a its area (a zero-area face: a = 0, n = 0),
+ * d = n . (c - P_0), q = corner - c:  [0..5] sum a n n^T (xx xy xz yy yz zz)  [6..8] sum a d n  [9] sum a  [10..12] sum a q
+ * [13..15] sum q  [16] the corner count (csrc/mesh_simplify.hip gives the order of every operation).  sums f64 [n_runs,17] receives
+ * them when it is not null.  rep f32 [n_runs,3]: xbar = [10..12] / [9] ([13..15] / [16] when [9] == 0); placement 1 (quadric), when [9]
+ * > 0 and w = trace / 3 > 0: (A + regularization w I) y = -(A xbar + b) by Cholesky, xbar + y clamped per axis to [-h/2, h/2]
+ * (clamped[r] int32 = 1 when an axis moved, else 0); placement 0 (mean) or a cell without area: xbar.  rep = (float)(c + x).  A record
+ * whose face has an index outside [0, nv) is skipped.  n_runs == 0: no-op.
+ * dh_simplify_faces: vrank int32 [nv] = the run of each vertex's cell (any value for a vertex no face uses).  Per face: tri int64
+ * [nf,3] = the three ranks rotated so that the smallest comes first (orientation kept), keep u8 [nf] = 1 when the three differ (else 0
+ * and tri = 0), key int64 [nf] = tri_0 n_runs + tri_1.  A face with an index outside [0, nv) or a rank outside [0, n_runs) gets
+ * keep 0.  nf == 0: no-op.
+ * DH_ERR_BAD_ARG: null pointer, negative count, a grid dh_simplify_grid cannot have returned, regularization not in (0, 1e6],
+ * placement not 0 / 1.  DH_ERR_UNSUPPORTED: nv, nf or n_runs >= 2^31, dims > 2^20 + 1, n_runs > 3 nf. */
+int dh_simplify_grid(const float* lo, const float* hi, int64_t cells, float* h, int32_t* dims);
+int dh_simplify_cells(const float* verts, int64_t nv, const float* lo, float h, const int32_t* dims, int64_t* keys, void* stream);
+int dh_simplify_sums(void);
+int dh_simplify_quadrics(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const int64_t* order,
+                         const int64_t* run_start, const int64_t* run_key, int64_t n_runs, const float* lo, float h, const int32_t* dims,
+                         double regularization, int placement, float* rep, int32_t* clamped, double* sums, void* stream);
+int dh_simplify_faces(const int64_t* faces, int64_t nf, const int32_t* vrank, int64_t nv, int64_t n_runs, int64_t* tri, uint8_t* keep,
+                      int64_t* key, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
