@@ -11,26 +11,23 @@
 //   [0..27] the upper triangle of sum J^T J, row by row (00 01 .. 06 11 12 .. 66)  [28..34] sum J^T b  [35] count
 //
 // Everything is accumulated in fp64.  Determinism: workgroup g of a hypothesis owns the samples g * 256 + t + k * (256 * blocks), each
-// lane adds its own in ascending order, the 64 lanes of a wave fold by a fixed xor butterfly, the four waves are added in order, and the
-// workgroup STORES its partial; icp_moments_reduce_kernel then adds the partials in block order.  No atomics: a launch is bitwise
-// reproducible.  The products are small because both clouds are centred on the origins the caller passes (their centroids).
+// lane adds its own in ascending order, and sums64.h folds the lanes, the waves and (sum64_reduce_kernel, defined here for every user)
+// the workgroups' partials in a fixed order.  No atomics: a launch is bitwise reproducible.  The products are small because both clouds
+// are centred on the origins the caller passes (their centroids).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "launch.h"
+#include "sums64.h"
 
 namespace dh {
 
 namespace {
-constexpr int ICP_THREADS = 256;
+constexpr int ICP_THREADS = SUM64_THREADS;
 constexpr int ICP_POINT_SUMS = 19;
 constexpr int ICP_PLANE_SUMS = 36;
 constexpr int64_t ICP_MAX_BLOCKS = 128;        // workgroups per hypothesis (each sample is read once; the partials stay few)
-
-int64_t icp_blocks(int64_t n) {
-    const int64_t b = (n + ICP_THREADS - 1) / ICP_THREADS;
-    return b < 1 ? 1 : (b < ICP_MAX_BLOCKS ? b : ICP_MAX_BLOCKS);
-}
 }  // namespace
 
 // grid (blocks, hypotheses); partial [H, blocks, K] doubles
@@ -42,7 +39,6 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_moments_kernel(const float* _
                                                                   const float* __restrict__ otgt, int64_t n, int64_t m,
                                                                   double* __restrict__ partial) {
     constexpr int K = PLANE ? ICP_PLANE_SUMS : ICP_POINT_SUMS;
-    __shared__ double wave_sum[ICP_THREADS / 64][K];
     const int h = blockIdx.y;
     const float limit = thr[h];
     const float* a = xf + 12 * (int64_t)h;
@@ -94,25 +90,11 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_moments_kernel(const float* _
             acc[35] += 1.0;
         }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double v = acc[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) wave_sum[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double v = wave_sum[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < ICP_THREADS / 64; ++w) v += wave_sum[w][threadIdx.x];
-        partial[((int64_t)h * gridDim.x + blockIdx.x) * K + threadIdx.x] = v;
-    }
+    sum64_block_store(acc, partial + ((int64_t)h * gridDim.x + blockIdx.x) * K);
 }
 
-// grid (hypotheses), K threads: out[h, k] = the partials of hypothesis h added in block order
-__global__ void icp_moments_reduce_kernel(const double* __restrict__ partial, int blocks, int K, double* __restrict__ out) {
+// grid (groups), 64 threads (K <= 64): out[g, k] = the `blocks` partials [K] of group g added in block order
+__global__ void sum64_reduce_kernel(const double* __restrict__ partial, int blocks, int K, double* __restrict__ out) {
     const int k = threadIdx.x;
     if (k >= K) return;
     const double* p = partial + (int64_t)blockIdx.x * blocks * K + k;
@@ -121,16 +103,21 @@ __global__ void icp_moments_reduce_kernel(const double* __restrict__ partial, in
     out[(int64_t)blockIdx.x * K + k] = v;
 }
 
+int launch_sum64_reduce(const double* partial, int64_t groups, int blocks, int K, double* out, hipStream_t st) {
+    hipLaunchKernelGGL(sum64_reduce_kernel, dim3((unsigned)groups), dim3(64), 0, st, partial, blocks, K, out);
+    return launch_status();
+}
+
 int icp_moments_sums(int plane) { return plane ? ICP_PLANE_SUMS : ICP_POINT_SUMS; }
 
 int64_t icp_moments_workspace(int64_t n, int64_t h, int plane) {
-    return h * icp_blocks(n) * icp_moments_sums(plane) * (int64_t)sizeof(double);
+    return h * sum64_blocks(n, ICP_MAX_BLOCKS) * icp_moments_sums(plane) * (int64_t)sizeof(double);
 }
 
 int launch_icp_moments(const float* src, const float* tgt, const float* nrm, const float* xf, const int32_t* idx, const float* d2,
                        const float* thr, const float* osrc, const float* otgt, int64_t n, int64_t m, int64_t h, double* out, void* ws,
                        hipStream_t st) {
-    const int64_t blocks = icp_blocks(n);
+    const int64_t blocks = sum64_blocks(n, ICP_MAX_BLOCKS);
     double* partial = static_cast<double*>(ws);
     const dim3 grid((unsigned)blocks, (unsigned)h);
     if (nrm)
@@ -139,10 +126,8 @@ int launch_icp_moments(const float* src, const float* tgt, const float* nrm, con
     else
         hipLaunchKernelGGL((icp_moments_kernel<false>), grid, dim3(ICP_THREADS), 0, st, src, tgt, nrm, xf, idx, d2, thr, osrc, otgt, n, m,
                            partial);
-    if (hipGetLastError() != hipSuccess) return -3;
-    const int K = icp_moments_sums(nrm != nullptr);
-    hipLaunchKernelGGL(icp_moments_reduce_kernel, dim3((unsigned)h), dim3(64), 0, st, partial, (int)blocks, K, out);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    if (launch_status() != DH_OK) return DH_ERR_LAUNCH;
+    return launch_sum64_reduce(partial, h, (int)blocks, icp_moments_sums(nrm != nullptr), out, st);
 }
 
 }  // namespace dh

@@ -176,6 +176,10 @@ int launch_icp_moments(const float* src, const float* tgt, const float* nrm, con
                        const float* thr, const float* osrc, const float* otgt, int64_t n, int64_t m, int64_t h, double* out, void* ws,
                        hipStream_t st);
 
+// the last step of a reproducible fp64 sum (sums64.h; the kernel lives in icp.hip): out[g, k] = the `blocks` partials [K] (K <= 64) of
+// each of `groups` groups added in block order
+int launch_sum64_reduce(const double* partial, int64_t groups, int blocks, int K, double* out, hipStream_t st);
+
 // mesh cleaning (mesh_clean.hip): label dilation, silhouette votes per vertex, connected components by union-find
 int launch_label_dilate(const int8_t* label, int64_t n_frames, int H, int W, int radius, uint8_t* tmp, uint8_t* keep, hipStream_t st);
 int launch_mesh_mask_votes(const float* verts, int64_t nv, const uint8_t* keep, const float* R, const float* T, const float* K,

@@ -4,9 +4,7 @@
 // hides what lies behind it, so it never votes "background").  Two separable passes (rows into the caller's tmp, then columns).
 //
 // mesh_votes_kernel: one thread per vertex, looping over the frames; the frame's R, T (and the sequence's K) are read at a
-// wave-uniform address.  Projection in fp32, in this order for every vertex and frame:
-//   c_r = fma(R_r2, z, fma(R_r1, y, R_r0 * x)) + T_r            (r = 0, 1, 2: x_cam = R v + T)
-//   u = fma(K02, c_2, fma(K01, c_1, K00 * c_0)) / c_2,   w = fma(K12, c_2, fma(K11, c_1, K10 * c_0)) / c_2
+// wave-uniform address.  Projection: mk_project (mesh_raster.h), for every vertex and frame.
 //   seen: c_2 > 0 and (floor(u + 0.5), floor(w + 0.5)) inside the image, range-checked as floats before any integer conversion
 // The label byte is loaded unconditionally (pixel 0 of the frame when the vertex is not seen) so that the loads of consecutive frames
 // do not wait behind a branch.  Counts are integers: bitwise reproducible.
@@ -22,16 +20,13 @@
 #include <math.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "launch.h"
+#include "mesh_raster.h"
 
 namespace dh {
 
 namespace {
 constexpr int MC_THREADS = 256;
-
-inline unsigned grid_for(int64_t n) {
-    const int64_t b = (n + MC_THREADS - 1) / MC_THREADS;
-    return (unsigned)(b < (1 << 20) ? b : (1 << 20));      // grid-stride loops cover the rest
-}
 
 __device__ inline int32_t uf_load(int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -102,14 +97,10 @@ __global__ __launch_bounds__(MC_THREADS) void mesh_votes_kernel(const float* __r
     for (int64_t f = 0; f < n_frames; ++f) {
         const float* Rf = R + f * 9;
         const float* Tf = T + f * 3;
-        const float c0 = __builtin_fmaf(Rf[2], vz, __builtin_fmaf(Rf[1], vy, Rf[0] * vx)) + Tf[0];
-        const float c1 = __builtin_fmaf(Rf[5], vz, __builtin_fmaf(Rf[4], vy, Rf[3] * vx)) + Tf[1];
-        const float c2 = __builtin_fmaf(Rf[8], vz, __builtin_fmaf(Rf[7], vy, Rf[6] * vx)) + Tf[2];
-        const float u = __builtin_fmaf(k02, c2, __builtin_fmaf(k01, c1, k00 * c0)) / c2;
-        const float w = __builtin_fmaf(k12, c2, __builtin_fmaf(k11, c1, k10 * c0)) / c2;
-        const float px = floorf(u + 0.5f), py = floorf(w + 0.5f);
+        const Cam c = mk_project(Rf, Tf, k00, k01, k02, k10, k11, k12, vx, vy, vz);
+        const float px = floorf(c.u + 0.5f), py = floorf(c.w + 0.5f);
         // every comparison is false for a NaN: a vertex with z ~ 0 (u, w huge, infinite or NaN) is not seen
-        const bool in = (c2 > 0.f) & (px >= 0.f) & (px < fw) & (py >= 0.f) & (py < fh);     // bitwise: no branch
+        const bool in = (c.c2 > 0.f) & (px >= 0.f) & (px < fw) & (py >= 0.f) & (py < fh);     // bitwise: no branch
         const int64_t pix = in ? (int64_t)(int)py * W + (int)px : 0;
         const uint8_t k = keep[f * HW + pix];
         ns += in;
@@ -125,8 +116,8 @@ __global__ __launch_bounds__(MC_THREADS) void uf_init_kernel(int32_t* __restrict
 
 __global__ __launch_bounds__(MC_THREADS) void uf_union_kernel(const int64_t* __restrict__ faces, int64_t nf, int64_t nv, int32_t* par) {
     for (int64_t i = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x; i < nf; i += (int64_t)gridDim.x * MC_THREADS) {
-        const int64_t a = faces[i * 3 + 0], b = faces[i * 3 + 1], c = faces[i * 3 + 2];
-        if (a < 0 || a >= nv || b < 0 || b >= nv || c < 0 || c >= nv) continue;     // a bad index never reaches the parent array
+        int64_t a, b, c;
+        if (!mk_face_in_range(faces, i, nv, a, b, c)) continue;     // a bad index never reaches the parent array
         uf_unite(par, (int32_t)a, (int32_t)b);
         uf_unite(par, (int32_t)a, (int32_t)c);
     }
@@ -142,29 +133,29 @@ __global__ __launch_bounds__(MC_THREADS) void uf_jump_kernel(int32_t* par, int64
 int launch_label_dilate(const int8_t* label, int64_t n_frames, int H, int W, int radius, uint8_t* tmp, uint8_t* keep, hipStream_t st) {
     const dim3 grid((unsigned)(n_frames * H), (unsigned)((W + MC_THREADS - 1) / MC_THREADS));   // api.hip: n_frames * H < 2^31
     hipLaunchKernelGGL(label_dilate_rows_kernel, grid, dim3(MC_THREADS), 0, st, label, W, radius, tmp);
-    if (hipGetLastError() != hipSuccess) return -3;
+    if (launch_status() != DH_OK) return DH_ERR_LAUNCH;
     hipLaunchKernelGGL(label_dilate_cols_kernel, grid, dim3(MC_THREADS), 0, st, tmp, H, W, radius, keep);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_mesh_mask_votes(const float* verts, int64_t nv, const uint8_t* keep, const float* R, const float* T, const float* K,
                            int64_t n_frames, int H, int W, int32_t* bg_votes, int32_t* seen, hipStream_t st) {
     hipLaunchKernelGGL(mesh_votes_kernel, dim3((unsigned)((nv + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, st, verts, nv, keep,
                        R, T, K, n_frames, H, W, bg_votes, seen);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_mesh_components(const int64_t* faces, int64_t nf, int64_t nv, int32_t* labels, hipStream_t st) {
-    hipLaunchKernelGGL(uf_init_kernel, dim3(grid_for(nv)), dim3(MC_THREADS), 0, st, labels, nv);
-    if (hipGetLastError() != hipSuccess) return -3;
+    hipLaunchKernelGGL(uf_init_kernel, dim3(grid_1d(nv, MC_THREADS)), dim3(MC_THREADS), 0, st, labels, nv);
+    if (launch_status() != DH_OK) return DH_ERR_LAUNCH;
     if (nf > 0) {
-        hipLaunchKernelGGL(uf_union_kernel, dim3(grid_for(nf)), dim3(MC_THREADS), 0, st, faces, nf, nv, labels);
-        if (hipGetLastError() != hipSuccess) return -3;
+        hipLaunchKernelGGL(uf_union_kernel, dim3(grid_1d(nf, MC_THREADS)), dim3(MC_THREADS), 0, st, faces, nf, nv, labels);
+        if (launch_status() != DH_OK) return DH_ERR_LAUNCH;
     }
     // after k jumps every pointer is min(2^k, distance to the root) steps up; a tree holds at most nv - 1 edges
     for (int64_t reach = 1; reach < nv - 1; reach *= 2) {
-        hipLaunchKernelGGL(uf_jump_kernel, dim3(grid_for(nv)), dim3(MC_THREADS), 0, st, labels, nv);
-        if (hipGetLastError() != hipSuccess) return -3;
+        hipLaunchKernelGGL(uf_jump_kernel, dim3(grid_1d(nv, MC_THREADS)), dim3(MC_THREADS), 0, st, labels, nv);
+        if (launch_status() != DH_OK) return DH_ERR_LAUNCH;
     }
     return 0;
 }

@@ -1,23 +1,12 @@
 // Mesh colouring (dynhor_amd/mesh_color.py): a z-buffer of the mesh in every frame, then per-vertex colours gathered from the
 // frames that see the vertex.
 //
-// Projection, in fp32 and in this order (the order of dh_mesh_mask_votes, csrc/mesh_clean.hip):
-//   c_r = fma(R_r2, z, fma(R_r1, y, R_r0 * x)) + T_r            (r = 0, 1, 2: x_cam = R v + T)
-//   u = fma(K02, c_2, fma(K01, c_1, K00 * c_0)) / c_2,   w = fma(K12, c_2, fma(K11, c_1, K10 * c_0)) / c_2
-// Pixel centres sit at integer (u, w).  mk_project and mk_edge (below) live in mesh_raster.h, shared with csrc/mesh_vis.hip.
-//
-// mesh_raster_kernel: one lane per (frame, face), frame-major.  A face is skipped when a vertex has c_2 <= 1e-3 or a non-finite
-// (u, w), when its screen area is 0, or when its box of pixel centres, clipped to the image, is empty.  Edge functions in fp32:
-//   edge(a, b, p) = fma(b.u - a.u, p.w - a.w, -((b.w - a.w) * (p.u - a.u)))
-//   e0 = edge(v1, v2, p), e1 = edge(v2, v0, p), e2 = edge(v0, v1, p), area = edge(v0, v1, v2)
-// The pixel centre p is covered when e0, e1, e2 are all >= 0 or all <= 0 (double-sided, edges included).  Perspective-correct depth:
+// mesh_raster_kernel: the face walker of mesh_raster.h (which states the projection, the skip rule, the coverage rule and the wave
+// phase) with mk_pixel as its per-pixel operation.  Perspective-correct depth of a covered pixel centre:
 //   z = (e0 + e1 + e2) / fma(e2, 1/z2, fma(e1, 1/z1, e0 * (1/z0)))
 // (normalised by the sum of the three edge values, so z is a weighted harmonic mean of z0, z1, z2 whatever the rounding).  The key
 // (float_bits(z) << 32) | face goes in by a 64-bit agent-scope atomic minimum: z > 0, so the bits order as the depths do; the
 // minimum does not depend on the order of arrival, so the buffer is bitwise reproducible, and on a depth tie the smaller face wins.
-// A lane rasterises its face alone when the clipped box is at most MK_SMALL_BOX pixels wide and tall.  A larger face is deferred to
-// the wave phase that follows in the same loop iteration: the wave takes its deferred faces one after the other (ballot order) and
-// spreads each face's box over its 64 lanes, so a coarse mesh with large faces never serialises one lane.
 //
 // mesh_bake_kernel: one thread per vertex, looping over the frames in ascending order and adding onto the caller's acc / n_views
 // (read once, written once: a fixed sequential fp32 sum per vertex, no float atomics).  A frame contributes when c_2 > 1e-3, the
@@ -30,36 +19,23 @@
 #include <math.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "launch.h"
 #include "mesh_raster.h"
 
 namespace dh {
 
 namespace {
-constexpr int MK_THREADS = 256;
-constexpr int MK_SMALL_BOX = 32;
-
-inline unsigned mk_grid(int64_t n) {
-    const int64_t b = (n + MK_THREADS - 1) / MK_THREADS;
-    return (unsigned)(b < (1 << 20) ? b : (1 << 20));      // grid-stride loops cover the rest
-}
-
-// The screen-space face one lane (or, in the wave phase, the whole wave) rasterises.
-struct Tri {
-    float u0, w0, u1, w1, u2, w2, iz0, iz1, iz2;
+struct MkDepth {
+    static constexpr int N = 9;
+    static constexpr bool FACE_TEST = false;
+    __device__ __forceinline__ void pixel(const Tri<9>& t, int x, int y, uint32_t face, uint64_t* zrow) const {
+        float e0, e1, e2;
+        if (!mk_covers(t, (float)x, (float)y, e0, e1, e2)) return;
+        const float z = (e0 + e1 + e2) / __builtin_fmaf(e2, t.iz[2], __builtin_fmaf(e1, t.iz[1], e0 * t.iz[0]));
+        const uint64_t key = ((uint64_t)__float_as_uint(z) << 32) | face;
+        __hip_atomic_fetch_min(zrow + x, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 };
-
-__device__ inline void mk_pixel(const Tri& t, int x, int y, uint32_t face, uint64_t* zrow) {
-    const float px = (float)x, py = (float)y;
-    const float e0 = mk_edge(t.u1, t.w1, t.u2, t.w2, px, py);
-    const float e1 = mk_edge(t.u2, t.w2, t.u0, t.w0, px, py);
-    const float e2 = mk_edge(t.u0, t.w0, t.u1, t.w1, px, py);
-    const bool pos = (e0 >= 0.f) & (e1 >= 0.f) & (e2 >= 0.f), neg = (e0 <= 0.f) & (e1 <= 0.f) & (e2 <= 0.f);
-    const float esum = e0 + e1 + e2;
-    if (!(pos | neg) || esum == 0.f) return;
-    const float z = esum / __builtin_fmaf(e2, t.iz2, __builtin_fmaf(e1, t.iz1, e0 * t.iz0));
-    const uint64_t key = ((uint64_t)__float_as_uint(z) << 32) | face;
-    __hip_atomic_fetch_min(zrow + x, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 }  // namespace
 
 __global__ __launch_bounds__(MK_THREADS) void mesh_raster_kernel(const float* __restrict__ verts, int64_t nv,
@@ -67,69 +43,7 @@ __global__ __launch_bounds__(MK_THREADS) void mesh_raster_kernel(const float* __
                                                                  const float* __restrict__ R, const float* __restrict__ T,
                                                                  const float* __restrict__ K, int64_t n_frames, int H, int W,
                                                                  uint64_t* zbuf) {
-    const float k00 = K[0], k01 = K[1], k02 = K[2], k10 = K[3], k11 = K[4], k12 = K[5];
-    const int64_t total = n_frames * nf, HW = (int64_t)H * W;
-    const int lane = threadIdx.x & 63;
-    // the loop bound is block-uniform, so every lane of a wave reaches the ballot of every iteration
-    for (int64_t base = (int64_t)blockIdx.x * MK_THREADS; base < total; base += (int64_t)gridDim.x * MK_THREADS) {
-        const int64_t i = base + threadIdx.x;
-        bool big = false;
-        Tri t = {};
-        int64_t f = 0;
-        uint32_t face = 0;
-        int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
-        if (i < total) {
-            f = i / nf;
-            const int64_t fi = i - f * nf;
-            face = (uint32_t)fi;
-            const int64_t a = faces[fi * 3 + 0], b = faces[fi * 3 + 1], c = faces[fi * 3 + 2];
-            if (a >= 0 && a < nv && b >= 0 && b < nv && c >= 0 && c < nv) {
-                const float* Rf = R + f * 9;
-                const float* Tf = T + f * 3;
-                const Cam p0 = mk_project(Rf, Tf, k00, k01, k02, k10, k11, k12, verts[a * 3], verts[a * 3 + 1], verts[a * 3 + 2]);
-                const Cam p1 = mk_project(Rf, Tf, k00, k01, k02, k10, k11, k12, verts[b * 3], verts[b * 3 + 1], verts[b * 3 + 2]);
-                const Cam p2 = mk_project(Rf, Tf, k00, k01, k02, k10, k11, k12, verts[c * 3], verts[c * 3 + 1], verts[c * 3 + 2]);
-                t = Tri{p0.u, p0.w, p1.u, p1.w, p2.u, p2.w, 1.f / p0.c2, 1.f / p1.c2, 1.f / p2.c2};
-                const float lim = 3.0e38f;    // |u|, |w| < lim: finite, and every comparison below is false for a NaN
-                const bool ok = (p0.c2 > 1e-3f) & (p1.c2 > 1e-3f) & (p2.c2 > 1e-3f) & (fabsf(p0.u) < lim) & (fabsf(p0.w) < lim) &
-                                (fabsf(p1.u) < lim) & (fabsf(p1.w) < lim) & (fabsf(p2.u) < lim) & (fabsf(p2.w) < lim) &
-                                (mk_edge(p0.u, p0.w, p1.u, p1.w, p2.u, p2.w) != 0.f);
-                const float fx0 = fmaxf(ceilf(fminf(fminf(p0.u, p1.u), p2.u)), 0.f);
-                const float fx1 = fminf(floorf(fmaxf(fmaxf(p0.u, p1.u), p2.u)), (float)(W - 1));
-                const float fy0 = fmaxf(ceilf(fminf(fminf(p0.w, p1.w), p2.w)), 0.f);
-                const float fy1 = fminf(floorf(fmaxf(fmaxf(p0.w, p1.w), p2.w)), (float)(H - 1));
-                if (ok && fx0 <= fx1 && fy0 <= fy1) {
-                    x0 = (int)fx0; x1 = (int)fx1; y0 = (int)fy0; y1 = (int)fy1;
-                    big = (x1 - x0 >= MK_SMALL_BOX) | (y1 - y0 >= MK_SMALL_BOX);
-                    if (!big) {
-                        uint64_t* zf = zbuf + f * HW;
-                        for (int y = y0; y <= y1; ++y)
-                            for (int x = x0; x <= x1; ++x) mk_pixel(t, x, y, face, zf + (int64_t)y * W);
-                    }
-                }
-            }
-        }
-        // wave phase: the deferred faces of this wave, one at a time, their boxes spread over the 64 lanes
-        uint64_t todo = __ballot(big);
-        while (todo) {
-            const int src = __ffsll((unsigned long long)todo) - 1;
-            todo &= todo - 1;
-            Tri s;
-            s.u0 = __shfl(t.u0, src); s.w0 = __shfl(t.w0, src); s.u1 = __shfl(t.u1, src); s.w1 = __shfl(t.w1, src);
-            s.u2 = __shfl(t.u2, src); s.w2 = __shfl(t.w2, src);
-            s.iz0 = __shfl(t.iz0, src); s.iz1 = __shfl(t.iz1, src); s.iz2 = __shfl(t.iz2, src);
-            const uint32_t sface = (uint32_t)__shfl((int)face, src);
-            const int64_t sf = (int64_t)__shfl((int)f, src);          // f < n_frames < 2^31 (api.hip)
-            const int sx0 = __shfl(x0, src), sx1 = __shfl(x1, src), sy0 = __shfl(y0, src), sy1 = __shfl(y1, src);
-            const int bw = sx1 - sx0 + 1;
-            const int64_t npix = (int64_t)bw * (sy1 - sy0 + 1);
-            uint64_t* zf = zbuf + sf * HW;
-            for (int64_t p = lane; p < npix; p += 64) {
-                const int y = sy0 + (int)(p / bw), x = sx0 + (int)(p % bw);
-                mk_pixel(s, x, y, sface, zf + (int64_t)y * W);
-            }
-        }
-    }
+    mk_walk_faces(verts, nv, faces, nf, R, T, K, n_frames, H, W, 0.f, zbuf, MkDepth{});
 }
 
 __global__ __launch_bounds__(MK_THREADS) void mesh_bake_kernel(const float* __restrict__ verts, const float* __restrict__ normals,
@@ -181,9 +95,9 @@ __global__ __launch_bounds__(MK_THREADS) void mesh_bake_kernel(const float* __re
 
 int launch_mesh_raster_depth(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* R, const float* T,
                              const float* K, int64_t n_frames, int H, int W, uint64_t* zbuf, hipStream_t st) {
-    hipLaunchKernelGGL(mesh_raster_kernel, dim3(mk_grid(n_frames * nf)), dim3(MK_THREADS), 0, st, verts, nv, faces, nf, R, T, K,
+    hipLaunchKernelGGL(mesh_raster_kernel, dim3(grid_1d(n_frames * nf, MK_THREADS)), dim3(MK_THREADS), 0, st, verts, nv, faces, nf, R, T, K,
                        n_frames, H, W, zbuf);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_mesh_bake_colors(const float* verts, const float* normals, int64_t nv, const uint8_t* rgb, const uint8_t* usable,
@@ -191,7 +105,7 @@ int launch_mesh_bake_colors(const float* verts, const float* normals, int64_t nv
                             float depth_eps, float min_cos, float* acc, int32_t* n_views, hipStream_t st) {
     hipLaunchKernelGGL(mesh_bake_kernel, dim3((unsigned)((nv + MK_THREADS - 1) / MK_THREADS)), dim3(MK_THREADS), 0, st, verts, normals,
                        nv, rgb, usable, zbuf, R, T, K, n_frames, H, W, depth_eps, min_cos, acc, n_views);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace dh

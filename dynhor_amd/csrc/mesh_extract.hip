@@ -13,6 +13,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "launch.h"
 
 namespace dh {
 
@@ -219,7 +220,7 @@ int launch_mc_block_points(const float* ax, const float* ay, const float* az, in
     const int64_t n_pts = nb * P * P * P, wg = (n_pts + MX_THREADS - 1) / MX_THREADS;
     hipLaunchKernelGGL(mc_block_points_kernel, dim3((unsigned)(wg < (1 << 20) ? wg : (1 << 20))), dim3(MX_THREADS), 0, st, ax, ay, az, N,
                        blocks, n_pts, B, pts);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_mc_count(const float* vals, const int32_t* blocks, int64_t nb, int N, int B, float threshold, const uint8_t* table,
@@ -227,7 +228,7 @@ int launch_mc_count(const float* vals, const int32_t* blocks, int64_t nb, int N,
     const int P = B + 1;
     hipLaunchKernelGGL(mc_count_kernel, dim3((unsigned)nb), dim3(MX_THREADS), (size_t)P * P * P * sizeof(float), st, vals, blocks, N, B,
                        threshold, table, block_map, counts, cut_faces, nonfinite);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_mc_emit(const float* vals, const int32_t* blocks, int64_t nb, int N, int B, float threshold, const uint8_t* table,
@@ -235,7 +236,7 @@ int launch_mc_emit(const float* vals, const int32_t* blocks, int64_t nb, int N, 
     const int P = B + 1;
     hipLaunchKernelGGL(mc_emit_kernel, dim3((unsigned)nb), dim3(MX_THREADS), (size_t)P * P * P * sizeof(float), st, vals, blocks, N, B,
                        threshold, table, offsets, n_tri, keys, pos);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace dh

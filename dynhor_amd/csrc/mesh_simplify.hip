@@ -16,7 +16,7 @@
 //   c_a = lo_a + (i_a + 0.5) h  (the cell's centre), q = P_k - c, d = (n.x (c.x - P_0.x) + n.y (c.y - P_0.y)) + n.z (c.z - P_0.z)
 //   g = a n;  the 17 terms:  [0..5] g_r n_s for rs = xx xy xz yy yz zz  [6..8] g_r d  [9] a  [10..12] a q_r  [13..15] q_r  [16] 1
 // simplify_quadrics_kernel: one wave per run.  Lane l adds the records l, l + 64, ... of the run in ascending order, the 64 lanes
-// fold by a fixed xor butterfly (all lanes active), and lane 0 solves and stores.  No atomics: bitwise reproducible.
+// fold by the fixed xor butterfly of sums64.h (all lanes active), and lane 0 solves and stores.  No atomics: bitwise reproducible.
 // Representative, relative to c: xbar = [10..12] / [9] (or [13..15] / [16] when [9] == 0).  With w = ([0] + [3] + [5]) / 3, when
 // [9] > 0 and w > 0 and the placement is "quadric": (A + lambda w I) y = -(A xbar + b) by a 3 x 3 Cholesky factorisation, x = xbar + y
 // clamped per axis to [-h/2, h/2] (clamped[run] = 1 when an axis moved); else x = xbar.  rep = (float)(c + x).
@@ -27,6 +27,9 @@
 #include <math.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "launch.h"
+#include "mesh_raster.h"
+#include "sums64.h"
 
 #pragma clang fp contract(off)
 
@@ -35,11 +38,6 @@ namespace dh {
 namespace {
 constexpr int SQ_THREADS = 256;
 constexpr int SQ_SUMS = 17;
-
-inline unsigned sq_grid(int64_t n) {
-    const int64_t b = (n + SQ_THREADS - 1) / SQ_THREADS;
-    return (unsigned)(b < 1 ? 1 : (b < (1 << 20) ? b : (1 << 20)));      // grid-stride loops cover the rest
-}
 
 struct SqGrid {
     float lo[3];
@@ -111,8 +109,8 @@ __global__ __launch_bounds__(SQ_THREADS) void simplify_quadrics_kernel(const flo
             const int64_t f = rec / 3;
             const int k = (int)(rec - 3 * f);
             if (f < 0 || f >= nf) continue;
-            const int64_t i0 = faces[f * 3 + 0], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
-            if (i0 < 0 || i0 >= nv || i1 < 0 || i1 >= nv || i2 < 0 || i2 >= nv) continue;      // the caller refuses such faces
+            int64_t i0, i1, i2;
+            if (!mk_face_in_range(faces, f, nv, i0, i1, i2)) continue;      // the caller refuses such faces
             double P[3][3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -144,13 +142,7 @@ __global__ __launch_bounds__(SQ_THREADS) void simplify_quadrics_kernel(const flo
             acc[16] += 1.0;
         }
         // every lane is here (the loop above has no early exit of the run): reduce first, branch after
-#pragma unroll
-        for (int k = 0; k < SQ_SUMS; ++k) {
-            double v = acc[k];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            acc[k] = v;
-        }
+        sum64_wave(acc);
         if (sums != nullptr && lane < SQ_SUMS) {
             double v = acc[0];
 #pragma unroll
@@ -207,9 +199,8 @@ __global__ __launch_bounds__(SQ_THREADS) void simplify_faces_kernel(const int64_
                                                                     int64_t* __restrict__ key) {
     const int64_t stride = (int64_t)gridDim.x * SQ_THREADS;
     for (int64_t f = (int64_t)blockIdx.x * SQ_THREADS + threadIdx.x; f < nf; f += stride) {
-        const int64_t i0 = faces[f * 3 + 0], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
-        int64_t a = 0, b = 0, c = 0;
-        bool ok = i0 >= 0 && i0 < nv && i1 >= 0 && i1 < nv && i2 >= 0 && i2 < nv;
+        int64_t i0, i1, i2, a = 0, b = 0, c = 0;
+        bool ok = mk_face_in_range(faces, f, nv, i0, i1, i2);
         if (ok) {
             a = vrank[i0]; b = vrank[i1]; c = vrank[i2];
             ok = a >= 0 && a < n_runs && b >= 0 && b < n_runs && c >= 0 && c < n_runs && a != b && b != c && a != c;
@@ -231,8 +222,8 @@ int launch_simplify_cells(const float* verts, int64_t nv, const float* lo, float
     SqGrid g;
     for (int a = 0; a < 3; ++a) { g.lo[a] = lo[a]; g.dims[a] = dims[a]; }
     g.h = h;
-    hipLaunchKernelGGL(simplify_cells_kernel, dim3(sq_grid(nv)), dim3(SQ_THREADS), 0, st, verts, nv, g, keys);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    hipLaunchKernelGGL(simplify_cells_kernel, dim3(grid_1d(nv, SQ_THREADS)), dim3(SQ_THREADS), 0, st, verts, nv, g, keys);
+    return launch_status();
 }
 
 int simplify_sums() { return SQ_SUMS; }
@@ -247,13 +238,14 @@ int launch_simplify_quadrics(const float* verts, int64_t nv, const int64_t* face
     const int64_t blocks = (n_runs + SQ_THREADS / 64 - 1) / (SQ_THREADS / 64);                    // one wave per run
     hipLaunchKernelGGL(simplify_quadrics_kernel, dim3((unsigned)(blocks < (1 << 16) ? blocks : (1 << 16))), dim3(SQ_THREADS), 0, st,
                        verts, nv, faces, nf, order, run_start, run_key, n_runs, g, lambda, quadric, rep, clamped, sums);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_simplify_faces(const int64_t* faces, int64_t nf, const int32_t* vrank, int64_t nv, int64_t n_runs, int64_t* tri, uint8_t* keep,
                           int64_t* key, hipStream_t st) {
-    hipLaunchKernelGGL(simplify_faces_kernel, dim3(sq_grid(nf)), dim3(SQ_THREADS), 0, st, faces, nf, vrank, nv, n_runs, tri, keep, key);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    hipLaunchKernelGGL(simplify_faces_kernel, dim3(grid_1d(nf, SQ_THREADS)), dim3(SQ_THREADS), 0, st, faces, nf, vrank, nv, n_runs, tri,
+                       keep, key);
+    return launch_status();
 }
 
 }  // namespace dh

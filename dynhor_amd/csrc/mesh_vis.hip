@@ -22,6 +22,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "launch.h"
 #include "mesh_raster.h"
 
 namespace dh {
@@ -271,7 +272,7 @@ static int ms_launch(const float* verts, const float* normals, const uint8_t* co
     blocks = (n_tiles + per * MS_WAVES - 1) / (per * MS_WAVES);
     hipLaunchKernelGGL(mesh_shade_kernel<VEC>, dim3((unsigned)blocks), dim3(MS_THREADS), 0, st, verts, normals, colors, nv, faces, nf,
                        zbuf, R, T, K, H, W, n_pix, rgb, label, alpha, out, counts, per);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int launch_mesh_shade(const float* verts, const float* normals, const uint8_t* colors, int64_t nv, const int64_t* faces, int64_t nf,

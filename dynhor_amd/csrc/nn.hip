@@ -16,6 +16,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "launch.h"
 
 namespace dh {
 
@@ -170,16 +171,16 @@ int launch_nearest_sqdist(const float* q, int64_t nq, const float* ref, int64_t 
     const NnPlan p = ws ? nn_plan(nq, nr) : NnPlan{1, nr};
     if (p.slabs == 1) {
         hipLaunchKernelGGL(nn_sqdist_kernel, dim3((unsigned)qb, 1), dim3(NN_THREADS), 0, st, q, nq, ref, nr, nr, d2, idx, (int64_t)0);
-        return hipGetLastError() == hipSuccess ? 0 : -3;
+        return launch_status();
     }
     // scratch: the slabs' distances [slabs, nq] floats, then their indices [slabs, nq] int32
     float* pd = static_cast<float*>(ws);
     int32_t* pi = reinterpret_cast<int32_t*>(pd + p.slabs * nq);
     hipLaunchKernelGGL(nn_sqdist_kernel, dim3((unsigned)qb, (unsigned)p.slabs), dim3(NN_THREADS), 0, st, q, nq, ref, nr, p.slab_len, pd,
                        pi, nq);
-    if (hipGetLastError() != hipSuccess) return -3;
+    if (launch_status() != DH_OK) return DH_ERR_LAUNCH;
     hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, pd, pi, nq, (int)p.slabs, d2, idx);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int64_t icp_correspond_workspace(int64_t n, int64_t m, int64_t h) {
@@ -194,16 +195,16 @@ int launch_icp_correspond(const float* src, int64_t n, const float* tgt, int64_t
     if (p.slabs == 1) {
         hipLaunchKernelGGL((icp_correspond_kernel), dim3((unsigned)qb, 1, (unsigned)h), dim3(NN_THREADS), 0, st, src, n, tgt, m, m, xf, d2,
                            idx);
-        return hipGetLastError() == hipSuccess ? 0 : -3;
+        return launch_status();
     }
     // scratch: the slabs' distances [h, slabs, n] floats, then their indices [h, slabs, n] int32
     float* pd = static_cast<float*>(ws);
     int32_t* pi = reinterpret_cast<int32_t*>(pd + h * p.slabs * n);
     hipLaunchKernelGGL((icp_correspond_kernel), dim3((unsigned)qb, (unsigned)p.slabs, (unsigned)h), dim3(NN_THREADS), 0, st, src, n, tgt, m,
                        p.slab_len, xf, pd, pi);
-    if (hipGetLastError() != hipSuccess) return -3;
+    if (launch_status() != DH_OK) return DH_ERR_LAUNCH;
     hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)h), dim3(256), 0, st, pd, pi, n, (int)p.slabs, d2, idx);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 }  // namespace dh

@@ -5,8 +5,8 @@
 // where the window holds no such pixel.  Two separable passes: rows write g^2 (g the nearest such pixel of the row within rmax) into
 // the caller's tmp, columns take min_dy (dy^2 + tmp).  rmax <= 2896 (api.hip), so every value is an integer <= 2 rmax^2 < 2^24: exact in fp32.
 //
-// sil_face_kernel: one lane per (frame, face), frame-major, with the projection, the skip rule and the wave phase of
-// mesh_raster_kernel (mesh_color.hip).  near[f,y,x] = (float_bits(d2) << 32) | face by a 64-bit agent-scope atomic minimum, d2 the
+// sil_face_kernel: the face walker of mesh_raster.h with sl_pixel as its per-pixel operation.
+// near[f,y,x] = (float_bits(d2) << 32) | face by a 64-bit agent-scope atomic minimum, d2 the
 // squared distance in pixels from the pixel centre to the face: 0 where the face covers the centre under the rasteriser's rule
 // (mk_edge values all >= 0 or all <= 0, their sum != 0), else the distance to the nearest of its three edge segments
 //   seg(a, b, p): ab = b - a, ap = p - a, t = clamp(<ap, ab> / <ab, ab>, 0, 1) (0 for a == b), r = ap - t ab, d2 = fma(r.w, r.w, r.u r.u)
@@ -29,40 +29,26 @@
 //   du/dc = (K00, K01, K02 - u) / z (dw/dc alike) to G_a, G_b = d/dx_cam; sums[11..13] += G_a + G_b, sums[2 + 3 r + c] += G_a[r] v_a[c]
 //   + G_b[r] v_b[c].  sums[14..16] += (tp, fp, fn) over label >= 0: (covered and label 1, covered and label 0, uncovered and label 1),
 //   covered = near's d2 bits are 0 (dh_mesh_shade's convention).
-// Reduction as icp.hip: every lane adds its pixels in ascending order, a fixed xor butterfly folds the wave, the four waves are added in
-// order, the workgroup stores its partial and sil_loss_reduce_kernel adds the partials in block order.  The number of workgroups per
-// frame depends on H W alone: bitwise reproducible from launch to launch and for every frame chunking.
+// Reduction: sums64.h (every lane adds its pixels in ascending order).  The number of workgroups per frame depends on H W alone: bitwise
+// reproducible from launch to launch and for every frame chunking.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "launch.h"
 #include "mesh_raster.h"
+#include "sums64.h"
 
 namespace dh {
 
 namespace {
 constexpr int SL_THREADS = 256;
-constexpr int SL_SMALL_BOX = 32;
 constexpr int SL_TILE = 16;
 constexpr int SL_MAX_SKIP_TILES = 64;          // a grown box over more tiles than this is not tested for the skip
 constexpr int SL_SUMS = 17;
 constexpr int64_t SL_MAX_BLOCKS = 64;          // workgroups per frame of the loss kernel
 constexpr float SL_FLT_MIN = 1.17549435e-38f;
 constexpr float SL_BOUND_MARGIN = 0.9999f;
-
-inline unsigned sl_grid(int64_t n) {
-    const int64_t b = (n + SL_THREADS - 1) / SL_THREADS;
-    return (unsigned)(b < 1 ? 1 : (b < (1 << 20) ? b : (1 << 20)));      // grid-stride loops cover the rest
-}
-
-inline int64_t sl_blocks(int64_t hw) {
-    const int64_t b = (hw + SL_THREADS - 1) / SL_THREADS;
-    return b < 1 ? 1 : (b < SL_MAX_BLOCKS ? b : SL_MAX_BLOCKS);
-}
-
-struct STri {
-    float u0, w0, u1, w1, u2, w2;
-};
 
 __device__ inline float sl_seg(float au, float aw, float bu, float bw, float px, float py) {
     const float abu = bu - au, abw = bw - aw, apu = px - au, apw = py - aw;
@@ -78,16 +64,13 @@ __device__ inline void sl_put(uint64_t* p, uint64_t cur, uint64_t key) {
 }
 
 template <bool HALO>
-__device__ inline void sl_pixel(const STri& t, float r2, int x, int y, uint32_t face, uint64_t* zrow) {
+__device__ inline void sl_pixel(const Tri<6>& t, float r2, int x, int y, uint32_t face, uint64_t* zrow) {
     const float px = (float)x, py = (float)y;
     const uint64_t cur = zrow[x];
     if (!HALO) {
         if (cur <= (uint64_t)face) return;
-        const float e0 = mk_edge(t.u1, t.w1, t.u2, t.w2, px, py);
-        const float e1 = mk_edge(t.u2, t.w2, t.u0, t.w0, px, py);
-        const float e2 = mk_edge(t.u0, t.w0, t.u1, t.w1, px, py);
-        const bool pos = (e0 >= 0.f) & (e1 >= 0.f) & (e2 >= 0.f), neg = (e0 <= 0.f) & (e1 <= 0.f) & (e2 <= 0.f);
-        if (!(pos | neg) || e0 + e1 + e2 == 0.f) return;
+        float e0, e1, e2;
+        if (!mk_covers(t, px, py, e0, e1, e2)) return;
         sl_put(zrow + x, cur, (uint64_t)face);
     } else {
         const uint32_t hi = (uint32_t)(cur >> 32);
@@ -106,6 +89,28 @@ __device__ inline void sl_pixel(const STri& t, float r2, int x, int y, uint32_t 
         sl_put(zrow + x, cur, ((uint64_t)__float_as_uint(d2) << 32) | face);
     }
 }
+
+// The walker's operation: sl_pixel, and for the HALO launch the per-face test "does the grown box touch a tile with an uncovered pixel"
+template <bool HALO>
+struct SlNearest {
+    static constexpr int N = 6;
+    static constexpr bool FACE_TEST = HALO;
+    float r2;
+    const uint8_t* tiles;
+    int TH, TW;
+    __device__ __forceinline__ bool work(int64_t f, int x0, int x1, int y0, int y1) const {
+        const int tx0 = x0 / SL_TILE, tx1 = x1 / SL_TILE, ty0 = y0 / SL_TILE, ty1 = y1 / SL_TILE;
+        if ((int64_t)(tx1 - tx0 + 1) * (ty1 - ty0 + 1) > SL_MAX_SKIP_TILES) return true;
+        const uint8_t* tf = tiles + f * (int64_t)TH * TW;
+        uint8_t open = 0;
+        for (int ty = ty0; ty <= ty1; ++ty)
+            for (int tx = tx0; tx <= tx1; ++tx) open |= tf[(int64_t)ty * TW + tx];
+        return open != 0;
+    }
+    __device__ __forceinline__ void pixel(const Tri<6>& t, int x, int y, uint32_t face, uint64_t* zrow) const {
+        sl_pixel<HALO>(t, r2, x, y, face, zrow);
+    }
+};
 }  // namespace
 
 // grid (n_frames * H image rows, column blocks)
@@ -160,85 +165,12 @@ __global__ __launch_bounds__(SL_THREADS) void sil_tiles_kernel(const uint64_t* _
 }
 
 template <bool HALO>
-__global__ __launch_bounds__(SL_THREADS) void sil_face_kernel(const float* __restrict__ verts, int64_t nv,
+__global__ __launch_bounds__(MK_THREADS) void sil_face_kernel(const float* __restrict__ verts, int64_t nv,
                                                               const int64_t* __restrict__ faces, int64_t nf,
                                                               const float* __restrict__ R, const float* __restrict__ T,
                                                               const float* __restrict__ K, int64_t n_frames, int H, int W, float rmax,
                                                               const uint8_t* __restrict__ tiles, int TH, int TW, uint64_t* near) {
-    const float k00 = K[0], k01 = K[1], k02 = K[2], k10 = K[3], k11 = K[4], k12 = K[5];
-    const int64_t total = n_frames * nf, HW = (int64_t)H * W;
-    const int lane = threadIdx.x & 63;
-    const float grow = HALO ? rmax : 0.f, r2 = rmax * rmax;
-    // the loop bound is block-uniform, so every lane of a wave reaches the ballot of every iteration
-    for (int64_t base = (int64_t)blockIdx.x * SL_THREADS; base < total; base += (int64_t)gridDim.x * SL_THREADS) {
-        const int64_t i = base + threadIdx.x;
-        bool big = false;
-        STri t = {};
-        int64_t f = 0;
-        uint32_t face = 0;
-        int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
-        if (i < total) {
-            f = i / nf;
-            const int64_t fi = i - f * nf;
-            face = (uint32_t)fi;
-            const int64_t a = faces[fi * 3 + 0], b = faces[fi * 3 + 1], c = faces[fi * 3 + 2];
-            if (a >= 0 && a < nv && b >= 0 && b < nv && c >= 0 && c < nv) {
-                const float* Rf = R + f * 9;
-                const float* Tf = T + f * 3;
-                const Cam p0 = mk_project(Rf, Tf, k00, k01, k02, k10, k11, k12, verts[a * 3], verts[a * 3 + 1], verts[a * 3 + 2]);
-                const Cam p1 = mk_project(Rf, Tf, k00, k01, k02, k10, k11, k12, verts[b * 3], verts[b * 3 + 1], verts[b * 3 + 2]);
-                const Cam p2 = mk_project(Rf, Tf, k00, k01, k02, k10, k11, k12, verts[c * 3], verts[c * 3 + 1], verts[c * 3 + 2]);
-                t = STri{p0.u, p0.w, p1.u, p1.w, p2.u, p2.w};
-                const float lim = 3.0e38f;    // |u|, |w| < lim: finite, and every comparison below is false for a NaN
-                const bool ok = (p0.c2 > 1e-3f) & (p1.c2 > 1e-3f) & (p2.c2 > 1e-3f) & (fabsf(p0.u) < lim) & (fabsf(p0.w) < lim) &
-                                (fabsf(p1.u) < lim) & (fabsf(p1.w) < lim) & (fabsf(p2.u) < lim) & (fabsf(p2.w) < lim) &
-                                (mk_edge(p0.u, p0.w, p1.u, p1.w, p2.u, p2.w) != 0.f);
-                const float fx0 = fmaxf(ceilf(fminf(fminf(p0.u, p1.u), p2.u) - grow), 0.f);
-                const float fx1 = fminf(floorf(fmaxf(fmaxf(p0.u, p1.u), p2.u) + grow), (float)(W - 1));
-                const float fy0 = fmaxf(ceilf(fminf(fminf(p0.w, p1.w), p2.w) - grow), 0.f);
-                const float fy1 = fminf(floorf(fmaxf(fmaxf(p0.w, p1.w), p2.w) + grow), (float)(H - 1));
-                if (ok && fx0 <= fx1 && fy0 <= fy1) {
-                    x0 = (int)fx0; x1 = (int)fx1; y0 = (int)fy0; y1 = (int)fy1;
-                    bool work = true;
-                    if (HALO) {
-                        const int tx0 = x0 / SL_TILE, tx1 = x1 / SL_TILE, ty0 = y0 / SL_TILE, ty1 = y1 / SL_TILE;
-                        if ((int64_t)(tx1 - tx0 + 1) * (ty1 - ty0 + 1) <= SL_MAX_SKIP_TILES) {
-                            const uint8_t* tf = tiles + f * (int64_t)TH * TW;
-                            uint8_t open = 0;
-                            for (int ty = ty0; ty <= ty1; ++ty)
-                                for (int tx = tx0; tx <= tx1; ++tx) open |= tf[(int64_t)ty * TW + tx];
-                            work = open != 0;
-                        }
-                    }
-                    big = work & ((x1 - x0 >= SL_SMALL_BOX) | (y1 - y0 >= SL_SMALL_BOX));
-                    if (work & !big) {
-                        uint64_t* zf = near + f * HW;
-                        for (int y = y0; y <= y1; ++y)
-                            for (int x = x0; x <= x1; ++x) sl_pixel<HALO>(t, r2, x, y, face, zf + (int64_t)y * W);
-                    }
-                }
-            }
-        }
-        // wave phase: the deferred faces of this wave, one at a time, their boxes spread over the 64 lanes
-        uint64_t todo = __ballot(big);
-        while (todo) {
-            const int src = __ffsll((unsigned long long)todo) - 1;
-            todo &= todo - 1;
-            STri s;
-            s.u0 = __shfl(t.u0, src); s.w0 = __shfl(t.w0, src); s.u1 = __shfl(t.u1, src); s.w1 = __shfl(t.w1, src);
-            s.u2 = __shfl(t.u2, src); s.w2 = __shfl(t.w2, src);
-            const uint32_t sface = (uint32_t)__shfl((int)face, src);
-            const int64_t sf = (int64_t)__shfl((int)f, src);          // f < n_frames < 2^31 (api.hip)
-            const int sx0 = __shfl(x0, src), sx1 = __shfl(x1, src), sy0 = __shfl(y0, src), sy1 = __shfl(y1, src);
-            const int bw = sx1 - sx0 + 1;
-            const int64_t npix = (int64_t)bw * (sy1 - sy0 + 1);
-            uint64_t* zf = near + sf * HW;
-            for (int64_t p = lane; p < npix; p += 64) {
-                const int y = sy0 + (int)(p / bw), x = sx0 + (int)(p % bw);
-                sl_pixel<HALO>(s, r2, x, y, sface, zf + (int64_t)y * W);
-            }
-        }
-    }
+    mk_walk_faces(verts, nv, faces, nf, R, T, K, n_frames, H, W, HALO ? rmax : 0.f, near, SlNearest<HALO>{rmax * rmax, tiles, TH, TW});
 }
 
 namespace {
@@ -283,13 +215,13 @@ __device__ inline void sl_chain(double* acc, const DCam& c, const double* Kd, co
 }  // namespace
 
 // grid (blocks, frames); partial [frames, blocks, SL_SUMS] doubles
+static_assert(SL_THREADS == SUM64_THREADS, "sum64_block_store folds a workgroup of SUM64_THREADS");
 __global__ __launch_bounds__(SL_THREADS) void sil_loss_kernel(const uint64_t* __restrict__ near, const float* __restrict__ verts, int64_t nv,
                                                               const int64_t* __restrict__ faces, int64_t nf, const float* __restrict__ R,
                                                               const float* __restrict__ T, const float* __restrict__ K,
                                                               const float* __restrict__ d2_obj, const float* __restrict__ d2_hand,
                                                               const int8_t* __restrict__ label, int H, int W, float sigma, float cut,
                                                               float edge_offset, double* __restrict__ partial) {
-    __shared__ double wave_sum[SL_THREADS / 64][SL_SUMS];
     const int64_t f = blockIdx.y, HW = (int64_t)H * W;
     const float cs = cut * sigma, cs2f = cs * cs;
     const double cs2 = cs2f, s2 = (double)sigma * (double)sigma;
@@ -312,10 +244,7 @@ __global__ __launch_bounds__(SL_THREADS) void sil_loss_kernel(const uint64_t* __
         const int64_t fi = (int64_t)(key & 0xffffffffu);
         int64_t a = 0, b = 0, c = 0;
         bool have = key != MK_EMPTY && fi < nf;
-        if (have) {
-            a = faces[fi * 3 + 0]; b = faces[fi * 3 + 1]; c = faces[fi * 3 + 2];
-            have = a >= 0 && a < nv && b >= 0 && b < nv && c >= 0 && c < nv;
-        }
+        if (have) have = mk_face_in_range(faces, fi, nv, a, b, c);
         const bool covered = have && (key >> 32) == 0;
         if (lab >= 0) {
             acc[14] += (covered && lab == 1) ? 1.0 : 0.0;
@@ -359,39 +288,15 @@ __global__ __launch_bounds__(SL_THREADS) void sil_loss_kernel(const uint64_t* __
         }
         acc[0] += (S - M) * (S - M);
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < SL_SUMS; ++k) {
-        double v = acc[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) wave_sum[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < SL_SUMS) {
-        double v = wave_sum[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < SL_THREADS / 64; ++w) v += wave_sum[w][threadIdx.x];
-        partial[(f * gridDim.x + blockIdx.x) * SL_SUMS + threadIdx.x] = v;
-    }
-}
-
-// grid (frames), 64 threads: out[f, k] = the partials of frame f added in block order
-__global__ void sil_loss_reduce_kernel(const double* __restrict__ partial, int blocks, double* __restrict__ out) {
-    const int k = threadIdx.x;
-    if (k >= SL_SUMS) return;
-    const double* p = partial + (int64_t)blockIdx.x * blocks * SL_SUMS + k;
-    double v = 0.0;
-    for (int b = 0; b < blocks; ++b) v += p[(int64_t)b * SL_SUMS];
-    out[(int64_t)blockIdx.x * SL_SUMS + k] = v;
+    sum64_block_store(acc, partial + (f * gridDim.x + blockIdx.x) * SL_SUMS);
 }
 
 int launch_label_edt(const int8_t* label, int64_t n_frames, int H, int W, int value, int rmax, float* tmp, float* out, hipStream_t st) {
     const dim3 grid((unsigned)(n_frames * H), (unsigned)((W + SL_THREADS - 1) / SL_THREADS));
     hipLaunchKernelGGL(label_edt_rows_kernel, grid, dim3(SL_THREADS), 0, st, label, W, value, rmax, tmp);
-    if (hipGetLastError() != hipSuccess) return -3;
+    if (launch_status() != DH_OK) return DH_ERR_LAUNCH;
     hipLaunchKernelGGL(label_edt_cols_kernel, grid, dim3(SL_THREADS), 0, st, tmp, H, W, rmax, out);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int64_t sil_nearest_workspace(int64_t n_frames, int H, int W) {
@@ -403,33 +308,33 @@ int launch_sil_nearest(const float* verts, int64_t nv, const int64_t* faces, int
                        int64_t n_frames, int H, int W, float rmax_px, uint64_t* near, void* ws, hipStream_t st) {
     const int TH = (H + SL_TILE - 1) / SL_TILE, TW = (W + SL_TILE - 1) / SL_TILE;
     uint8_t* tiles = static_cast<uint8_t*>(ws);
-    const dim3 grid(sl_grid(n_frames * nf));
-    hipLaunchKernelGGL((sil_face_kernel<false>), grid, dim3(SL_THREADS), 0, st, verts, nv, faces, nf, R, T, K, n_frames, H, W, rmax_px,
+    const dim3 grid(grid_1d(n_frames * nf, MK_THREADS));
+    hipLaunchKernelGGL((sil_face_kernel<false>), grid, dim3(MK_THREADS), 0, st, verts, nv, faces, nf, R, T, K, n_frames, H, W, rmax_px,
                        tiles, TH, TW, near);
-    if (hipGetLastError() != hipSuccess) return -3;
-    hipLaunchKernelGGL(sil_tiles_kernel, dim3(sl_grid(n_frames * TH * TW)), dim3(SL_THREADS), 0, st, near, n_frames, H, W, TH, TW, tiles);
-    if (hipGetLastError() != hipSuccess) return -3;
-    hipLaunchKernelGGL((sil_face_kernel<true>), grid, dim3(SL_THREADS), 0, st, verts, nv, faces, nf, R, T, K, n_frames, H, W, rmax_px,
+    if (launch_status() != DH_OK) return DH_ERR_LAUNCH;
+    hipLaunchKernelGGL(sil_tiles_kernel, dim3(grid_1d(n_frames * TH * TW, SL_THREADS)), dim3(SL_THREADS), 0, st, near, n_frames, H, W, TH,
+                       TW, tiles);
+    if (launch_status() != DH_OK) return DH_ERR_LAUNCH;
+    hipLaunchKernelGGL((sil_face_kernel<true>), grid, dim3(MK_THREADS), 0, st, verts, nv, faces, nf, R, T, K, n_frames, H, W, rmax_px,
                        tiles, TH, TW, near);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_status();
 }
 
 int sil_loss_sums() { return SL_SUMS; }
 
 int64_t sil_loss_grad_workspace(int64_t n_frames, int H, int W) {
-    return n_frames * sl_blocks((int64_t)H * W) * SL_SUMS * (int64_t)sizeof(double);
+    return n_frames * sum64_blocks((int64_t)H * W, SL_MAX_BLOCKS) * SL_SUMS * (int64_t)sizeof(double);
 }
 
 int launch_sil_loss_grad(const uint64_t* near, const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* R,
                          const float* T, const float* K, const float* d2_obj, const float* d2_hand, const int8_t* label, int64_t n_frames,
                          int H, int W, float sigma, float cut, float edge_offset, double* out, void* ws, hipStream_t st) {
-    const int64_t blocks = sl_blocks((int64_t)H * W);
+    const int64_t blocks = sum64_blocks((int64_t)H * W, SL_MAX_BLOCKS);
     double* partial = static_cast<double*>(ws);
     hipLaunchKernelGGL(sil_loss_kernel, dim3((unsigned)blocks, (unsigned)n_frames), dim3(SL_THREADS), 0, st, near, verts, nv, faces, nf, R,
                        T, K, d2_obj, d2_hand, label, H, W, sigma, cut, edge_offset, partial);
-    if (hipGetLastError() != hipSuccess) return -3;
-    hipLaunchKernelGGL(sil_loss_reduce_kernel, dim3((unsigned)n_frames), dim3(64), 0, st, partial, (int)blocks, out);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    if (launch_status() != DH_OK) return DH_ERR_LAUNCH;
+    return launch_sum64_reduce(partial, n_frames, (int)blocks, SL_SUMS, out, st);
 }
 
 }  // namespace dh

@@ -1,0 +1,238 @@
+"""The mesh kernels' outputs bit for bit against tests/golden/mesh_kernel_bits.json, one SHA-256 per output tensor, recorded by
+tests/golden/make_golden_mesh_kernel_bits.py at the commit the file names.  Every output here is reproducible by construction (64-bit
+atomic minima, integer counts, fixed-order fp64 sums), so a change to these kernels that means to change no arithmetic must leave every
+hash as it is: a differing hash is a finding to explain, never a reason to record again.  The inputs are the cases of the kernels' own
+tests (their builders imported), plus one ten-face mesh that walks the rasteriser's skip rules; every input tensor is hashed as well
+("in:" entries), so that a failure says whether the inputs or the kernel moved."""
+import functools
+import hashlib
+import json
+import math
+import os
+
+import pytest
+import torch
+
+from tests import pose_sil_util as U
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda:0")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mesh_kernel_bits.json")
+
+
+def sha(t: torch.Tensor) -> str:
+    return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def _ins(**tensors):
+    return {"in:" + k: v for k, v in tensors.items()}
+
+
+# ------------------------------------------------------------------------------------------------ the cases
+def _raster(which):
+    from dynhor_amd.mesh_color import raster_depth
+    from tests.test_gpu_mesh_color import _scenes
+    H, W, R, T, K, meshes = _scenes()
+    verts, faces = meshes[which]
+    return dict(_ins(verts=verts, faces=faces, R=R, T=T), zbuf=raster_depth(verts, faces, R, T, K, H, W))
+
+
+def _bake():
+    """The inputs of test_gpu_mesh_color.test_bake_matches_fp64_and_chunking."""
+    from dynhor_amd import _lib
+    from dynhor_amd.dataset import Dataset
+    from dynhor_amd.mesh_color import raster_depth, usable_map, vertex_normals
+    from dynhor_amd.scene import scene_sdf
+    from tests.test_gpu_mesh_color import _mesh_of
+    ds = Dataset.from_synthetic(n_frames=7, H=96, W=128, seed=3, device=DEV, hand=True)
+    verts, faces = _mesh_of(scene_sdf, N=96)
+    normals = vertex_normals(verts, faces)
+    zbuf = raster_depth(verts, faces, ds.R, ds.T, ds.K, ds.H, ds.W)
+    usable = usable_map(ds.label, 1)
+    nv = verts.shape[0]
+    acc = torch.zeros(nv, 4, device=DEV)
+    cnt = torch.zeros(nv, dtype=torch.int32, device=DEV)
+    _lib.check(_lib.lib().dh_mesh_bake_colors(_lib.ptr(verts), _lib.ptr(normals), nv, _lib.ptr(ds.rgb), _lib.ptr(usable),
+                                              _lib.ptr(zbuf), _lib.ptr(ds.R), _lib.ptr(ds.T), _lib.ptr(ds.K), ds.n_images, ds.H, ds.W,
+                                              0.01, 0.1, _lib.ptr(acc), _lib.ptr(cnt), _lib.stream()))
+    return dict(_ins(verts=verts, faces=faces, normals=normals, rgb=ds.rgb, usable=usable, R=ds.R, T=ds.T), zbuf=zbuf, acc=acc,
+                n_views=cnt)
+
+
+def _nearest(kind):
+    """test_gpu_pose_sil._nearest_case without its label maps: nearest_faces takes none, they draw nothing from the scene's random
+    generator, and rendering them on the CPU is nearly all of that builder's 12 s for the fine mesh.  The recorded input hashes hold
+    the meshes and poses to those of the full builder, which the recording used."""
+    from unittest import mock
+    from dynhor_amd.pose_sil import nearest_faces
+    from tests.test_gpu_pose_sil import _nearest_case
+    with mock.patch.object(U, "render_labels", lambda *a, **k: torch.zeros(0, dtype=torch.int8)):
+        _, d = _nearest_case(kind)
+    return dict(_ins(verts=d.verts, faces=d.faces, R=d.R0, T=d.T0),
+                near=nearest_faces(d.verts, d.faces, d.R0, d.T0, d.K, d.H, d.W, 12.0))
+
+
+def _sil_loss(sigma):
+    """test_gpu_pose_sil.test_loss_sums_and_gradient_against_the_restatement at one sigma."""
+    from dynhor_amd.pose_sil import halo_radius, label_edt, nearest_faces, silhouette_sums
+    from tests.test_gpu_pose_sil import _dev
+    d = _dev(U.small_scene())
+    cut, delta = 3.0, 0.5
+    rmax = int(math.ceil(cut * sigma + delta)) + 1
+    d2o, d2h = label_edt(d.label, 1, rmax), label_edt(d.label, -1, rmax)
+    near = nearest_faces(d.verts, d.faces, d.R0, d.T0, d.K, d.H, d.W, halo_radius(sigma, cut))
+    sums = silhouette_sums(d.verts, d.faces, near, d.R0, d.T0, d.K, d2o, d2h, d.label, sigma, cut, delta)
+    return dict(_ins(verts=d.verts, faces=d.faces, R=d.R0, T=d.T0, label=d.label, d2_obj=d2o, d2_hand=d2h), near=near, sums=sums)
+
+
+def _votes():
+    """The inputs of test_gpu_mesh_clean.test_votes_match_fp64_restatement."""
+    from dynhor_amd.dataset import Dataset
+    from dynhor_amd.mesh_clean import dilate_labels, mask_votes
+    from tests.test_gpu_mesh_clean import _pixel_points
+    ds = Dataset.from_synthetic(n_frames=6, H=48, W=64, seed=11, device=DEV, hand=True)
+    keep = dilate_labels(ds.label, 0)
+    g = torch.Generator(device="cpu").manual_seed(3)
+    pts = [torch.rand(4000, 3, generator=g) * 1.6 - 0.8, torch.rand(500, 3, generator=g) * 10.0 - 5.0]
+    lab0 = ds.label[0].cpu()
+    for value in (-1, 0, 1):
+        yx = (lab0 == value).nonzero()
+        sel = yx[torch.randperm(yx.shape[0], generator=g)[:300]]
+        depth = 1.5 + torch.rand(sel.shape[0], generator=g, dtype=torch.float64)
+        pts.append(_pixel_points(ds, 0, sel[:, 1].to(DEV), sel[:, 0].to(DEV), depth.to(DEV)).cpu())
+    cam = -(ds.T[1].double() @ ds.R[1].double())
+    fwd = ds.R[1, 2].double()
+    pts.append((cam[None] - fwd[None] * torch.linspace(1e-3, 1.0, 200, dtype=torch.float64, device=DEV)[:, None]).float().cpu())
+    verts = torch.cat(pts).to(DEV).contiguous()
+    bg, seen = mask_votes(verts, keep, ds.R, ds.T, ds.K)
+    return dict(_ins(verts=verts, keep=keep, R=ds.R, T=ds.T), bg_votes=bg, seen=seen)
+
+
+@functools.lru_cache(maxsize=None)
+def _moments_inputs():
+    """The inputs of test_gpu_mesh_align.test_moments_match_fp64_sums_and_are_reproducible, shared by the point and the plane case."""
+    from dynhor_amd.mesh_align import icp_correspond
+    from tests.test_gpu_mesh_align import _clouds, _transforms
+    n, m, H = 1_000_000, 50_000, 3
+    src, tgt = _clouds(n, m, seed=17)
+    g = torch.Generator(device=DEV).manual_seed(2)
+    nrm = torch.randn(m, 3, device=DEV, generator=g)
+    nrm = (nrm / nrm.norm(dim=1, keepdim=True)).contiguous()
+    xf, _ = _transforms(H, seed=5)
+    d2, idx = icp_correspond(src, tgt, xf)
+    thr = torch.kthvalue(d2, int(0.9 * n), dim=1).values
+    return src, tgt, nrm, xf, idx, d2, thr, src.mean(0), tgt.mean(0)
+
+
+def _moments(plane):
+    from dynhor_amd.mesh_align import icp_moments
+    src, tgt, nrm, xf, idx, d2, thr, o_src, o_tgt = _moments_inputs()
+    out = icp_moments(src, tgt, nrm if plane else None, xf, idx, d2, thr, o_src, o_tgt)
+    return dict(_ins(src=src, tgt=tgt, nrm=nrm, xf=xf, idx=idx, d2=d2, thr=thr, o_src=o_src, o_tgt=o_tgt), moments=out)
+
+
+def _simplify():
+    """The five outputs of simplify_mesh(return_sums=True) on the smallest mesh builder of test_gpu_mesh_simplify.py."""
+    from dynhor_amd.mesh_simplify import simplify_mesh
+    from tests.test_gpu_mesh_simplify import _coarse_ellipsoid
+    v, f = _coarse_ellipsoid()
+    v, f = v.to(DEV), f.to(DEV)
+    ov, of, stats, extra = simplify_mesh(v, f, cells=6, return_sums=True)
+    return dict(_ins(verts=v, faces=f), verts=ov, faces=of, sums=extra["sums"], keys=extra["keys"], used=extra["used"],
+                n_clamped=torch.tensor([stats["n_clamped"]], dtype=torch.int64))
+
+
+# The skip rules of the face walker, which no other test reaches: ten faces in one 64 x 96 frame, given as (u, w, depth) per corner and
+# unprojected through K (R = I, T = 0).  Faces 0..3 must be rejected whole; face 4 has no pixel; 5..8 are clipped by one border each;
+# face 9 is 60 px wide (the wave phase).
+SKIP_H, SKIP_W, SKIP_F, SKIP_RMAX = 64, 96, 80.0, 12.0
+SKIP_CORNERS = [
+    [(10, 10, 2.0), (20, 10, 2.0), (15, 20, -1.0)],          # 0: a vertex behind the camera
+    [(30, 10, 2.0), (30, 10, 2.0), (40, 15, 2.0)],           # 1: zero area (two corners coincide)
+    [(50, 10, 2.0), (60, 10, 2.0), (55, 20, 2.0)],           # 2: its third index is nv
+    [(70, 10, 2.0), (80, 10, 2.0), (75, 20, 2.0)],           # 3: its first index is -1
+    [(200, 10, 2.0), (220, 10, 2.0), (210, 30, 2.0)],        # 4: wholly off-image (and farther than the halo)
+    [(-10, 20, 2.1), (10, 22, 2.1), (0, 35, 2.1)],           # 5: clipped by the left border
+    [(90, 20, 2.2), (110, 25, 2.2), (95, 35, 2.2)],          # 6: right
+    [(40, -8, 2.3), (55, 5, 2.3), (45, 8, 2.3)],             # 7: top
+    [(40, 70, 2.4), (60, 58, 2.4), (50, 55, 2.4)],           # 8: bottom
+    [(15, 40, 3.0), (75, 45, 3.0), (40, 62, 3.0)],           # 9: wider than 32 px
+]
+SKIP_REJECTED, SKIP_DRAWN = (0, 1, 2, 3), (5, 6, 7, 8, 9)
+
+
+def _skip_mesh():
+    cx, cy = SKIP_W // 2, SKIP_H // 2
+    verts = [((u - cx) * z / SKIP_F, (w - cy) * z / SKIP_F, z) for tri in SKIP_CORNERS for (u, w, z) in tri]
+    faces = [[3 * i, 3 * i + 1, 3 * i + 2] for i in range(len(SKIP_CORNERS))]
+    faces[2][2] = len(verts)
+    faces[3][0] = -1
+    K = torch.tensor([[SKIP_F, 0, cx], [0, SKIP_F, cy], [0, 0, 1]], dtype=torch.float32)
+    return (torch.tensor(verts, dtype=torch.float32).to(DEV), torch.tensor(faces, dtype=torch.int64).to(DEV),
+            torch.eye(3).reshape(1, 3, 3).to(DEV).contiguous(), torch.zeros(1, 3, device=DEV), K.to(DEV))
+
+
+def _skip_rules():
+    """The wrappers refuse a mesh with indices outside [0, nv), so this one goes through the library directly."""
+    from dynhor_amd import _lib
+    L = _lib.lib()
+    verts, faces, R, T, K = _skip_mesh()
+    nv, nf, H, W = verts.shape[0], faces.shape[0], SKIP_H, SKIP_W
+    zbuf = torch.full((1, H, W), -1, dtype=torch.int64, device=DEV)
+    near = torch.full((1, H, W), -1, dtype=torch.int64, device=DEV)
+    ws = torch.empty(int(L.dh_sil_nearest_workspace(1, H, W)), dtype=torch.uint8, device=DEV)
+    _lib.check(L.dh_mesh_raster_depth(_lib.ptr(verts), nv, _lib.ptr(faces), nf, _lib.ptr(R), _lib.ptr(T), _lib.ptr(K), 1, H, W,
+                                      _lib.ptr(zbuf), _lib.stream()))
+    _lib.check(L.dh_sil_nearest(_lib.ptr(verts), nv, _lib.ptr(faces), nf, _lib.ptr(R), _lib.ptr(T), _lib.ptr(K), 1, H, W, SKIP_RMAX,
+                                _lib.ptr(near), _lib.ptr(ws), _lib.stream()))
+    return dict(_ins(verts=verts, faces=faces), zbuf=zbuf, near=near)
+
+
+CASES = {
+    "raster_triangles": functools.partial(_raster, 0),
+    "raster_sphere": functools.partial(_raster, 1),
+    "bake": _bake,
+    "nearest_coarse": functools.partial(_nearest, "coarse"),
+    "nearest_fine": functools.partial(_nearest, "fine"),
+    "sil_loss_sigma4": functools.partial(_sil_loss, 4.0),
+    "sil_loss_sigma1.5": functools.partial(_sil_loss, 1.5),
+    "votes": _votes,
+    "moments_point": functools.partial(_moments, False),
+    "moments_plane": functools.partial(_moments, True),
+    "simplify": _simplify,
+    "skip_rules": _skip_rules,
+}
+
+
+def hashes(case):
+    return {k: sha(v) for k, v in CASES[case]().items()}
+
+
+# ------------------------------------------------------------------------------------------------ the tests
+@pytest.mark.parametrize("case", list(CASES))
+def test_outputs_equal_the_recorded_bits(case):
+    golden = json.load(open(GOLDEN))
+    want = golden["hashes"][case]
+    got = hashes(case)
+    assert sorted(got) == sorted(want), (sorted(got), sorted(want))
+    moved_in = [k for k in got if k.startswith("in:") and got[k] != want[k]]
+    assert not moved_in, f"{case}: the INPUTS differ from the recording (not the kernels under test): {moved_in}"
+    moved = [k for k in got if got[k] != want[k]]
+    assert not moved, f"{case}: outputs differ from the bits recorded at {golden['commit'][:12]} (library {golden['lib_sha16']}): {moved}"
+
+
+def test_skip_rules_reject_four_faces_and_draw_five():
+    out = _skip_rules()
+    for name in ("zbuf", "near"):
+        buf = out[name]
+        ids = set((buf[buf != -1] & 0xFFFFFFFF).unique().tolist())
+        assert not ids & set(SKIP_REJECTED), (name, sorted(ids))
+        assert 4 not in ids and ids == set(SKIP_DRAWN), (name, sorted(ids))
+    covered = out["zbuf"] != -1
+    assert torch.equal(((out["near"] >> 32) == 0) & (out["near"] != -1), covered)
+    # every border is reached, and face 9's clipped box is wider than the per-lane path takes
+    ys, xs = covered[0].nonzero(as_tuple=True)
+    assert int(xs.min()) == 0 and int(xs.max()) == SKIP_W - 1 and int(ys.min()) == 0 and int(ys.max()) == SKIP_H - 1
+    wide = ((out["zbuf"][0] & 0xFFFFFFFF) == 9) & covered[0]
+    assert int(wide.any(dim=0).sum()) > 32
