@@ -98,6 +98,10 @@ SIGNATURES = {
     "dh_mesh_raster_depth": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "dh_mesh_bake_colors": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _vp, _vp, _vp]),
     "dh_mesh_shade": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "dh_texture_bake": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _i32,
+                               _vp, _vp, _vp]),
+    "dh_mesh_shade_tex": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _f32,
+                                 _i32, _vp, _vp, _vp]),
     "dh_label_edt": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dh_sil_nearest_workspace": (_i64, [_i64, _i32, _i32]),
     "dh_sil_nearest": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp]),

@@ -684,6 +684,40 @@ int dh_mesh_shade(const float* verts, const float* normals, const uint8_t* color
                              static_cast<hipStream_t>(stream));
 }
 
+int dh_texture_bake(const float* verts, const float* normals, int64_t nv, const int64_t* faces, int64_t nf, const float* uv,
+                    const int32_t* owner, int S, const uint8_t* rgb, const uint8_t* usable, const uint64_t* zbuf, const float* R,
+                    const float* T, const float* K, int64_t n_frames, int H, int W, float depth_eps, float min_cos, int sharpen,
+                    float* acc, int32_t* n_views, void* stream) {
+    if (nv < 0 || nf < 0 || S < 0 || n_frames < 0 || H <= 0 || W <= 0 || sharpen < 0 || sharpen > 4) return DH_ERR_BAD_ARG;
+    if (depth_eps != depth_eps || depth_eps < 0.f || min_cos != min_cos) return DH_ERR_BAD_ARG;      // NaN, negative
+    if (nf >= ((int64_t)1 << 31) || S > (1 << 15)) return DH_ERR_UNSUPPORTED;                      // owner is int32; grid (S/16, S/16)
+    if (H > (1 << 24) || W > (1 << 24) || n_frames >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;
+    if (nf == 0 || S == 0 || n_frames == 0) return DH_OK;
+    if (!verts || !normals || !faces || !uv || !owner || !rgb || !usable || !zbuf || !R || !T || !K || !acc || !n_views ||
+        misaligned16(acc))
+        return DH_ERR_BAD_ARG;
+    return launch_texture_bake(verts, normals, nv, faces, nf, uv, owner, S, rgb, usable, zbuf, R, T, K, n_frames, H, W, depth_eps,
+                               min_cos, sharpen, acc, n_views, static_cast<hipStream_t>(stream));
+}
+
+int dh_mesh_shade_tex(const float* verts, const float* normals, int64_t nv, const int64_t* faces, int64_t nf, const float* uv,
+                      const uint8_t* tex, int Sh, int Sw, const uint64_t* zbuf, const float* R, const float* T, const float* K,
+                      int64_t n_frames, int H, int W, const uint8_t* rgb, const uint8_t* usable, float alpha, int lit, uint8_t* out,
+                      int64_t* sums, void* stream) {
+    if (nv < 0 || nf < 0 || n_frames < 0 || H <= 0 || W <= 0 || (lit != 0 && lit != 1)) return DH_ERR_BAD_ARG;
+    if (alpha != alpha || alpha < 0.f || alpha > 1.f || (usable == nullptr) != (sums == nullptr) || (sums && !rgb)) return DH_ERR_BAD_ARG;
+    if (nf > 0 && (Sh <= 0 || Sw <= 0)) return DH_ERR_BAD_ARG;
+    if (nf >= ((int64_t)1 << 32) || n_frames >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;   // the z-buffer's limits
+    if (H > (1 << 24) || W > (1 << 24) || Sh > (1 << 24) || Sw > (1 << 24)) return DH_ERR_UNSUPPORTED;
+    if (n_frames > (((int64_t)1 << 31) - 1) / shade_tex_blocks_per_frame(H, W)) return DH_ERR_UNSUPPORTED;   // one 1-D grid
+    if (n_frames == 0) return DH_OK;
+    if (!zbuf || !R || !T || !K || !out || (nf > 0 && (!verts || !normals || !faces || !uv || !tex))) return DH_ERR_BAD_ARG;
+    const int64_t bytes = n_frames * H * W * 3;
+    if (rgb && rgb < out + bytes && out < rgb + bytes) return DH_ERR_BAD_ARG;                     // out must not overlap rgb
+    return launch_mesh_shade_tex(verts, normals, nv, faces, nf, uv, tex, Sh, Sw, zbuf, R, T, K, n_frames, H, W, rgb, usable, alpha, lit,
+                                 out, sums, static_cast<hipStream_t>(stream));
+}
+
 // shared argument rules of the three dh_mc_* entry points: 2 <= N <= 2^20 grid points per axis, 1 <= B <= 16 cells per block edge,
 // fewer than 2^31 blocks per call (one workgroup each)
 static int mc_args(int64_t nb, int N, int B) {

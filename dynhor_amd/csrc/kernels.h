@@ -196,6 +196,17 @@ int launch_mesh_bake_colors(const float* verts, const float* normals, int64_t nv
 int launch_mesh_shade(const float* verts, const float* normals, const uint8_t* colors, int64_t nv, const int64_t* faces, int64_t nf,
                       const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
                       const uint8_t* rgb, const int8_t* label, float alpha, uint8_t* out, int64_t* counts, hipStream_t st);
+// texture atlas (mesh_texture.hip): per-texel colour gathered over the frames; the z-buffer's faces drawn with the texture, squared
+// error against the frames (shade_tex_blocks_per_frame: the workgroups one frame takes, for the grid limit)
+int launch_texture_bake(const float* verts, const float* normals, int64_t nv, const int64_t* faces, int64_t nf, const float* uv,
+                        const int32_t* owner, int S, const uint8_t* rgb, const uint8_t* usable, const uint64_t* zbuf, const float* R,
+                        const float* T, const float* K, int64_t n_frames, int H, int W, float depth_eps, float min_cos, int sharpen,
+                        float* acc, int32_t* n_views, hipStream_t st);
+int64_t shade_tex_blocks_per_frame(int H, int W);
+int launch_mesh_shade_tex(const float* verts, const float* normals, int64_t nv, const int64_t* faces, int64_t nf, const float* uv,
+                          const uint8_t* tex, int Sh, int Sw, const uint64_t* zbuf, const float* R, const float* T, const float* K,
+                          int64_t n_frames, int H, int W, const uint8_t* rgb, const uint8_t* usable, float alpha, int lit, uint8_t* out,
+                          int64_t* sums, hipStream_t st);
 
 // silhouette pose refinement (sil.hip): windowed exact distance transform of a label value, nearest face per pixel within rmax_px
 // (ws = sil_nearest_workspace bytes), loss / pose-gradient sums per frame (sil_loss_sums() doubles, ws = sil_loss_grad_workspace bytes)

@@ -8,6 +8,7 @@
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode validate_mesh --is_continue --mesh_color views+network
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode validate_mesh --is_continue --mesh_extract sparse --mesh_resolution 1024
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode validate_mesh --is_continue --mesh_resolution 512 --mesh_simplify faces:12000
+    python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode validate_mesh --is_continue --mesh_resolution 512 --mesh_simplify faces:5000 --mesh_texture views
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode visualize_mesh --is_continue --turntable 36   # overlays, IoU
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode refine_poses --is_continue --pose_frames worst:5   # silhouette fit
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode export_poses --is_continue    # obj_infos/<stem>.npz of the poses
@@ -58,9 +59,17 @@ def main():
                     help="validate_mesh / evaluate_mesh / visualize_mesh / refine_poses: none | cells:N | faces:T -- simplify the "
                          "(cleaned) mesh by quadric vertex clustering on N cells along its longest axis, or to at most T faces; "
                          "validate_mesh also writes <iter>_simple.ply (default: the config's mesh_simplify.mode, else none)")
+    ap.add_argument("--mesh_texture", type=str, default=None, choices=["none", "views", "views+network"],
+                    help="validate_mesh: bake a texture atlas for the (cleaned, simplified) mesh from the frames and also write "
+                         "<iter>_textured.obj, .obj.mtl, _texture_kd.png and <iter>_texture.json (default: the config's "
+                         "mesh_texture.mode, else none)")
+    ap.add_argument("--texture_size", type=int, default=None,
+                    help="validate_mesh: texels per side of the atlas; two faces share a square cell of at least 8 texels, so size S "
+                         "holds 2 (S // 8)^2 faces (default: the config's mesh_texture.size, else 1024)")
     # visualize_mesh only (defaults: the config's mesh_vis: block, else the reconstruction at --mesh_resolution, no turntable)
     ap.add_argument("--vis_mesh", type=str, default=None,
-                    help="visualize_mesh: draw this mesh (.ply / .obj) instead of the reconstruction; refine_poses: fit the poses to it")
+                    help="visualize_mesh: draw this mesh (.ply / .obj; an .obj with a texture is drawn with it) instead of the "
+                         "reconstruction; refine_poses: fit the poses to it")
     ap.add_argument("--vis_normalize", type=str, default=None, choices=["none", "reference"],
                     help="visualize_mesh: 'reference' = bring --vis_mesh into the canonical frame (mean 0, max vertex norm 0.5)")
     ap.add_argument("--turntable", type=int, default=None, help="visualize_mesh: frames of render_res/<iter>/turntable.gif (0: none)")
@@ -130,7 +139,8 @@ def main():
     else:
         res = 64 if args.mesh_resolution is None else args.mesh_resolution
         print("surface crossings", runner.validate_mesh(resolution=res, clean=args.mesh_clean, color=args.mesh_color,
-                                                        extract=args.mesh_extract, simplify=args.mesh_simplify)[1])
+                                                        extract=args.mesh_extract, simplify=args.mesh_simplify,
+                                                        texture=args.mesh_texture, texture_size=args.texture_size)[1])
         xs = runner.last_extract_stats
         if xs is not None and runner.rank == 0:
             print(f"mesh_extract sparse: {xs['active_blocks']} of {xs['blocks']} blocks of {xs['block']}^3 cells active at lipschitz "
@@ -150,6 +160,11 @@ def main():
         if cs is not None and runner.rank == 0:
             print(f"mesh_color {cs['mode']}: {cs['verts_in']} vertices, {cs['unseen_verts']} seen by no view, "
                   f"{cs['mean_views']:.2f} views per seen vertex", flush=True)
+        ts = runner.last_texture_stats
+        if ts is not None and runner.rank == 0:
+            print(f"mesh_texture {ts['mode']}: {ts['faces']} faces on a {ts['size']} x {ts['size']} atlas (cells of {ts['cell']} texels, "
+                  f"{100 * ts['owned_frac']:.1f} % owned), {ts['unseen_texels']} owned texels seen by no view, {ts['mean_views']:.2f} "
+                  f"views per seen texel, re-render PSNR {ts['psnr'] if ts['psnr'] is None else round(ts['psnr'], 2)} dB", flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

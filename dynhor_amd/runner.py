@@ -66,6 +66,10 @@ MESH_CLEAN_DEFAULTS = {"mode": "none", "dilate_px": 2, "min_bg_votes": 1, "min_a
 # the optional mesh_color: block of the YAML (validate_mesh; dynhor_amd/mesh_color.py)
 MESH_COLOR_DEFAULTS = {"mode": "none", "erode_px": 1, "min_cos": 0.1, "depth_eps": 0.01}
 
+# the optional mesh_texture: block of the YAML (validate_mesh; dynhor_amd/mesh_texture.py): mode none | views | views+network, size = the
+# atlas edge in texels; erode_px / min_cos / depth_eps as in mesh_color; sharpen: the weight is cos^(2^sharpen); image: png | jpg
+MESH_TEXTURE_DEFAULTS = {"mode": "none", "size": 1024, "erode_px": 1, "min_cos": 0.1, "depth_eps": 0.01, "sharpen": 2, "image": "png"}
+
 # the optional mesh_extract: block of the YAML (validate_mesh / evaluate_mesh / visualize_mesh; dynhor_amd/mesh_extract.py): mode "dense"
 # queries the whole grid; "sparse" only the blocks of `block`^3 cells whose centre value lies within lipschitz x the block radius of the
 # threshold (the same mesh, no resolution limit).  lipschitz: mesh_extract.DEFAULT_LIPSCHITZ says where the number comes from
@@ -176,6 +180,8 @@ class Runner:
         self.last_clean_stats = None     # validate_mesh / evaluate_mesh with cleaning: mesh_clean.clean_mesh's counts
         self.last_mesh_colors = None     # validate_mesh with colouring: mesh_color.color_mesh's u8 [V,3] colours and its stats
         self.last_color_stats = None
+        self.last_texture = None         # validate_mesh with a texture: (tex u8 [S,S,3], uv [M,3,2], owner [S,S]) of mesh_texture.bake_texture
+        self.last_texture_stats = None   # ... and its stats with the re-render PSNR (what <iter>_texture.json holds)
         self.last_simplify_stats = None  # validate_mesh / evaluate_mesh / _select_mesh with simplification: mesh_simplify's counts
         self.last_extract_stats = None   # validate_mesh / evaluate_mesh / visualize_mesh with sparse extraction: its counts
         self.last_vis_dir = None         # visualize_mesh: the render_res/<iter> directory it wrote
@@ -444,7 +450,7 @@ class Runner:
 
     @torch.no_grad()
     def validate_mesh(self, resolution=64, threshold=0.0, world_space=False, save=True, clean=None, color=None, extract=None,
-                      simplify=None):
+                      simplify=None, texture=None, texture_size=None):
         """Upstream Runner.validate_mesh / NeuSRenderer.extract_geometry: -sdf on a regular grid over
         the object bounding box (HIP no-grad SDF kernel, 64^3-point chunks), iso-surface by marching cubes (model.mesh_method: 'cubes' | 'tetrahedra')
         (dynhor_amd/mesh.py; mcubes is not available), written as meshes/<iter>.ply.  Returns (vertices, triangles).
@@ -459,7 +465,13 @@ class Runner:
         from far fewer SDF queries and leaves its counts in self.last_extract_stats.
         simplify: none | cells:N | faces:T (None: the config's mesh_simplify.mode, default "none"; mesh_simplify.simplify_mesh).  With a
         mode other than "none" the (cleaned) mesh is simplified before it is coloured, written as <iter>_simple.ply and returned (its
-        counts in self.last_simplify_stats); <iter>.ply and <iter>_clean.ply are unchanged and <iter>_color.ply is the simplified mesh."""
+        counts in self.last_simplify_stats); <iter>.ply and <iter>_clean.ply are unchanged and <iter>_color.ply is the simplified mesh.
+        texture: none | views | views+network (None: the config's mesh_texture.mode, default "none"; mesh_texture.bake_texture), on an
+        atlas of texture_size texels per side (None: the config's mesh_texture.size, default 1024).  With a mode other than "none" the
+        mesh that would be coloured (after clean and simplify) gets a texture atlas baked from the frames, written as
+        <iter>_textured.obj + <iter>_textured.obj.mtl + <iter>_textured_texture_kd.png, and <iter>_texture.json holds the bake's stats
+        and the re-render PSNR per frame (mesh_texture.texture_psnr); texture, coordinates and stats stay in self.last_texture /
+        self.last_texture_stats.  Every other file is unchanged."""
         from .mesh import write_ply
         bmin, bmax = self.dataset.object_bbox_min, self.dataset.object_bbox_max
         ec = self._extract_conf(extract)
@@ -492,7 +504,46 @@ class Runner:
             if save and self.rank == 0:
                 os.makedirs(d, exist_ok=True)
                 write_ply(os.path.join(d, "{:0>8d}_color.ply".format(self.iter_step)), verts, faces, colors=self.last_mesh_colors)
+        tc = self._texture_conf(texture, texture_size)
+        self.last_texture = self.last_texture_stats = None
+        if tc["mode"] != "none":
+            from .mesh_texture import bake_texture, texture_psnr, write_textured_obj
+            tex, uv, owner, st = bake_texture(verts, faces, self.dataset, size=int(tc["size"]), mode=tc["mode"], renderer=self.renderer,
+                                              erode_px=int(tc["erode_px"]), min_cos=float(tc["min_cos"]),
+                                              depth_eps=float(tc["depth_eps"]), sharpen=int(tc["sharpen"]))
+            ps = texture_psnr(verts, faces, self.dataset, uv, tex, erode_px=int(tc["erode_px"]))
+            ds = self.dataset
+            stems = list(ds.stems) if ds.stems is not None else ["{:04d}".format(i) for i in range(ds.n_images)]
+            fin = lambda x: x if x is None or math.isfinite(x) else None           # an exact match has no finite PSNR
+            st = dict(st, iter=self.iter_step, verts=int(verts.shape[0]), psnr=fin(ps["pooled"]), psnr_pixels=ps["count"],
+                      frames=[{"stem": s_, "psnr": fin(p_)} for s_, p_ in zip(stems, ps["frames"])])
+            self.last_texture, self.last_texture_stats = (tex, uv, owner), st
+            if save and self.rank == 0:
+                os.makedirs(d, exist_ok=True)
+                write_textured_obj(os.path.join(d, "{:0>8d}_textured.obj".format(self.iter_step)), verts, faces, uv, tex,
+                                   image=tc["image"])
+                with open(os.path.join(d, "{:0>8d}_texture.json".format(self.iter_step)), "w") as f:
+                    json.dump(st, f, indent=1)
         return verts, faces
+
+    def _texture_conf(self, mode=None, size=None):
+        """The YAML's optional mesh_texture: block over MESH_TEXTURE_DEFAULTS; `mode` / `size` (when not None) override its mode / size."""
+        from .mesh_texture import IMAGES, MODES
+        c = dict(MESH_TEXTURE_DEFAULTS)
+        c.update(self.conf.get("mesh_texture") or {})
+        if mode is not None:
+            c["mode"] = mode
+        if size is not None:
+            c["size"] = size
+        if c["mode"] not in MODES:
+            raise ValueError(f"mesh_texture mode must be one of {MODES}, got {c['mode']!r}")
+        if isinstance(c["size"], bool) or not isinstance(c["size"], int) or not 8 <= c["size"] <= 32768:
+            raise ValueError(f"mesh_texture size must be an integer in [8, 32768], got {c['size']!r}")
+        if isinstance(c["sharpen"], bool) or not isinstance(c["sharpen"], int) or not 0 <= c["sharpen"] <= 4:
+            raise ValueError(f"mesh_texture sharpen must be an integer in [0, 4], got {c['sharpen']!r}")
+        if c["image"] not in IMAGES:
+            raise ValueError(f"mesh_texture image must be one of {IMAGES}, got {c['image']!r}")
+        return c
 
     def _color_conf(self, mode=None):
         """The YAML's optional mesh_color: block over MESH_COLOR_DEFAULTS; `mode` (when not None) overrides its mode."""
@@ -614,7 +665,8 @@ class Runner:
         else:
             raise ValueError("evaluate_mesh: no ground truth -- pass gt_mesh (or set eval.gt_mesh in the config); only a synthetic "
                              "dataset has one built in")
-        verts, faces = self.validate_mesh(resolution=resolution, save=False, clean="none", extract=extract, simplify="none")
+        verts, faces = self.validate_mesh(resolution=resolution, save=False, clean="none", extract=extract, simplify="none",
+                                          texture="none")
         mode = self._clean_conf(clean)["mode"]
         if mode != "none":
             verts, faces = self._clean_mesh(verts, faces, clean)
@@ -664,7 +716,7 @@ class Runner:
             raise ValueError(f"{fn}: normalize must be 'none' or 'reference', got {normalize!r}")
         if mesh is None:
             verts, faces = self.validate_mesh(resolution=resolution, save=False, clean="none", color="none", extract=extract,
-                                              simplify="none")
+                                              simplify="none", texture="none")
             name = f"reconstruction@{resolution}"
         else:
             verts, faces = metrics.load_mesh(str(mesh))
@@ -687,7 +739,9 @@ class Runner:
         extracts it at `resolution` (no .ply written), or the .ply / .obj file `mesh` (metrics.load_mesh), taken as in the canonical
         frame (normalize "none") or normalised as the reference normalises its prior (normalize "reference").  clean / color: the
         mesh_clean / mesh_color modes of validate_mesh (None: the config's blocks), applied to whichever mesh is drawn; with a colour
-        mode the shading uses the vertex colours.  extract: validate_mesh's extraction mode for the reconstruction.  simplify:
+        mode the shading uses the vertex colours.  A textured .obj (`vt` lines and a `map_Kd` image, mesh_texture.load_textured_obj) that
+        is neither cleaned, simplified nor coloured is drawn with its texture, lit (silhouette.json then carries `textured`: true); a
+        mesh without a texture is drawn exactly as before.  extract: validate_mesh's extraction mode for the reconstruction.  simplify:
         validate_mesh's simplification mode, applied after cleaning (silhouette.json then carries `simplify`).  Arguments left at
         None take the YAML's optional mesh_vis: block over MESH_VIS_DEFAULTS.  Rank 0 writes render_res/<iter:08d>/<stem>.jpg for every frame (quality 95), silhouette.json (the summary
         plus iter, mesh, clean, color, alpha), turntable.gif when turntable > 0 (orbit_cameras, 100 ms per frame, looping), and logs
@@ -710,6 +764,12 @@ class Runner:
             colors, self.last_color_stats = color_mesh(verts, faces, cc["mode"], dataset=self.dataset, renderer=self.renderer,
                                                        erode_px=int(cc["erode_px"]), min_cos=float(cc["min_cos"]),
                                                        depth_eps=float(cc["depth_eps"]))
+        textured = None                                          # (uv, tex) of a mesh file that brings its own texture
+        if mesh is not None and str(mesh).lower().endswith(".obj") and cmode == "none" and smode == "none" and cc["mode"] == "none":
+            from .mesh_texture import load_textured_obj, overlay_frames_textured, turntable_textured
+            _, tfaces, tuv, ttex = load_textured_obj(str(mesh))
+            if tuv is not None and torch.equal(tfaces, faces.cpu()):
+                textured = (tuv.to(self.device).contiguous(), ttex.to(self.device).contiguous())
         ds = self.dataset
         stems = list(ds.stems) if ds.stems is not None else ["{:04d}".format(i) for i in range(ds.n_images)]
         d = os.path.join(self.base_exp_dir, "render_res", "{:0>8d}".format(self.iter_step))
@@ -727,14 +787,22 @@ class Runner:
                 host = out.cpu().numpy()
                 pending.extend(pool.submit(write, os.path.join(d, stems[f0 + k] + ".jpg"), host[k]) for k in range(host.shape[0]))
         try:
-            counts = overlay_frames(verts, faces, ds, colors=colors, alpha=alpha, sink=sink)
+            if textured is not None:
+                counts = overlay_frames_textured(verts, faces, ds, textured[0], textured[1], alpha=alpha, sink=sink)
+            else:
+                counts = overlay_frames(verts, faces, ds, colors=colors, alpha=alpha, sink=sink)
             res = silhouette_summary(counts.cpu(), stems)
             res.update(iter=self.iter_step, mesh=name, clean=cmode, color=cc["mode"], alpha=alpha)
+            if textured is not None:
+                res.update(textured=True)
             if smode != "none":
                 res.update(simplify=smode, faces=int(faces.shape[0]))
             if save and n_turn > 0:
                 Ro, To = orbit_cameras(ds.R, ds.T, n_turn)
-                imgs = render_turntable(verts, faces, ds.K, ds.H, ds.W, Ro, To, colors=colors).cpu().numpy()
+                if textured is not None:
+                    imgs = turntable_textured(verts, faces, ds.K, ds.H, ds.W, Ro, To, textured[0], textured[1]).cpu().numpy()
+                else:
+                    imgs = render_turntable(verts, faces, ds.K, ds.H, ds.W, Ro, To, colors=colors).cpu().numpy()
                 frames = [Image.fromarray(im) for im in imgs]
                 frames[0].save(os.path.join(d, "turntable.gif"), save_all=True, append_images=frames[1:], duration=100, loop=0)
         finally:

@@ -501,6 +501,42 @@ int dh_mesh_shade(const float* verts, const float* normals, const uint8_t* color
                   const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
                   const uint8_t* rgb, const int8_t* label, float alpha, uint8_t* out, int64_t* counts, void* stream);
 
+/* ---- texture atlas (dynhor_amd/mesh_texture.py: one UV triangle per face, baked from the frames; the mesh drawn with its texture) ----
+ * uv f32 [nf,3,2]: the texture coordinates of every face corner in continuous texel units (texel (i, j), i the column, has its
+ * centre at (i + 0.5, j + 0.5)); projection, pixel centres and the edge function are dh_mesh_raster_depth's.
+ *
+ * dh_texture_bake: one lane per texel of the S x S atlas; owner int32 [S,S] names the face a texel belongs to (< 0: none).  A texel
+ * (x, y) is worked on when o = owner[y,x] lies in [0, nf), the vertex indices of faces[o] lie in [0, nv) and area = edge(uv0, uv1, uv2)
+ * is not 0; every other texel is left untouched.  b_i = max(edge_i(x + 0.5, y + 0.5) / area, 0), renormalised to sum 1 (a texel outside
+ * its UV triangle repeats the nearest edge); p = sum_i b_i v_i, n = sum_i b_i normals_i.  For each frame f in ascending order the frame
+ * contributes when z > 1e-3, 0 <= u <= W - 1 and 0 <= w <= H - 1, usable u8 [n_frames,H,W] is set at the nearest pixel (floor(u + 0.5),
+ * floor(w + 0.5)), zbuf (dh_mesh_raster_depth for the same mesh and cameras) is not empty there and z <= depth(zbuf) + depth_eps, and
+ * c = <n, normalize(C_f - p)> / |n| >= min_cos.  Its weight is c squared `sharpen` times (0: c, the vertex rule; 2: c^4); its colour the
+ * bilinear fetch of rgb / 255 at (u, w).  A contributing frame ADDS acc[y,x] += (weight colour, weight) (acc f32 [S,S,4], 16-byte
+ * aligned) and n_views[y,x] += 1 (int32 [S,S]): the caller zeroes both once and issues frame chunks in order on one stream, so every
+ * texel's sum is a fixed sequential fp32 sum (colour terms as fma(weight, colour, acc)), bitwise reproducible whatever the chunking.
+ * nf == 0, S == 0 or n_frames == 0: no-op.  DH_ERR_BAD_ARG: null pointer, misaligned acc, negative count, H or W < 1, depth_eps
+ * negative or NaN, min_cos NaN, sharpen outside [0, 4].  DH_ERR_UNSUPPORTED: nf >= 2^31, S > 2^15, n_frames >= 2^31, H or W > 2^24.
+ *
+ * dh_mesh_shade_tex: dh_mesh_shade with a texture in place of vertex colours.  Coverage, the weights l_j and the shading term s are
+ * dh_mesh_shade's; (s_t, t_t) = sum_j l_j uv[face][j]; base = the bilinear fetch of tex u8 [Sh,Sw,3] / 255: taps at floor(s_t - 0.5)
+ * and + 1 (likewise t_t), indices clamped to the image, weights from the fractional parts.  lit 0: c = base; lit 1: c = min(1, base
+ * (0.3 + 0.7 s)).  o = alpha c + (1 - alpha) bg as in dh_mesh_shade; an uncovered pixel copies rgb (255 without rgb).  usable u8
+ * [n_frames,H,W] and sums int64 [n_frames,2] go together and need rgb: over the covered pixels with usable set the call ADDS to
+ * sums[f] (sum over the three channels of (out - rgb)^2, 1); the caller zeroes sums.  Integer atomics after a per-wave reduction:
+ * output and sums are bitwise reproducible.  out must not overlap rgb.  With nf == 0 every pixel is uncovered and verts, normals,
+ * faces, uv, tex may be null; n_frames == 0: no-op.  DH_ERR_BAD_ARG: null required pointer, negative count, H or W < 1, Sh or Sw < 1
+ * with nf > 0, alpha NaN or outside [0, 1], lit not 0 or 1, exactly one of usable / sums null, sums without rgb, out overlapping rgb.
+ * DH_ERR_UNSUPPORTED: nf >= 2^32, n_frames >= 2^31, H, W, Sh or Sw > 2^24, n_frames ceil(H W / 1024) >= 2^31. */
+int dh_texture_bake(const float* verts, const float* normals, int64_t nv, const int64_t* faces, int64_t nf, const float* uv,
+                    const int32_t* owner, int S, const uint8_t* rgb, const uint8_t* usable, const uint64_t* zbuf, const float* R,
+                    const float* T, const float* K, int64_t n_frames, int H, int W, float depth_eps, float min_cos, int sharpen,
+                    float* acc, int32_t* n_views, void* stream);
+int dh_mesh_shade_tex(const float* verts, const float* normals, int64_t nv, const int64_t* faces, int64_t nf, const float* uv,
+                      const uint8_t* tex, int Sh, int Sw, const uint64_t* zbuf, const float* R, const float* T, const float* K,
+                      int64_t n_frames, int H, int W, const uint8_t* rgb, const uint8_t* usable, float alpha, int lit, uint8_t* out,
+                      int64_t* sums, void* stream);
+
 /* ---- silhouette pose refinement (dynhor_amd/pose_sil.py: per-frame poses fitted to the object masks through a soft silhouette) ----
  * Projection, pixel centres, edge function, coverage and the rule by which a face is skipped are dh_mesh_raster_depth's (the same
  * fp32 code), so a pixel is "covered" here exactly where that z-buffer is not empty.
