@@ -108,6 +108,9 @@ SIGNATURES = {
     "dh_sil_loss_sums": (_i32, []),
     "dh_sil_loss_grad_workspace": (_i64, [_i64, _i32, _i32]),
     "dh_sil_loss_grad": (_i32, [_vp, _vp, _i64, _vp, _i64] + [_vp] * 6 + [_i64, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp]),
+    "dh_label_boxes": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp]),
+    "dh_sil_crop_pack": (_i32, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "dh_sil_bank_score": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp]),
     "dh_mc_block_points": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp]),
     "dh_mc_count": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dh_mc_emit": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _i64, _vp, _vp, _vp]),

@@ -816,6 +816,36 @@ int dh_sil_loss_grad(const uint64_t* near, const float* verts, int64_t nv, const
                                 ws, static_cast<hipStream_t>(stream));
 }
 
+int dh_label_boxes(const int8_t* label, int64_t n, int H, int W, int32_t* boxes, void* stream) {
+    const int rc = sil_args(n, H, W);
+    if (rc != DH_OK) return rc;
+    if (label_boxes_chunks(H, W) >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;                 // grid (chunks, images)
+    if (n == 0) return DH_OK;
+    if (!label || !boxes) return DH_ERR_BAD_ARG;
+    return launch_label_boxes(label, n, H, W, boxes, static_cast<hipStream_t>(stream));
+}
+
+int dh_sil_crop_pack(const int8_t* label, int64_t n, int H, int W, const float* sq, int S, uint64_t* obj, uint64_t* keep, void* stream) {
+    const int rc = sil_args(n, H, W);
+    if (rc != DH_OK) return rc;
+    if (S < 8 || S > 128 || (S & 7) != 0) return DH_ERR_BAD_ARG;                                     // S^2 a multiple of 64
+    if (n > (((int64_t)1 << 32) - 4) / (S * S / 64)) return DH_ERR_UNSUPPORTED;                       // one 1-D grid, four words per workgroup
+    if (n == 0) return DH_OK;
+    if (!label || !sq || !obj || !keep) return DH_ERR_BAD_ARG;
+    return launch_sil_crop_pack(label, n, H, W, sq, S, obj, keep, static_cast<hipStream_t>(stream));
+}
+
+int dh_sil_bank_score(const uint64_t* frame_obj, const uint64_t* frame_keep, int64_t n_frames, const uint64_t* bank_obj, int64_t n_views,
+                      int n_words, int32_t* out, void* stream) {
+    if (n_frames < 0 || n_views < 0 || n_words < 1) return DH_ERR_BAD_ARG;
+    if (n_words > (1 << 20)) return DH_ERR_UNSUPPORTED;                                             // 64 n_words fits an int32 count
+    if (sil_bank_score_frame_tiles(n_frames) > 65535 || sil_bank_score_view_tiles(n_views) >= ((int64_t)1 << 31))
+        return DH_ERR_UNSUPPORTED;                                                                 // grid (view tiles, frame tiles)
+    if (n_frames == 0 || n_views == 0) return DH_OK;
+    if (!frame_obj || !frame_keep || !bank_obj || !out || (reinterpret_cast<uintptr_t>(out) & 7u) != 0) return DH_ERR_BAD_ARG;
+    return launch_sil_bank_score(frame_obj, frame_keep, n_frames, bank_obj, n_views, n_words, out, static_cast<hipStream_t>(stream));
+}
+
 // shared argument rules of the simplification entry points: a grid as dh_simplify_grid returns it
 static int simplify_grid_args(const float* lo, float h, const int32_t* dims) {
     if (!lo || !dims || !(h >= 0.f) || !(h <= 3.0e38f)) return DH_ERR_BAD_ARG;

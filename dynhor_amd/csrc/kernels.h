@@ -220,6 +220,18 @@ int launch_sil_loss_grad(const uint64_t* near, const float* verts, int64_t nv, c
                          const float* T, const float* K, const float* d2_obj, const float* d2_hand, const int8_t* label, int64_t n_frames,
                          int H, int W, float sigma, float cut, float edge_offset, double* out, void* ws, hipStream_t st);
 
+// pose initialisation by silhouette retrieval (pose_init.hip): tight box of label == 1 per image, the label resampled on an S x S
+// square and packed one bit per sample (obj / keep planes), intersection / union counts of every frame against every bank view
+// (label_boxes_chunks / sil_bank_score_*_tiles: the grid sizes, for the limits)
+int64_t label_boxes_chunks(int H, int W);
+int launch_label_boxes(const int8_t* label, int64_t n, int H, int W, int32_t* boxes, hipStream_t st);
+int launch_sil_crop_pack(const int8_t* label, int64_t n, int H, int W, const float* sq, int S, uint64_t* obj, uint64_t* keep,
+                         hipStream_t st);
+int64_t sil_bank_score_frame_tiles(int64_t F);
+int64_t sil_bank_score_view_tiles(int64_t V);
+int launch_sil_bank_score(const uint64_t* frame_obj, const uint64_t* frame_keep, int64_t F, const uint64_t* bank_obj, int64_t V, int Wd,
+                          int32_t* out, hipStream_t st);
+
 // block-sparse marching cubes (mesh_extract.hip): sample points of the listed blocks, triangles and cut faces per block, triangle emit
 int launch_mc_block_points(const float* ax, const float* ay, const float* az, int N, const int32_t* blocks, int64_t nb, int B, float* pts,
                            hipStream_t st);

@@ -12,6 +12,7 @@
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode visualize_mesh --is_continue --turntable 36   # overlays, IoU
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode refine_poses --is_continue --pose_frames worst:5   # silhouette fit
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode export_poses --is_continue    # obj_infos/<stem>.npz of the poses
+    python -m dynhor_amd.run --config_path X.yaml --mode init_poses --vis_mesh template.obj --vis_normalize reference   # poses from masks
 
 With --gpus N > 1 this process starts N ranks (one per GPU) through dynhor_amd.launch before it touches the GPU and exits
 with their code; under an external `torch.distributed.run` (WORLD_SIZE set) it is one of the ranks.
@@ -26,7 +27,7 @@ def main():
     ap.add_argument("--config_path", type=str, required=True)
     ap.add_argument("--mode", type=str, default="train",
                     choices=["train", "validate_image", "validate_mesh", "evaluate_mesh", "visualize_mesh", "refine_poses",
-                             "export_poses"])
+                             "export_poses", "init_poses"])
     ap.add_argument("--is_continue", action="store_true")
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks on this node (one process per GPU)")
@@ -69,7 +70,8 @@ def main():
     # visualize_mesh only (defaults: the config's mesh_vis: block, else the reconstruction at --mesh_resolution, no turntable)
     ap.add_argument("--vis_mesh", type=str, default=None,
                     help="visualize_mesh: draw this mesh (.ply / .obj; an .obj with a texture is drawn with it) instead of the "
-                         "reconstruction; refine_poses: fit the poses to it")
+                         "reconstruction; refine_poses: fit the poses to it; init_poses: the template (default: the config's "
+                         "data_info.obj_path with normalize_mesh)")
     ap.add_argument("--vis_normalize", type=str, default=None, choices=["none", "reference"],
                     help="visualize_mesh: 'reference' = bring --vis_mesh into the canonical frame (mean 0, max vertex norm 0.5)")
     ap.add_argument("--turntable", type=int, default=None, help="visualize_mesh: frames of render_res/<iter>/turntable.gif (0: none)")
@@ -131,6 +133,12 @@ def main():
         if runner.rank == 0:
             import json
             print(json.dumps({k: v for k, v in res.items() if k not in ("stems", "curve")}), flush=True)
+    elif args.mode == "init_poses":
+        res = runner.init_poses(mesh=args.vis_mesh, normalize=args.vis_normalize)
+        runner.close()
+        if runner.rank == 0:
+            import json
+            print(json.dumps({k: v for k, v in res.items() if k not in ("frames", "refine")}), flush=True)
     elif args.mode == "export_poses":
         d = runner.export_poses(args.pose_dir)
         if runner.rank == 0:

@@ -583,6 +583,30 @@ int dh_sil_loss_grad(const uint64_t* near, const float* verts, int64_t nv, const
                      const float* T, const float* K, const float* d2_obj, const float* d2_hand, const int8_t* label, int64_t n_frames,
                      int H, int W, float sigma, float cut, float edge_offset, double* out, void* ws, void* stream);
 
+/* ---- pose initialisation by silhouette retrieval (dynhor_amd/pose_init.py: a bank of views of a template, retrieval per frame) ----
+ * Integer kernels without float atomics: every output is bitwise the same from launch to launch and for every split of the images,
+ * frames or views into calls.  Pixel centres are integers, as for dh_mesh_raster_depth.
+ *
+ * dh_label_boxes: label i8 [n,H,W] -> boxes int32 [n,4] = (xmin, ymin, xmax, ymax) over the pixels with label == 1, (W, H, -1, -1) for
+ * an image without one (32-bit integer atomic min / max after a reduction per workgroup).  n == 0: no-op.
+ * DH_ERR_BAD_ARG: null pointer, negative n, H or W < 1.  DH_ERR_UNSUPPORTED: n >= 2^31, H or W > 2^24, H W >= 2^44.
+ *
+ * dh_sil_crop_pack: sq f32 [n,3] = (x0, y0, step) of a square sampling grid per image, S a multiple of 8 in [8, 128].  Sample (r, c),
+ * r the row, reads the pixel px = floorf(fmaf(c + 0.5f, step, x0) + 0.5f), py = floorf(fmaf(r + 0.5f, step, y0) + 0.5f) in fp32; inside
+ * the image obj = (label == 1), keep = (label >= 0), outside both are 0.  Sample s = r S + c is bit (s & 63) of word (s >> 6) of
+ * obj / keep u64 [n, S^2 / 64] (one wave's ballot is one word).  An image whose step is not > 0 (0: the caller's mark of an empty box;
+ * NaN) gets all-zero words.  n == 0: no-op.  DH_ERR_BAD_ARG: null pointer, negative n, H or W < 1, S not a multiple of 8 in [8, 128].
+ * DH_ERR_UNSUPPORTED: n >= 2^31, H or W > 2^24, n S^2 / 64 >= 2^32 - 4.
+ *
+ * dh_sil_bank_score: frame_obj, frame_keep u64 [n_frames,n_words], bank_obj u64 [n_views,n_words] -> out int32 [n_frames,n_views,2]
+ * (8-byte aligned) = (sum over the words of popc(fo & bo & fk), of popc((fo | bo) & fk)): intersection and union of the frame's and
+ * the view's object samples over the frame's keep samples.  n_frames == 0 or n_views == 0: no-op.  DH_ERR_BAD_ARG: null pointer,
+ * misaligned out, negative count, n_words < 1.  DH_ERR_UNSUPPORTED: n_words > 2^20, n_frames > 16 * 65535, n_views >= 2^37. */
+int dh_label_boxes(const int8_t* label, int64_t n, int H, int W, int32_t* boxes, void* stream);
+int dh_sil_crop_pack(const int8_t* label, int64_t n, int H, int W, const float* sq, int S, uint64_t* obj, uint64_t* keep, void* stream);
+int dh_sil_bank_score(const uint64_t* frame_obj, const uint64_t* frame_keep, int64_t n_frames, const uint64_t* bank_obj, int64_t n_views,
+                      int n_words, int32_t* out, void* stream);
+
 /* ---- block-sparse marching cubes (dynhor_amd/mesh_extract.py: the iso-surface from the blocks near it only) ----
  * The grid has N points per axis, cut into nbk = ceil((N - 1) / B) blocks of B cells per axis; block (bx, by, bz) of blocks int32 [nb,3]
  * covers the grid indices [b B, min(b B + B, N - 1)] and carries P^3 samples, P = B + 1, sample (i, j, k) of block n at row n P^3 +
