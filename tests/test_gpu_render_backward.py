@@ -17,11 +17,24 @@ def _loss_inputs(B, dev, seed):
     return rgb, obj, keep, mono, R
 
 
-@pytest.mark.parametrize("B,ns,ni,car,normal_w,bg", [(16, 64, 64, 0.3, 0.05, False), (130, 64, 64, 1.0, 0.0, True),
-                                                     (48, 32, 32, 0.0, 0.05, False)])
-def test_parameter_gradients_match_oracle_autograd(B, ns, ni, car, normal_w, bg):
+def check_parameter_gradients(B, ns, ni, car, normal_w, bg, arithmetic=None, stale_batch=None, up_sample_steps=4):
+    """Loss and every parameter gradient of one render against the oracle's autograd (fp64, and fp32 as the yardstick).
+    arithmetic: the product renderer's (None: the library default).  stale_batch: render and differentiate that many rays first, so
+    that the renderer's reused, uninitialised workspace holds another launch's tiles when the case itself runs."""
     dev = "cuda:0"
-    o_r, p_r = make_pair(seed=21, jitter=0.05, n_samples=ns, n_importance=ni)
+    o_r, p_r = make_pair(seed=21, jitter=0.05, n_samples=ns, n_importance=ni, up_sample_steps=up_sample_steps)
+    if arithmetic is not None:
+        p_r.arithmetic = arithmetic
+    if stale_batch is not None:
+        so, sd, snear, sfar, st_rand = make_rays(stale_batch, seed=900 + stale_batch)
+        out = p_r.render(so, sd, snear, sfar, cos_anneal_ratio=car, t_rand=st_rand)
+        srgb, sobj, skeep, smono, sR = _loss_inputs(stale_batch, dev, seed=stale_batch)
+        O.neus_losses(out, srgb, sobj, skeep, igr_weight=0.1, mask_weight=0.1, normal_weight=normal_w, mono_normal=smono,
+                      R=sR)["loss"].backward()
+        torch.cuda.synchronize()
+        assert p_r._ws.numel() > 0
+        for m in (p_r.sdf_network, p_r.deviation_network, p_r.color_network):
+            m.zero_grad(set_to_none=True)
     o, d, near, far, t_rand = make_rays(B, seed=300 + B)
     z = o_r.sample_z(o, d, near, far, t_rand=t_rand)
     rgb, obj, keep, mono, R = _loss_inputs(B, dev, seed=B)
@@ -74,6 +87,12 @@ def test_parameter_gradients_match_oracle_autograd(B, ns, ni, car, normal_w, bg)
     # flat gradient buffer is what the fused optimiser / all-reduce consume
     flat = p_r.store.grad_flat
     assert flat is not None and flat.numel() == 802491
+
+
+@pytest.mark.parametrize("B,ns,ni,car,normal_w,bg", [(16, 64, 64, 0.3, 0.05, False), (130, 64, 64, 1.0, 0.0, True),
+                                                     (48, 32, 32, 0.0, 0.05, False)])
+def test_parameter_gradients_match_oracle_autograd(B, ns, ni, car, normal_w, bg):
+    check_parameter_gradients(B, ns, ni, car, normal_w, bg)
 
 
 def test_workspace_overwrite_is_detected():
