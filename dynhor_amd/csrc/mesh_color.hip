@@ -10,17 +10,16 @@
 //
 // mesh_bake_kernel: one thread per vertex, looping over the frames in ascending order and adding onto the caller's acc / n_views
 // (read once, written once: a fixed sequential fp32 sum per vertex, no float atomics).  A frame contributes when c_2 > 1e-3, the
-// nearest pixel (floor(u + 0.5), floor(w + 0.5)) lies in the image (range-checked as floats), usable[pixel] != 0, the z-buffer at that
-// pixel is not empty and c_2 <= depth + depth_eps, and cos = <n, d> / |d| >= min_cos for d = C - v, C = -R^T T the camera centre:
-//   C_k = -fma(R_2k, T_2, fma(R_1k, T_1, R_0k * T_0)),   |d| = sqrt(fma(d_z, d_z, fma(d_y, d_y, d_x * d_x)))
-//   cos = fma(n_z, d_z, fma(n_y, d_y, n_x * d_x)) / |d|
+// nearest pixel (floor(u + 0.5), floor(w + 0.5)) lies in the image (range-checked as floats), usable[pixel] != 0, mk_view sees the
+// vertex through the z-buffer's key at that pixel (mesh_shade.h states the depth test and cos = <n, d> / |d|, d = C - v the direction
+// to the camera centre; dh_texture_bake shares it), and cos >= min_cos:
 //   acc.rgb = fma(cos, rgb / 255, acc.rgb),  acc.w += cos,  n_views += 1
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "kernels.h"
 #include "launch.h"
-#include "mesh_raster.h"
+#include "mesh_shade.h"
 
 namespace dh {
 
@@ -70,15 +69,9 @@ __global__ __launch_bounds__(MK_THREADS) void mesh_bake_kernel(const float* __re
         const bool in = (c.c2 > 1e-3f) & (px >= 0.f) & (px < fw) & (py >= 0.f) & (py < fh);
         const int64_t pix = f * HW + (in ? (int64_t)(int)py * W + (int)px : 0);
         const uint8_t us = usable[pix];
-        const uint64_t key = zbuf[pix];
-        const float depth = __uint_as_float((uint32_t)(key >> 32));
-        const float cx = -__builtin_fmaf(Rf[6], Tf[2], __builtin_fmaf(Rf[3], Tf[1], Rf[0] * Tf[0]));
-        const float cy = -__builtin_fmaf(Rf[7], Tf[2], __builtin_fmaf(Rf[4], Tf[1], Rf[1] * Tf[0]));
-        const float cz = -__builtin_fmaf(Rf[8], Tf[2], __builtin_fmaf(Rf[5], Tf[1], Rf[2] * Tf[0]));
-        const float dx = cx - vx, dy = cy - vy, dz = cz - vz;
-        const float len = sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
-        const float cs = __builtin_fmaf(nz, dz, __builtin_fmaf(ny, dy, nx * dx)) / len;
-        if (in & (us != 0) & (key != MK_EMPTY) & (c.c2 <= depth + depth_eps) & (cs >= min_cos)) {
+        const View v = mk_view(zbuf[pix], c.c2, depth_eps, Rf, Tf, vx, vy, vz, nx, ny, nz);
+        const float cs = v.cos;
+        if (in & (us != 0) & v.seen & (cs >= min_cos)) {
             ar = __builtin_fmaf(cs, (float)rgb[pix * 3 + 0] / 255.f, ar);
             ag = __builtin_fmaf(cs, (float)rgb[pix * 3 + 1] / 255.f, ag);
             ab = __builtin_fmaf(cs, (float)rgb[pix * 3 + 2] / 255.f, ab);

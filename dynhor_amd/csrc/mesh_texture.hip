@@ -8,18 +8,16 @@
 //   e0 = edge(uv1, uv2, q), e1 = edge(uv2, uv0, q), e2 = edge(uv0, uv1, q),  b_i = max(e_i / area, 0),  b_i = b_i / ((b0 + b1) + b2)
 //   p = fma(b2, v2, fma(b1, v1, b0 v0)),  n = fma(b2, n2, fma(b1, n1, b0 n0))     (a gutter texel repeats the nearest edge)
 // and for every frame f in ascending order: (c, u, w) = mk_project(p).  The frame contributes when c_2 > 1e-3, 0 <= u <= W - 1 and
-// 0 <= w <= H - 1, usable and the z-buffer at the nearest pixel (floor(u + 0.5), floor(w + 0.5)) are set / not empty,
-// c_2 <= depth + depth_eps, and cosv = (<n, d> / |d|) / |n| >= min_cos, d = C_f - p, C_f = -R_f^T T_f (dot products and lengths as
-// fma chains from the x term up, as in mesh_bake_kernel).  weight = cosv squared `sharpen` times.  The colour is the bilinear fetch
-// at (u, w): x0 = floor(u), x1 = min(x0 + 1, W - 1), fx = u - x0, likewise y;
-//   top = fma(fx, c10 - c00, c00), bot = fma(fx, c11 - c01, c01), col = fma(fy, bot - top, top) / 255      (c..: the bytes as floats)
+// 0 <= w <= H - 1, usable at the nearest pixel (floor(u + 0.5), floor(w + 0.5)) is set, mk_view (mesh_shade.h, shared with
+// mesh_bake_kernel) sees p through the z-buffer's key there, and cosv = mk_view's cos / |n| >= min_cos.  weight = cosv squared
+// `sharpen` times.  The colour is mk_bilinear_u8 at (u, w): x0 = floor(u), x1 = min(x0 + 1, W - 1), fx = u - x0, likewise y;
 //   acc.rgb = fma(weight, col, acc.rgb),  acc.w += weight,  n_views += 1
 // acc / n_views are read once and written once: a fixed sequential fp32 sum per texel, no float atomics.
 //
-// mesh_shade_tex_kernel: one lane per pixel, four pixels per lane 256 apart, every workgroup inside one frame.  Coverage and the
-// weights l_j are dh_mesh_shade's (csrc/mesh_vis.hip states them); (s, t) = fma(l2, uv2, fma(l1, uv1, l0 uv0)); the bilinear fetch
-// of tex u8 [Sh,Sw,3]: i0 = floor(s - 0.5), fx = (s - 0.5) - i0, taps i0 and i0 + 1 clamped to [0, Sw - 1], likewise t, lerped as
-// above; c = lit ? clamp(col (0.3 + 0.7 shade), 0, 1) : col;  out = min(floor(fma(255, fma(alpha, c, (1 - alpha) bg), 0.5)), 255).
+// mesh_shade_tex_kernel: one lane per pixel, four pixels per lane 256 apart, every workgroup inside one frame.  Coverage, the weights
+// l_j, the headlight and the composite are dh_mesh_shade's (mk_key_face, mk_pixel_weights, mk_headlight, mk_composite of mesh_shade.h);
+// (s, t) = fma(l2, uv2, fma(l1, uv1, l0 uv0)); col = mk_bilinear_u8 of tex u8 [Sh,Sw,3]: i0 = floor(s - 0.5), fx = (s - 0.5) - i0, taps
+// i0 and i0 + 1 clamped to [0, Sw - 1], likewise t;  out = mk_composite(col, lit ? shade : 1, alpha, bg).
 // With usable and sums, over the covered pixels with usable set: sums[f] += (sum_channels (out - rgb)^2, 1), reduced over the wave by
 // integer shuffles, over the workgroup through LDS, then one 64-bit integer atomic each: bitwise reproducible.
 #include <hip/hip_runtime.h>
@@ -27,7 +25,7 @@
 #include <stdint.h>
 #include "kernels.h"
 #include "launch.h"
-#include "mesh_raster.h"
+#include "mesh_shade.h"
 
 namespace dh {
 
@@ -35,17 +33,6 @@ namespace {
 constexpr int TX_TILE = 16;                 // texels per workgroup edge of the bake (four 8 x 8 wave tiles)
 constexpr int TS_THREADS = 256;
 constexpr int TS_PER_LANE = 4;              // pixels per lane of the textured shade
-constexpr float TX_INV255 = 1.f / 255.f;
-
-__device__ __forceinline__ float tx_lerp2(float c00, float c10, float c01, float c11, float fx, float fy) {
-    const float top = __builtin_fmaf(fx, c10 - c00, c00);
-    const float bot = __builtin_fmaf(fx, c11 - c01, c01);
-    return __builtin_fmaf(fy, bot - top, top);
-}
-
-__device__ __forceinline__ uint32_t tx_byte(float o) {
-    return (uint32_t)fminf(floorf(__builtin_fmaf(255.f, o, 0.5f)), 255.f);
-}
 }  // namespace
 
 __global__ __launch_bounds__(TX_TILE* TX_TILE) void texture_bake_kernel(
@@ -92,15 +79,9 @@ __global__ __launch_bounds__(TX_TILE* TX_TILE) void texture_bake_kernel(
         // 0 <= u <= W - 1: the nearest pixel and both taps of the fetch lie in the image
         const int64_t pix = f * HW + (int64_t)(int)floorf(c.w + 0.5f) * W + (int)floorf(c.u + 0.5f);
         if (usable[pix] == 0) continue;
-        const uint64_t key = zbuf[pix];
-        const float depth = __uint_as_float((uint32_t)(key >> 32));
-        if (key == MK_EMPTY || !(c.c2 <= depth + depth_eps)) continue;
-        const float cx = -__builtin_fmaf(Rf[6], Tf[2], __builtin_fmaf(Rf[3], Tf[1], Rf[0] * Tf[0]));
-        const float cy = -__builtin_fmaf(Rf[7], Tf[2], __builtin_fmaf(Rf[4], Tf[1], Rf[1] * Tf[0]));
-        const float cz = -__builtin_fmaf(Rf[8], Tf[2], __builtin_fmaf(Rf[5], Tf[1], Rf[2] * Tf[0]));
-        const float dx = cx - p[0], dy = cy - p[1], dz = cz - p[2];
-        const float len = sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
-        const float cs = (__builtin_fmaf(n[2], dz, __builtin_fmaf(n[1], dy, n[0] * dx)) / len) / nlen;
+        const View v = mk_view(zbuf[pix], c.c2, depth_eps, Rf, Tf, p[0], p[1], p[2], n[0], n[1], n[2]);
+        if (!v.seen) continue;
+        const float cs = v.cos / nlen;
         if (!(cs >= min_cos)) continue;
         float wgt = cs;
         for (int k = 0; k < sharpen; ++k) wgt *= wgt;
@@ -108,14 +89,11 @@ __global__ __launch_bounds__(TX_TILE* TX_TILE) void texture_bake_kernel(
         const int x0 = (int)fx0, y0 = (int)fy0;
         const int x1 = x0 + 1 < W ? x0 + 1 : W - 1, y1 = y0 + 1 < H ? y0 + 1 : H - 1;
         const float fx = c.u - fx0, fy = c.w - fy0;
-        const uint8_t* img = rgb + f * HW * 3;
-        const uint8_t* c00 = img + ((int64_t)y0 * W + x0) * 3;
-        const uint8_t* c10 = img + ((int64_t)y0 * W + x1) * 3;
-        const uint8_t* c01 = img + ((int64_t)y1 * W + x0) * 3;
-        const uint8_t* c11 = img + ((int64_t)y1 * W + x1) * 3;
-        a.x = __builtin_fmaf(wgt, tx_lerp2((float)c00[0], (float)c10[0], (float)c01[0], (float)c11[0], fx, fy) * TX_INV255, a.x);
-        a.y = __builtin_fmaf(wgt, tx_lerp2((float)c00[1], (float)c10[1], (float)c01[1], (float)c11[1], fx, fy) * TX_INV255, a.y);
-        a.z = __builtin_fmaf(wgt, tx_lerp2((float)c00[2], (float)c10[2], (float)c01[2], (float)c11[2], fx, fy) * TX_INV255, a.z);
+        float col[3];
+        mk_bilinear_u8(rgb + f * HW * 3, W, x0, x1, y0, y1, fx, fy, col);
+        a.x = __builtin_fmaf(wgt, col[0], a.x);
+        a.y = __builtin_fmaf(wgt, col[1], a.y);
+        a.z = __builtin_fmaf(wgt, col[2], a.z);
         a.w += wgt;
         cnt += 1;
     }
@@ -148,35 +126,14 @@ __global__ __launch_bounds__(TS_THREADS) void mesh_shade_tex_kernel(
             bg[0] = rgb[pidx * 3 + 0]; bg[1] = rgb[pidx * 3 + 1]; bg[2] = rgb[pidx * 3 + 2];
         }
         const uint64_t key = zbuf[pidx];
-        const int64_t fi = (int64_t)(key & 0xffffffffu);
         int64_t ia = 0, ib = 0, ic = 0;
-        const bool cv = key != MK_EMPTY && fi < nf && mk_face_in_range(faces, fi, nv, ia, ib, ic);
+        const bool cv = mk_key_face(key, faces, nf, nv, ia, ib, ic);
         uint32_t o[3] = {bg[0], bg[1], bg[2]};
         if (cv) {
-            const Cam p0 = mk_project(Rf, Tf, k00, k01, k02, k10, k11, k12, verts[ia * 3], verts[ia * 3 + 1], verts[ia * 3 + 2]);
-            const Cam p1 = mk_project(Rf, Tf, k00, k01, k02, k10, k11, k12, verts[ib * 3], verts[ib * 3 + 1], verts[ib * 3 + 2]);
-            const Cam p2 = mk_project(Rf, Tf, k00, k01, k02, k10, k11, k12, verts[ic * 3], verts[ic * 3 + 1], verts[ic * 3 + 2]);
-            const float iz0 = 1.f / p0.c2, iz1 = 1.f / p1.c2, iz2 = 1.f / p2.c2;
-            const float px = (float)xx, py = (float)yy;
-            const float e0 = mk_edge(p1.u, p1.w, p2.u, p2.w, px, py);
-            const float e1 = mk_edge(p2.u, p2.w, p0.u, p0.w, px, py);
-            const float e2 = mk_edge(p0.u, p0.w, p1.u, p1.w, px, py);
-            const float den = __builtin_fmaf(e2, iz2, __builtin_fmaf(e1, iz1, e0 * iz0));
-            const bool ok = (fabsf(den) > 0.f) & (fabsf(den) < 3.0e38f);
-            const float rden = 1.f / den;
-            const float l0 = ok ? (e0 * iz0) * rden : 1.f / 3.f;
-            const float l1 = ok ? (e1 * iz1) * rden : 1.f / 3.f;
-            const float l2 = ok ? (e2 * iz2) * rden : 1.f / 3.f;
-            float shade = 1.f;
-            if (lit) {
-                const float nx = __builtin_fmaf(l2, normals[ic * 3 + 0], __builtin_fmaf(l1, normals[ib * 3 + 0], l0 * normals[ia * 3 + 0]));
-                const float ny = __builtin_fmaf(l2, normals[ic * 3 + 1], __builtin_fmaf(l1, normals[ib * 3 + 1], l0 * normals[ia * 3 + 1]));
-                const float nz = __builtin_fmaf(l2, normals[ic * 3 + 2], __builtin_fmaf(l1, normals[ib * 3 + 2], l0 * normals[ia * 3 + 2]));
-                const float ncz = __builtin_fmaf(Rf[8], nz, __builtin_fmaf(Rf[7], ny, Rf[6] * nx));
-                const float len = sqrtf(__builtin_fmaf(nz, nz, __builtin_fmaf(ny, ny, nx * nx)));
-                shade = __builtin_fmaf(0.7f, len > 0.f ? fabsf(ncz) / len : 0.f, 0.3f);
-            }
-            const float* uf = uv + fi * 6;
+            float l0, l1, l2;
+            mk_pixel_weights(verts, ia, ib, ic, Rf, Tf, k00, k01, k02, k10, k11, k12, xx, yy, l0, l1, l2);
+            const float shade = lit ? mk_headlight(normals, ia, ib, ic, l0, l1, l2, Rf) : 1.f;
+            const float* uf = uv + (int64_t)(key & 0xffffffffu) * 6;
             const float s = __builtin_fmaf(l2, uf[4], __builtin_fmaf(l1, uf[2], l0 * uf[0])) - 0.5f;
             const float tt = __builtin_fmaf(l2, uf[5], __builtin_fmaf(l1, uf[3], l0 * uf[1])) - 0.5f;
             const float si = floorf(s), ti = floorf(tt);
@@ -184,16 +141,10 @@ __global__ __launch_bounds__(TS_THREADS) void mesh_shade_tex_kernel(
             // fmaxf / fminf take the number over a NaN: the four taps always lie in the texture
             const int i0 = (int)fminf(fmaxf(si, 0.f), smax), i1 = (int)fminf(fmaxf(si + 1.f, 0.f), smax);
             const int j0 = (int)fminf(fmaxf(ti, 0.f), tmax), j1 = (int)fminf(fmaxf(ti + 1.f, 0.f), tmax);
-            const uint8_t* c00 = tex + ((int64_t)j0 * Sw + i0) * 3;
-            const uint8_t* c10 = tex + ((int64_t)j0 * Sw + i1) * 3;
-            const uint8_t* c01 = tex + ((int64_t)j1 * Sw + i0) * 3;
-            const uint8_t* c11 = tex + ((int64_t)j1 * Sw + i1) * 3;
+            float col[3];
+            mk_bilinear_u8(tex, Sw, i0, i1, j0, j1, fx, fy, col);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float base_k = tx_lerp2((float)c00[k], (float)c10[k], (float)c01[k], (float)c11[k], fx, fy) * TX_INV255;
-                const float col = fmaxf(fminf(1.f, base_k * shade), 0.f);
-                o[k] = tx_byte(__builtin_fmaf(alpha, col, (1.f - alpha) * ((float)bg[k] * TX_INV255)));
-            }
+            for (int k = 0; k < 3; ++k) o[k] = mk_composite(col[k], shade, alpha, bg[k]);
         }
         out[pidx * 3 + 0] = (uint8_t)o[0]; out[pidx * 3 + 1] = (uint8_t)o[1]; out[pidx * 3 + 2] = (uint8_t)o[2];
         if (sums && cv && usable[pidx] != 0) {

@@ -6,15 +6,9 @@
 // bytes).  A wave walks a contiguous span of tiles of 64 such groups, so a frame's counts stay in the wave's scalar accumulators
 // until the frame changes: one integer atomic per wave, frame and count, after a reduction by ballot and population count.
 //
-// A pixel is covered when its key is not empty, its face index i = key & 0xffffffff is < nf and the face's vertices lie in [0, nv)
-// (the face is read only then).  For a covered pixel centre p = (x, y) of frame f and face (a, b, c) = (v0, v1, v2):
-//   the three vertices are projected by mk_project and the edge values e0 = edge(v1, v2, p), e1 = edge(v2, v0, p),
-//   e2 = edge(v0, v1, p) taken by mk_edge, both the rasteriser's own code (mesh_raster.h);
-//   den = fma(e2, 1/z2, fma(e1, 1/z1, e0 * (1/z0)))      (the denominator of the rasteriser's depth),
-//   l_j = (e_j * (1/z_j)) * (1 / den)                    (1/3 each if den is 0 or not finite: a z-buffer that is not this mesh's),
-//   n = sum_j l_j n_j,  nz = fma(R_f8, n_z, fma(R_f7, n_y, R_f6 * n_x)),  s = |nz| / |n| (0 when |n| is 0 or NaN),
-//   base = colors ? sum_j l_j colors_j / 255 : (0.8, 0.46, 0.51),  c = clamp(base * fma(0.7, s, 0.3), 0, 1),
-//   o = fma(alpha, c, (1 - alpha) * bg),  bg = rgb / 255 (1 without frames),  out = min(floor(fma(255, o, 0.5)), 255).
+// A pixel is covered by mk_key_face.  A covered pixel takes its weights l_j from mk_pixel_weights and its light from mk_headlight, and
+// per channel mk_composite(base, shade, alpha, bg) with base = colors ? fma(l2, c2, fma(l1, c1, l0 c0)) / 255 : (0.8, 0.46, 0.51) and
+// bg the frame's byte (255 without frames): mesh_shade.h states the four rules, which dh_mesh_shade_tex shares.
 // An uncovered pixel copies its background bytes (255 without frames).  With labels, over the pixels with label >= 0:
 //   counts[f] += (covered & label == 1, covered & label == 0, !covered & label == 1).
 // Everything is integer or per pixel: the output and the counts are bitwise reproducible.
@@ -23,7 +17,7 @@
 #include <stdint.h>
 #include "kernels.h"
 #include "launch.h"
-#include "mesh_raster.h"
+#include "mesh_shade.h"
 
 namespace dh {
 
@@ -31,62 +25,25 @@ namespace {
 constexpr int MS_THREADS = 256;
 constexpr int MS_WAVES = MS_THREADS / 64;
 constexpr int MS_TILE = 64 * 4;            // pixels of one wave step
-constexpr float MS_INV255 = 1.f / 255.f;
-
-__device__ inline bool ms_face(uint64_t key, const int64_t* __restrict__ faces, int64_t nf, int64_t nv, int64_t& a, int64_t& b,
-                               int64_t& c) {
-    const int64_t i = (int64_t)(key & 0xffffffffu);
-    if (key == MK_EMPTY || i >= nf) return false;
-    a = faces[i * 3 + 0];
-    b = faces[i * 3 + 1];
-    c = faces[i * 3 + 2];
-    return a >= 0 && a < nv && b >= 0 && b < nv && c >= 0 && c < nv;
-}
-
-__device__ inline uint32_t ms_byte(float o) {
-    return (uint32_t)fminf(floorf(__builtin_fmaf(255.f, o, 0.5f)), 255.f);
-}
 
 // The three composited bytes of a covered pixel, packed as r | g << 8 | b << 16.
 __device__ inline uint32_t ms_shade(const float* __restrict__ verts, const float* __restrict__ normals,
                                     const uint8_t* __restrict__ colors, int64_t a, int64_t b, int64_t c, const float* Rf,
                                     const float* Tf, float k00, float k01, float k02, float k10, float k11, float k12, int x, int y,
                                     uint32_t bg, float alpha) {
-    const Cam p0 = mk_project(Rf, Tf, k00, k01, k02, k10, k11, k12, verts[a * 3], verts[a * 3 + 1], verts[a * 3 + 2]);
-    const Cam p1 = mk_project(Rf, Tf, k00, k01, k02, k10, k11, k12, verts[b * 3], verts[b * 3 + 1], verts[b * 3 + 2]);
-    const Cam p2 = mk_project(Rf, Tf, k00, k01, k02, k10, k11, k12, verts[c * 3], verts[c * 3 + 1], verts[c * 3 + 2]);
-    const float iz0 = 1.f / p0.c2, iz1 = 1.f / p1.c2, iz2 = 1.f / p2.c2;
-    const float px = (float)x, py = (float)y;
-    const float e0 = mk_edge(p1.u, p1.w, p2.u, p2.w, px, py);
-    const float e1 = mk_edge(p2.u, p2.w, p0.u, p0.w, px, py);
-    const float e2 = mk_edge(p0.u, p0.w, p1.u, p1.w, px, py);
-    const float den = __builtin_fmaf(e2, iz2, __builtin_fmaf(e1, iz1, e0 * iz0));
-    const bool ok = (fabsf(den) > 0.f) & (fabsf(den) < 3.0e38f);
-    const float rden = 1.f / den;
-    const float l0 = ok ? (e0 * iz0) * rden : 1.f / 3.f;
-    const float l1 = ok ? (e1 * iz1) * rden : 1.f / 3.f;
-    const float l2 = ok ? (e2 * iz2) * rden : 1.f / 3.f;
-    const float nx = __builtin_fmaf(l2, normals[c * 3 + 0], __builtin_fmaf(l1, normals[b * 3 + 0], l0 * normals[a * 3 + 0]));
-    const float ny = __builtin_fmaf(l2, normals[c * 3 + 1], __builtin_fmaf(l1, normals[b * 3 + 1], l0 * normals[a * 3 + 1]));
-    const float nz = __builtin_fmaf(l2, normals[c * 3 + 2], __builtin_fmaf(l1, normals[b * 3 + 2], l0 * normals[a * 3 + 2]));
-    const float ncz = __builtin_fmaf(Rf[8], nz, __builtin_fmaf(Rf[7], ny, Rf[6] * nx));
-    const float len = sqrtf(__builtin_fmaf(nz, nz, __builtin_fmaf(ny, ny, nx * nx)));
-    const float s = len > 0.f ? fabsf(ncz) / len : 0.f;
-    const float shade = __builtin_fmaf(0.7f, s, 0.3f);
+    float l0, l1, l2;
+    mk_pixel_weights(verts, a, b, c, Rf, Tf, k00, k01, k02, k10, k11, k12, x, y, l0, l1, l2);
+    const float shade = mk_headlight(normals, a, b, c, l0, l1, l2, Rf);
     float base[3] = {0.8f, 0.46f, 0.51f};
     if (colors) {
 #pragma unroll
         for (int k = 0; k < 3; ++k)
             base[k] = __builtin_fmaf(l2, (float)colors[c * 3 + k], __builtin_fmaf(l1, (float)colors[b * 3 + k],
-                                                                                   l0 * (float)colors[a * 3 + k])) * MS_INV255;
+                                                                                   l0 * (float)colors[a * 3 + k])) * MK_INV255;
     }
     uint32_t o = 0;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float col = fmaxf(fminf(1.f, base[k] * shade), 0.f);          // fminf / fmaxf take the number over a NaN
-        const float bk = (float)((bg >> (8 * k)) & 0xffu) * MS_INV255;
-        o |= ms_byte(__builtin_fmaf(alpha, col, (1.f - alpha) * bk)) << (8 * k);
-    }
+    for (int k = 0; k < 3; ++k) o |= mk_composite(base[k], shade, alpha, (bg >> (8 * k)) & 0xffu) << (8 * k);
     return o;
 }
 
@@ -171,7 +128,7 @@ __global__ __launch_bounds__(MS_THREADS) void mesh_shade_kernel(const float* __r
             const uint32_t bg = (j == 0 ? cw[0] : (j == 1 ? (cw[0] >> 24) | (cw[1] << 8)
                                                           : (j == 2 ? (cw[1] >> 16) | (cw[2] << 16) : cw[2] >> 8))) & 0xffffffu;
             int64_t a = 0, b = 0, c = 0;
-            const bool cv = ms_face(kj, faces, nf, nv, a, b, c);
+            const bool cv = mk_key_face(kj, faces, nf, nv, a, b, c);
             const uint32_t o = cv ? ms_shade(verts, normals, colors, a, b, c, R + (int64_t)fj * 9, T + (int64_t)fj * 3, k00, k01, k02,
                                              k10, k11, k12, xj, yj, bg, alpha)
                                   : bg;

@@ -29,13 +29,53 @@ def _verts(fn, verts):
     return _device_tensor(fn, "verts", verts, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[V,3]")
 
 
+def _same_device(fn, device, *tensors):
+    if any(t is not None and t.device != device for t in tensors):
+        raise ValueError(f"{fn}: every tensor must be on {device}")
+
+
 def _cams(fn, F, R, T, K, device):
     R = _device_tensor(fn, "R", R, torch.float32, lambda s: s in ((F, 3, 3), (F, 9)), f"[{F},3,3]")
     T = _device_tensor(fn, "T", T, torch.float32, lambda s: s in ((F, 3), (F, 1, 3)), f"[{F},3]")
     K = _device_tensor(fn, "K", K, torch.float32, lambda s: s == (3, 3), "[3,3]")
-    if any(t.device != device for t in (R, T, K)):
-        raise ValueError(f"{fn}: every tensor must be on {device}")
+    _same_device(fn, device, R, T, K)
     return R, T, K
+
+
+def _normals(fn, verts, faces, normals):
+    if normals is None:
+        normals = vertex_normals(verts, faces)
+    return _device_tensor(fn, "normals", normals, torch.float32, lambda s: s == tuple(verts.shape), "[V,3]")
+
+
+def _draw_args(fn, verts, faces, zbuf, R, T, K, alpha, normals, rgb):
+    """What mesh_vis.shade and mesh_texture.render_textured check alike, under the caller's name `fn`: (verts, faces, zbuf int64
+    [F,H,W] with H, W > 0, R, T, K for its F frames, alpha as a float in [0, 1], normals (default vertex_normals), rgb u8 [F,H,W,3] or
+    None), all on zbuf's device."""
+    verts = _verts(fn, verts)
+    faces = _faces(fn, faces)
+    zbuf = _device_tensor(fn, "zbuf", zbuf, torch.int64, lambda s: len(s) == 3, "[F,H,W]")
+    F, H, W = zbuf.shape
+    if H == 0 or W == 0:
+        raise ValueError(f"{fn}: empty images {H}x{W}")
+    R, T, K = _cams(fn, F, R, T, K, zbuf.device)
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"{fn}: alpha must lie in [0, 1], got {alpha}")
+    normals = _normals(fn, verts, faces, normals)
+    if rgb is not None:
+        rgb = _device_tensor(fn, "rgb", rgb, torch.uint8, lambda s: s == (F, H, W, 3), f"[{F},{H},{W},3]")
+    _same_device(fn, zbuf.device, verts, faces, normals, rgb)
+    return verts, faces, zbuf, R, T, K, alpha, normals, rgb
+
+
+def _check_bake_args(fn, erode_px, min_cos, depth_eps, frame_chunk, sharpen=None):
+    want, got = "erode_px >= 0, frame_chunk >= 1, depth_eps >= 0, min_cos a number", f"{erode_px}, {frame_chunk}, {depth_eps}, {min_cos}"
+    bad = int(erode_px) < 0 or int(frame_chunk) < 1 or not float(depth_eps) >= 0 or float(min_cos) != float(min_cos)
+    if sharpen is not None:
+        want, got, bad = want + ", sharpen in 0..4", got + f", {sharpen}", bad or not 0 <= int(sharpen) <= 4
+    if bad:
+        raise ValueError(f"{fn}: {want}; got {got}")
 
 
 def raster_depth(verts, faces, R, T, K, H: int, W: int) -> torch.Tensor:
@@ -56,6 +96,23 @@ def raster_depth(verts, faces, R, T, K, H: int, W: int) -> torch.Tensor:
         _lib.check(_lib.lib().dh_mesh_raster_depth(_lib.ptr(verts), verts.shape[0], _lib.ptr(faces), faces.shape[0], _lib.ptr(R),
                                                    _lib.ptr(T), _lib.ptr(K), F, H, W, _lib.ptr(zbuf), _lib.stream()))
     return zbuf
+
+
+def frame_chunks(fn, verts, faces, R, T, K, H: int, W: int, frame_chunk: int):
+    """The frames of the cameras R [F,3,3], T [F,3] in chunks of `frame_chunk`: yields (f0, f1, Rc, Tc, zbuf) with Rc, Tc the chunk's
+    contiguous cameras and zbuf = raster_depth(verts, faces, Rc, Tc, K, H, W), which holds frame_chunk * H * W * 8 bytes and is freed
+    when the chunk is done.  Every kernel that consumes a chunk works per frame or adds the frames in order, so results are bitwise
+    the same for every chunk size."""
+    if int(frame_chunk) < 1:
+        raise ValueError(f"{fn}: frame_chunk must be >= 1, got {frame_chunk}")
+    F = R.shape[0]
+    for f0 in range(0, F, int(frame_chunk)):
+        f1 = min(F, f0 + int(frame_chunk))
+        Rc, Tc = R[f0:f1].contiguous(), T[f0:f1].contiguous()
+        zbuf = raster_depth(verts, faces, Rc, Tc, K, H, W)
+        yield f0, f1, Rc, Tc, zbuf
+        zbuf.untyped_storage().resize_(0)            # the consumer's loop variable still names it: give the memory back now
+        del zbuf
 
 
 def zbuf_depth(zbuf: torch.Tensor) -> torch.Tensor:
@@ -93,35 +150,28 @@ def bake_vertex_colors(verts, faces, dataset, erode_px: int = 1, min_cos: float 
                        normals=None):
     """(colors f32 [V,3], weight [V], n_views int32 [V]) from the dataset's frames with its current poses (Dataset.R / T, refined in
     place by pose refinement): colors = sum(c rgb/255) / sum(c) over the contributing frames (module docstring), weight = sum(c); NaN
-    colour where no frame contributes.  Frames go in chunks of `frame_chunk`, so the z-buffer holds frame_chunk * H * W * 8 bytes;
-    the per-vertex sums run over the frames in order whatever the chunking, so the result is bitwise the same for every chunk size.
+    colour where no frame contributes.  Frames go in chunks of `frame_chunk` (frame_chunks); the per-vertex sums run over the frames
+    in order whatever the chunking, so the result is bitwise the same for every chunk size.
     normals: unit vertex normals (default: vertex_normals(verts, faces))."""
-    verts = _verts("bake_vertex_colors", verts)
-    faces = _faces("bake_vertex_colors", faces)
-    if int(erode_px) < 0 or int(frame_chunk) < 1 or not float(depth_eps) >= 0 or float(min_cos) != float(min_cos):
-        raise ValueError(f"bake_vertex_colors: erode_px >= 0, frame_chunk >= 1, depth_eps >= 0, min_cos a number; got {erode_px}, "
-                         f"{frame_chunk}, {depth_eps}, {min_cos}")
-    if normals is None:
-        normals = vertex_normals(verts, faces)
-    normals = _device_tensor("bake_vertex_colors", "normals", normals, torch.float32, lambda s: s == tuple(verts.shape), "[V,3]")
+    fn = "bake_vertex_colors"
+    verts = _verts(fn, verts)
+    faces = _faces(fn, faces)
+    _check_bake_args(fn, erode_px, min_cos, depth_eps, frame_chunk)
+    normals = _normals(fn, verts, faces, normals)
     ds = dataset
     F, H, W = ds.n_images, ds.H, ds.W
-    R, T, K = _cams("bake_vertex_colors", F, ds.R, ds.T, ds.K, verts.device)
-    rgb = _device_tensor("bake_vertex_colors", "dataset.rgb", ds.rgb, torch.uint8, lambda s: s == (F, H, W, 3), f"[{F},{H},{W},3]")
+    R, T, K = _cams(fn, F, ds.R, ds.T, ds.K, verts.device)
+    rgb = _device_tensor(fn, "dataset.rgb", ds.rgb, torch.uint8, lambda s: s == (F, H, W, 3), f"[{F},{H},{W},3]")
     nv = verts.shape[0]
     acc = torch.zeros(nv, 4, dtype=torch.float32, device=verts.device)
     n_views = torch.zeros(nv, dtype=torch.int32, device=verts.device)
     L = _lib.lib()
     with torch.cuda.device(verts.device):
-        for f0 in range(0, F, int(frame_chunk)):
-            f1 = min(F, f0 + int(frame_chunk))
-            Rc, Tc = R[f0:f1].contiguous(), T[f0:f1].contiguous()
-            zbuf = raster_depth(verts, faces, Rc, Tc, K, H, W)
+        for f0, f1, Rc, Tc, zbuf in frame_chunks(fn, verts, faces, R, T, K, H, W, frame_chunk):
             usable = usable_map(ds.label[f0:f1].contiguous(), erode_px)
             _lib.check(L.dh_mesh_bake_colors(_lib.ptr(verts), _lib.ptr(normals), nv, _lib.ptr(rgb[f0:f1]), _lib.ptr(usable),
                                              _lib.ptr(zbuf), _lib.ptr(Rc), _lib.ptr(Tc), _lib.ptr(K), f1 - f0, H, W,
                                              float(depth_eps), float(min_cos), _lib.ptr(acc), _lib.ptr(n_views), _lib.stream()))
-            del zbuf, usable
     w = acc[:, 3]
     colors = torch.where((n_views > 0)[:, None], acc[:, :3] / w[:, None], torch.full_like(acc[:, :3], float("nan")))
     return colors, w, n_views

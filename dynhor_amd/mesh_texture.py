@@ -41,7 +41,8 @@ import torch
 
 from . import _lib
 from .mesh_clean import _device_tensor, _faces
-from .mesh_color import _cams, _verts, network_vertex_colors, raster_depth, usable_map, vertex_normals
+from .mesh_color import (_cams, _check_bake_args, _draw_args, _normals, _same_device, _verts, frame_chunks, network_vertex_colors,
+                         usable_map, vertex_normals)
 
 MODES = ("none", "views", "views+network")
 MIN_CELL = 8
@@ -92,16 +93,8 @@ def face_atlas(n_faces: int, size: int, device=None):
 
 def _uv(fn, uv, nf, device):
     uv = _device_tensor(fn, "uv", uv, torch.float32, lambda s: s == (nf, 3, 2), f"[{nf},3,2]")
-    if uv.device != device:
-        raise ValueError(f"{fn}: every tensor must be on {device}")
+    _same_device(fn, device, uv)
     return uv
-
-
-def _check_bake_args(fn, erode_px, min_cos, depth_eps, sharpen, frame_chunk):
-    if int(erode_px) < 0 or int(frame_chunk) < 1 or not float(depth_eps) >= 0 or float(min_cos) != float(min_cos) or \
-            not 0 <= int(sharpen) <= 4:
-        raise ValueError(f"{fn}: erode_px >= 0, frame_chunk >= 1, depth_eps >= 0, min_cos a number, sharpen in 0..4; got {erode_px}, "
-                         f"{frame_chunk}, {depth_eps}, {min_cos}, {sharpen}")
 
 
 def bake_texture_sums(verts, faces, dataset, uv, owner, erode_px: int = 1, min_cos: float = 0.1, depth_eps: float = 0.01,
@@ -112,34 +105,27 @@ def bake_texture_sums(verts, faces, dataset, uv, owner, erode_px: int = 1, min_c
     fn = "bake_texture_sums"
     verts = _verts(fn, verts)
     faces = _faces(fn, faces)
-    _check_bake_args(fn, erode_px, min_cos, depth_eps, sharpen, frame_chunk)
+    _check_bake_args(fn, erode_px, min_cos, depth_eps, frame_chunk, sharpen)
     nf, nv, dev = faces.shape[0], verts.shape[0], verts.device
     uv = _uv(fn, uv, nf, dev)
     owner = _device_tensor(fn, "owner", owner, torch.int32, lambda s: len(s) == 2 and s[0] == s[1], "[S,S]")
-    if normals is None:
-        normals = vertex_normals(verts, faces)
-    normals = _device_tensor(fn, "normals", normals, torch.float32, lambda s: s == tuple(verts.shape), "[V,3]")
+    normals = _normals(fn, verts, faces, normals)
     ds = dataset
     F, H, W = ds.n_images, ds.H, ds.W
     R, T, K = _cams(fn, F, ds.R, ds.T, ds.K, dev)
     rgb = _device_tensor(fn, "dataset.rgb", ds.rgb, torch.uint8, lambda s: s == (F, H, W, 3), f"[{F},{H},{W},3]")
-    if any(t.device != dev for t in (faces, owner, normals, rgb)):
-        raise ValueError(f"{fn}: every tensor must be on {dev}")
+    _same_device(fn, dev, faces, owner, normals, rgb)
     S = owner.shape[0]
     acc = torch.zeros(S, S, 4, dtype=torch.float32, device=dev)
     n_views = torch.zeros(S, S, dtype=torch.int32, device=dev)
     L = _lib.lib()
     with torch.cuda.device(dev):
-        for f0 in range(0, F, int(frame_chunk)):
-            f1 = min(F, f0 + int(frame_chunk))
-            Rc, Tc = R[f0:f1].contiguous(), T[f0:f1].contiguous()
-            zbuf = raster_depth(verts, faces, Rc, Tc, K, H, W)
+        for f0, f1, Rc, Tc, zbuf in frame_chunks(fn, verts, faces, R, T, K, H, W, frame_chunk):
             usable = usable_map(ds.label[f0:f1].contiguous(), erode_px)
             _lib.check(L.dh_texture_bake(_lib.ptr(verts), _lib.ptr(normals), nv, _lib.ptr(faces), nf, _lib.ptr(uv), _lib.ptr(owner), S,
                                          _lib.ptr(rgb[f0:f1]), _lib.ptr(usable), _lib.ptr(zbuf), _lib.ptr(Rc), _lib.ptr(Tc), _lib.ptr(K),
                                          f1 - f0, H, W, float(depth_eps), float(min_cos), int(sharpen), _lib.ptr(acc),
                                          _lib.ptr(n_views), _lib.stream()))
-            del zbuf, usable
     return acc, n_views
 
 
@@ -211,30 +197,16 @@ def render_textured(verts, faces, zbuf, R, T, K, uv, tex, normals=None, rgb=None
     headlight, composited over rgb u8 [F,H,W,3] (white without) with alpha.  usable u8 [F,H,W] (needs rgb): sums[f] = (sum over the
     covered usable pixels and the three channels of (out - rgb)^2, their number)."""
     fn = "render_textured"
-    verts = _verts(fn, verts)
-    faces = _faces(fn, faces)
-    zbuf = _device_tensor(fn, "zbuf", zbuf, torch.int64, lambda s: len(s) == 3, "[F,H,W]")
+    verts, faces, zbuf, R, T, K, alpha, normals, rgb = _draw_args(fn, verts, faces, zbuf, R, T, K, alpha, normals, rgb)
     F, H, W = zbuf.shape
-    if H == 0 or W == 0:
-        raise ValueError(f"{fn}: empty images {H}x{W}")
     dev = zbuf.device
-    R, T, K = _cams(fn, F, R, T, K, dev)
-    alpha = float(alpha)
-    if not 0.0 <= alpha <= 1.0:
-        raise ValueError(f"{fn}: alpha must lie in [0, 1], got {alpha}")
     uv = _uv(fn, uv, faces.shape[0], dev)
     tex = _device_tensor(fn, "tex", tex, torch.uint8, lambda s: len(s) == 3 and s[2] == 3 and s[0] > 0 and s[1] > 0, "[Sh,Sw,3]")
-    if normals is None:
-        normals = vertex_normals(verts, faces)
-    normals = _device_tensor(fn, "normals", normals, torch.float32, lambda s: s == tuple(verts.shape), "[V,3]")
-    if rgb is not None:
-        rgb = _device_tensor(fn, "rgb", rgb, torch.uint8, lambda s: s == (F, H, W, 3), f"[{F},{H},{W},3]")
     if usable is not None:
         if rgb is None:
             raise ValueError(f"{fn}: usable needs rgb (the error sums are taken against it)")
         usable = _device_tensor(fn, "usable", usable, torch.uint8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
-    if any(t is not None and t.device != dev for t in (verts, faces, normals, tex, rgb, usable)):
-        raise ValueError(f"{fn}: every tensor must be on {dev}")
+    _same_device(fn, dev, tex, usable)
     out = torch.empty(F, H, W, 3, dtype=torch.uint8, device=dev)
     sums = torch.zeros(F, 2, dtype=torch.int64, device=dev) if usable is not None else None
     opt = lambda t: _lib.ptr(t) if t is not None else ctypes.c_void_p(0)
@@ -257,69 +229,23 @@ def psnr_from_sums(sse, count):
 def texture_psnr(verts, faces, dataset, uv, tex, erode_px: int = 1, frame_chunk: int = 16) -> dict:
     """Re-render PSNR of the textured mesh, unlit, against the dataset's frames at its current poses, over the pixels the mesh covers
     whose label is usable (object, eroded by erode_px): {"frames": [psnr or None per frame], "pooled", "sse", "count"}."""
-    verts = _verts("texture_psnr", verts)
-    faces = _faces("texture_psnr", faces)
-    if int(frame_chunk) < 1 or int(erode_px) < 0:
-        raise ValueError(f"texture_psnr: frame_chunk >= 1 and erode_px >= 0, got {frame_chunk} and {erode_px}")
+    fn = "texture_psnr"
+    verts = _verts(fn, verts)
+    faces = _faces(fn, faces)
+    if int(erode_px) < 0:
+        raise ValueError(f"{fn}: erode_px must be >= 0, got {erode_px}")
     ds = dataset
     F, H, W = ds.n_images, ds.H, ds.W
-    R, T, K = _cams("texture_psnr", F, ds.R, ds.T, ds.K, verts.device)
+    R, T, K = _cams(fn, F, ds.R, ds.T, ds.K, verts.device)
     normals = vertex_normals(verts, faces)
     sums = torch.zeros(F, 2, dtype=torch.int64, device=verts.device)
-    for f0 in range(0, F, int(frame_chunk)):
-        f1 = min(F, f0 + int(frame_chunk))
-        Rc, Tc = R[f0:f1].contiguous(), T[f0:f1].contiguous()
-        zbuf = raster_depth(verts, faces, Rc, Tc, K, H, W)
+    for f0, f1, Rc, Tc, zbuf in frame_chunks(fn, verts, faces, R, T, K, H, W, frame_chunk):
         usable = usable_map(ds.label[f0:f1].contiguous(), erode_px)
         sums[f0:f1] = render_textured(verts, faces, zbuf, Rc, Tc, K, uv, tex, normals=normals, rgb=ds.rgb[f0:f1].contiguous(),
                                       usable=usable)[1]
-        del zbuf, usable
     rows = sums.tolist()
     sse, count = sum(r[0] for r in rows), sum(r[1] for r in rows)
     return {"frames": [psnr_from_sums(*r) for r in rows], "pooled": psnr_from_sums(sse, count), "sse": sse, "count": count}
-
-
-def overlay_frames_textured(verts, faces, dataset, uv, tex, alpha: float = 0.6, frame_chunk: int = 16, sink=None):
-    """mesh_vis.overlay_frames for a mesh that has a texture: the same counts int64 [F,3] (mesh_vis.shade's, from the same z-buffer),
-    the images drawn lit through render_textured."""
-    from .mesh_vis import shade
-    verts = _verts("overlay_frames_textured", verts)
-    faces = _faces("overlay_frames_textured", faces)
-    if int(frame_chunk) < 1:
-        raise ValueError(f"overlay_frames_textured: frame_chunk must be >= 1, got {frame_chunk}")
-    ds = dataset
-    F, H, W = ds.n_images, ds.H, ds.W
-    R, T, K = _cams("overlay_frames_textured", F, ds.R, ds.T, ds.K, verts.device)
-    normals = vertex_normals(verts, faces)
-    counts = torch.zeros(F, 3, dtype=torch.int64, device=verts.device)
-    for f0 in range(0, F, int(frame_chunk)):
-        f1 = min(F, f0 + int(frame_chunk))
-        Rc, Tc = R[f0:f1].contiguous(), T[f0:f1].contiguous()
-        zbuf = raster_depth(verts, faces, Rc, Tc, K, H, W)
-        counts[f0:f1] = shade(verts, faces, zbuf, Rc, Tc, K, normals=normals, rgb=ds.rgb[f0:f1], label=ds.label[f0:f1], alpha=alpha)[1]
-        out = render_textured(verts, faces, zbuf, Rc, Tc, K, uv, tex, normals=normals, rgb=ds.rgb[f0:f1].contiguous(), alpha=alpha,
-                              lit=True)[0]
-        del zbuf
-        if sink is not None:
-            sink(f0, out)
-        del out
-    return counts
-
-
-def turntable_textured(verts, faces, K, H: int, W: int, R, T, uv, tex, frame_chunk: int = 16):
-    """mesh_vis.turntable for a mesh that has a texture: u8 [n,H,W,3], lit, on white."""
-    verts = _verts("turntable_textured", verts)
-    faces = _faces("turntable_textured", faces)
-    n = R.shape[0]
-    R, T, K = _cams("turntable_textured", n, R, T, K, verts.device)
-    normals = vertex_normals(verts, faces)
-    out = torch.empty(n, int(H), int(W), 3, dtype=torch.uint8, device=verts.device)
-    for f0 in range(0, n, int(frame_chunk)):
-        f1 = min(n, f0 + int(frame_chunk))
-        Rc, Tc = R[f0:f1].contiguous(), T[f0:f1].contiguous()
-        zbuf = raster_depth(verts, faces, Rc, Tc, K, H, W)
-        out[f0:f1] = render_textured(verts, faces, zbuf, Rc, Tc, K, uv, tex, normals=normals, lit=True)[0]
-    return out
 
 
 # ------------------------------------------------------------------------------------------------ files

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from .mesh_clean import _device_tensor, _faces
-from .mesh_color import _cams, _verts, raster_depth, vertex_normals
+from .mesh_color import _cams, _draw_args, _same_device, _verts, frame_chunks, vertex_normals
 
 BASE_COLOR = (0.8, 0.46, 0.51)      # the constant base colour of a mesh without vertex colours
 N_WORST = 5
@@ -34,27 +34,13 @@ def shade(verts, faces, zbuf, R, T, K, normals=None, colors=None, rgb=None, labe
     unit vertex normals (default vertex_normals(verts, faces)); colors: u8 [V,3] or None for BASE_COLOR; rgb: u8 [F,H,W,3] frames or
     None for white; label: i8 [F,H,W] (1 object, 0 background, -1 hand) or None for no counts; alpha in [0, 1]."""
     fn = "shade"
-    verts = _verts(fn, verts)
-    faces = _faces(fn, faces)
-    zbuf = _device_tensor(fn, "zbuf", zbuf, torch.int64, lambda s: len(s) == 3, "[F,H,W]")
+    verts, faces, zbuf, R, T, K, alpha, normals, rgb = _draw_args(fn, verts, faces, zbuf, R, T, K, alpha, normals, rgb)
     F, H, W = zbuf.shape
-    if H == 0 or W == 0:
-        raise ValueError(f"{fn}: empty images {H}x{W}")
-    R, T, K = _cams(fn, F, R, T, K, zbuf.device)
-    alpha = float(alpha)
-    if not 0.0 <= alpha <= 1.0:
-        raise ValueError(f"{fn}: alpha must lie in [0, 1], got {alpha}")
-    if normals is None:
-        normals = vertex_normals(verts, faces)
-    normals = _device_tensor(fn, "normals", normals, torch.float32, lambda s: s == tuple(verts.shape), "[V,3]")
     if colors is not None:
         colors = _device_tensor(fn, "colors", colors, torch.uint8, lambda s: s == tuple(verts.shape), "[V,3]")
-    if rgb is not None:
-        rgb = _device_tensor(fn, "rgb", rgb, torch.uint8, lambda s: s == (F, H, W, 3), f"[{F},{H},{W},3]")
     if label is not None:
         label = _device_tensor(fn, "label", label, torch.int8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
-    if any(t is not None and t.device != zbuf.device for t in (verts, faces, normals, colors, rgb, label)):
-        raise ValueError(f"{fn}: every tensor must be on {zbuf.device}")
+    _same_device(fn, zbuf.device, colors, label)
     out = torch.empty(F, H, W, 3, dtype=torch.uint8, device=zbuf.device)
     counts = torch.zeros(F, 3, dtype=torch.int64, device=zbuf.device) if label is not None else None
     opt = lambda t: _lib.ptr(t) if t is not None else ctypes.c_void_p(0)
@@ -65,28 +51,34 @@ def shade(verts, faces, zbuf, R, T, K, normals=None, colors=None, rgb=None, labe
     return out, counts
 
 
-def overlay_frames(verts, faces, dataset, colors=None, alpha: float = 0.6, frame_chunk: int = 16, sink=None):
+def _draw(verts, faces, zbuf, Rc, Tc, K, normals, colors, texture, rgb=None, label=None, alpha: float = 1.0):
+    """(out, counts) of one chunk: shade, or with texture = (uv, tex) the counts of shade and the image of render_textured, lit."""
+    out, counts = None, None
+    if texture is None or label is not None:
+        out, counts = shade(verts, faces, zbuf, Rc, Tc, K, normals=normals, colors=colors, rgb=rgb, label=label, alpha=alpha)
+    if texture is not None:
+        from .mesh_texture import render_textured
+        out = render_textured(verts, faces, zbuf, Rc, Tc, K, texture[0], texture[1], normals=normals, rgb=rgb, alpha=alpha, lit=True)[0]
+    return out, counts
+
+
+def overlay_frames(verts, faces, dataset, colors=None, alpha: float = 0.6, frame_chunk: int = 16, sink=None, texture=None):
     """counts int64 [F,3] (tp, fp, fn per frame) of the mesh drawn over the dataset's frames with its current poses (Dataset.R / T /
-    K, refined in place by pose refinement), its rgb and its labels.  Frames go in chunks of `frame_chunk` (raster, then shade; the
-    z-buffer holds frame_chunk * H * W * 8 bytes); sink(f0, out_chunk u8 [n,H,W,3]) is called for every chunk when given.  Images
-    and counts are bitwise the same for every chunk size."""
-    verts = _verts("overlay_frames", verts)
-    faces = _faces("overlay_frames", faces)
-    if int(frame_chunk) < 1:
-        raise ValueError(f"overlay_frames: frame_chunk must be >= 1, got {frame_chunk}")
+    K, refined in place by pose refinement), its rgb and its labels.  Frames go in chunks of `frame_chunk` (frame_chunks: raster, then
+    shade); sink(f0, out_chunk u8 [n,H,W,3]) is called for every chunk when given.  texture = (uv, tex) of a mesh that has one: the
+    same counts (shade's, from the same z-buffer), the images drawn lit through mesh_texture.render_textured.  Images and counts are
+    bitwise the same for every chunk size."""
+    fn = "overlay_frames"
+    verts = _verts(fn, verts)
+    faces = _faces(fn, faces)
     ds = dataset
     F, H, W = ds.n_images, ds.H, ds.W
-    R, T, K = _cams("overlay_frames", F, ds.R, ds.T, ds.K, verts.device)
+    R, T, K = _cams(fn, F, ds.R, ds.T, ds.K, verts.device)
     normals = vertex_normals(verts, faces)
     counts = torch.zeros(F, 3, dtype=torch.int64, device=verts.device)
-    for f0 in range(0, F, int(frame_chunk)):
-        f1 = min(F, f0 + int(frame_chunk))
-        Rc, Tc = R[f0:f1].contiguous(), T[f0:f1].contiguous()
-        zbuf = raster_depth(verts, faces, Rc, Tc, K, H, W)
-        out, cnt = shade(verts, faces, zbuf, Rc, Tc, K, normals=normals, colors=colors, rgb=ds.rgb[f0:f1], label=ds.label[f0:f1],
-                         alpha=alpha)
-        counts[f0:f1] = cnt
-        del zbuf
+    for f0, f1, Rc, Tc, zbuf in frame_chunks(fn, verts, faces, R, T, K, H, W, frame_chunk):
+        out, counts[f0:f1] = _draw(verts, faces, zbuf, Rc, Tc, K, normals, colors, texture, rgb=ds.rgb[f0:f1], label=ds.label[f0:f1],
+                                   alpha=alpha)
         if sink is not None:
             sink(f0, out)
         del out
@@ -149,17 +141,15 @@ def orbit_cameras(R, T, n: int):
     return torch.stack(Rs).to(R.device, R.dtype), torch.stack(Ts).to(R.device, R.dtype)
 
 
-def turntable(verts, faces, K, H: int, W: int, R, T, colors=None, frame_chunk: int = 16):
-    """u8 [n,H,W,3]: the mesh from the cameras R [n,3,3], T [n,3] (e.g. orbit_cameras) with intrinsics K, on white, alpha 1."""
+def turntable(verts, faces, K, H: int, W: int, R, T, colors=None, frame_chunk: int = 16, texture=None):
+    """u8 [n,H,W,3]: the mesh from the cameras R [n,3,3], T [n,3] (e.g. orbit_cameras) with intrinsics K, on white, alpha 1; with
+    texture = (uv, tex) drawn with its texture, lit."""
     verts = _verts("turntable", verts)
     faces = _faces("turntable", faces)
     n = R.shape[0]
     R, T, K = _cams("turntable", n, R, T, K, verts.device)
     normals = vertex_normals(verts, faces)
     out = torch.empty(n, int(H), int(W), 3, dtype=torch.uint8, device=verts.device)
-    for f0 in range(0, n, int(frame_chunk)):
-        f1 = min(n, f0 + int(frame_chunk))
-        Rc, Tc = R[f0:f1].contiguous(), T[f0:f1].contiguous()
-        zbuf = raster_depth(verts, faces, Rc, Tc, K, H, W)
-        out[f0:f1] = shade(verts, faces, zbuf, Rc, Tc, K, normals=normals, colors=colors, alpha=1.0)[0]
+    for f0, f1, Rc, Tc, zbuf in frame_chunks("turntable", verts, faces, R, T, K, H, W, frame_chunk):
+        out[f0:f1] = _draw(verts, faces, zbuf, Rc, Tc, K, normals, colors, texture)[0]
     return out

@@ -771,7 +771,7 @@ class Runner:
                                                        depth_eps=float(cc["depth_eps"]))
         textured = None                                          # (uv, tex) of a mesh file that brings its own texture
         if mesh is not None and str(mesh).lower().endswith(".obj") and cmode == "none" and smode == "none" and cc["mode"] == "none":
-            from .mesh_texture import load_textured_obj, overlay_frames_textured, turntable_textured
+            from .mesh_texture import load_textured_obj
             _, tfaces, tuv, ttex = load_textured_obj(str(mesh))
             if tuv is not None and torch.equal(tfaces, faces.cpu()):
                 textured = (tuv.to(self.device).contiguous(), ttex.to(self.device).contiguous())
@@ -792,10 +792,7 @@ class Runner:
                 host = out.cpu().numpy()
                 pending.extend(pool.submit(write, os.path.join(d, stems[f0 + k] + ".jpg"), host[k]) for k in range(host.shape[0]))
         try:
-            if textured is not None:
-                counts = overlay_frames_textured(verts, faces, ds, textured[0], textured[1], alpha=alpha, sink=sink)
-            else:
-                counts = overlay_frames(verts, faces, ds, colors=colors, alpha=alpha, sink=sink)
+            counts = overlay_frames(verts, faces, ds, colors=colors, alpha=alpha, sink=sink, texture=textured)
             res = silhouette_summary(counts.cpu(), stems)
             res.update(iter=self.iter_step, mesh=name, clean=cmode, color=cc["mode"], alpha=alpha)
             if textured is not None:
@@ -804,10 +801,7 @@ class Runner:
                 res.update(simplify=smode, faces=int(faces.shape[0]))
             if save and n_turn > 0:
                 Ro, To = orbit_cameras(ds.R, ds.T, n_turn)
-                if textured is not None:
-                    imgs = turntable_textured(verts, faces, ds.K, ds.H, ds.W, Ro, To, textured[0], textured[1]).cpu().numpy()
-                else:
-                    imgs = render_turntable(verts, faces, ds.K, ds.H, ds.W, Ro, To, colors=colors).cpu().numpy()
+                imgs = render_turntable(verts, faces, ds.K, ds.H, ds.W, Ro, To, colors=colors, texture=textured).cpu().numpy()
                 frames = [Image.fromarray(im) for im in imgs]
                 frames[0].save(os.path.join(d, "turntable.gif"), save_all=True, append_images=frames[1:], duration=100, loop=0)
         finally:

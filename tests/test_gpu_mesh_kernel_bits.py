@@ -1,5 +1,6 @@
-"""The mesh kernels' outputs bit for bit against tests/golden/mesh_kernel_bits.json, one SHA-256 per output tensor, recorded by
-tests/golden/make_golden_mesh_kernel_bits.py at the commit the file names.  Every output here is reproducible by construction (64-bit
+"""The mesh kernels' outputs bit for bit against tests/golden/mesh_kernel_bits.json and, for the draw and texture kernels (DRAW_CASES),
+tests/golden/mesh_draw_bits.json: one SHA-256 per output tensor, recorded by tests/golden/make_golden_mesh_kernel_bits.py at the commit
+each file names.  Every output here is reproducible by construction (64-bit
 atomic minima, integer counts, fixed-order fp64 sums), so a change to these kernels that means to change no arithmetic must leave every
 hash as it is: a differing hash is a finding to explain, never a reason to record again.  The inputs are the cases of the kernels' own
 tests (their builders imported), plus one ten-face mesh that walks the rasteriser's skip rules; every input tensor is hashed as well
@@ -18,7 +19,9 @@ from tests import pose_sil_util as U
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mesh_kernel_bits.json")
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+GOLDEN = os.path.join(GOLDEN_DIR, "mesh_kernel_bits.json")
+GOLDEN_DRAW = os.path.join(GOLDEN_DIR, "mesh_draw_bits.json")
 
 
 def sha(t: torch.Tensor) -> str:
@@ -143,6 +146,98 @@ def _simplify():
                 n_clamped=torch.tensor([stats["n_clamped"]], dtype=torch.int64))
 
 
+def _shade_colors():
+    """The scene of test_gpu_mesh_vis.test_shade_matches_fp64_on_the_gpus_zbuffer with vertex colours, frames and alpha 0.6: the frames
+    aligned (the dword form of the kernel) and at an odd byte offset (its byte form)."""
+    from dynhor_amd.mesh_color import raster_depth, vertex_normals
+    from dynhor_amd.mesh_vis import shade
+    from tests.test_gpu_mesh_color import _cameras
+    from tests.test_gpu_mesh_vis import _smooth_colors, _two_spheres
+    H, W = 64, 96
+    R, T, K = _cameras(6, H, W, seed=3)
+    verts, faces = _two_spheres()
+    normals = vertex_normals(verts, faces)
+    colors = _smooth_colors(verts)
+    zbuf = raster_depth(verts, faces, R, T, K, H, W)
+    g = torch.Generator(device=DEV).manual_seed(1)
+    frames = torch.randint(0, 256, (6, H, W, 3), dtype=torch.uint8, device=DEV, generator=g)
+    store = torch.empty(frames.numel() + 1, dtype=torch.uint8, device=DEV)
+    odd = store[1:].view(6, H, W, 3)
+    odd.copy_(frames)
+    assert frames.data_ptr() % 4 == 0 and odd.data_ptr() % 4 == 1
+    out = shade(verts, faces, zbuf, R, T, K, normals=normals, colors=colors, rgb=frames, alpha=0.6)[0]
+    out_odd = shade(verts, faces, zbuf, R, T, K, normals=normals, colors=colors, rgb=odd, alpha=0.6)[0]
+    return dict(_ins(verts=verts, faces=faces, normals=normals, colors=colors, rgb=frames, R=R, T=T, zbuf=zbuf), out=out,
+                out_odd=out_odd)
+
+
+def _shade_counts():
+    """The scene of test_gpu_mesh_vis.test_counts_equal_a_torch_count: no vertex colours, groups of four pixels straddle frames."""
+    from dynhor_amd.mesh_color import raster_depth, vertex_normals
+    from dynhor_amd.mesh_vis import shade
+    from tests.test_gpu_mesh_color import _cameras
+    from tests.test_gpu_mesh_vis import _labels_for, _two_spheres
+    H, W = 45, 61
+    R, T, K = _cameras(5, H, W, seed=4)
+    verts, faces = _two_spheres()
+    normals = vertex_normals(verts, faces)
+    zbuf = raster_depth(verts, faces, R, T, K, H, W)
+    lab = _labels_for(zbuf)
+    g = torch.Generator(device=DEV).manual_seed(2)
+    rgb = torch.randint(0, 256, (5, H, W, 3), dtype=torch.uint8, device=DEV, generator=g)
+    out, counts = shade(verts, faces, zbuf, R, T, K, normals=normals, rgb=rgb, label=lab, alpha=0.6)
+    return dict(_ins(verts=verts, faces=faces, normals=normals, rgb=rgb, label=lab, R=R, T=T, zbuf=zbuf), out=out, counts=counts)
+
+
+@functools.lru_cache(maxsize=None)
+def _texture_scene():
+    """The bake_case scene of test_gpu_mesh_texture.py without its fp64 restatement, shared by the two texture cases."""
+    from dynhor_amd.mesh_color import raster_depth, usable_map, vertex_normals
+    from dynhor_amd.mesh_texture import face_atlas
+    from tests import mesh_texture_util as X
+    verts, faces, ds = X.bake_scene(DEV)
+    S = X.atlas_size_with_margin(faces.shape[0])
+    uv, owner, _ = face_atlas(faces.shape[0], S, device=DEV)
+    normals = vertex_normals(verts, faces)
+    zbuf = raster_depth(verts, faces, ds.R, ds.T, ds.K, ds.H, ds.W)
+    return verts, faces, ds, S, uv, owner, normals, zbuf, usable_map(ds.label, 1)
+
+
+def _texture_bake():
+    """One dh_texture_bake call over all frames at the defaults (sharpen 2), and one with sharpen 0."""
+    from dynhor_amd import _lib
+    verts, faces, ds, S, uv, owner, normals, zbuf, usable = _texture_scene()
+    out = dict(_ins(verts=verts, faces=faces, normals=normals, uv=uv, owner=owner, rgb=ds.rgb, usable=usable, R=ds.R, T=ds.T, zbuf=zbuf))
+    for sharpen in (2, 0):
+        acc = torch.zeros(S, S, 4, device=DEV)
+        cnt = torch.zeros(S, S, dtype=torch.int32, device=DEV)
+        _lib.check(_lib.lib().dh_texture_bake(_lib.ptr(verts), _lib.ptr(normals), verts.shape[0], _lib.ptr(faces), faces.shape[0],
+                                              _lib.ptr(uv), _lib.ptr(owner), S, _lib.ptr(ds.rgb), _lib.ptr(usable), _lib.ptr(zbuf),
+                                              _lib.ptr(ds.R), _lib.ptr(ds.T), _lib.ptr(ds.K), ds.n_images, ds.H, ds.W, 0.01, 0.1, sharpen,
+                                              _lib.ptr(acc), _lib.ptr(cnt), _lib.stream()))
+        out.update({f"acc_sharpen{sharpen}": acc, f"n_views_sharpen{sharpen}": cnt})
+    return out
+
+
+def _shade_tex():
+    """The border-reaching uv and the texture of test_gpu_mesh_texture.test_shade_tex_matches_fp64_with_exact_sums."""
+    from dynhor_amd.mesh_texture import render_textured
+    from tests import mesh_texture_util as X
+    verts, faces, ds, S, uv, _, normals, zbuf, usable = _texture_scene()
+    tex = X.smooth_noisy_frames(1, S, S, seed=11, device=DEV)[0].contiguous()
+    uv = uv.clone()
+    big = torch.tensor([[[0.0, 0.0], [S, 0.0], [0.0, S]], [[S, S], [0.0, S], [S, 0.0]]], device=DEV)
+    uv[0::7] = big[0]
+    uv[3::7] = big[1]
+    out = dict(_ins(verts=verts, faces=faces, normals=normals, uv=uv, tex=tex, rgb=ds.rgb, usable=usable, R=ds.R, T=ds.T, zbuf=zbuf))
+    for lit, alpha, name in ((False, 1.0, "unlit_a1"), (True, 0.6, "lit_a0.6")):
+        img, sums = render_textured(verts, faces, zbuf, ds.R, ds.T, ds.K, uv, tex, normals=normals, rgb=ds.rgb, usable=usable,
+                                    alpha=alpha, lit=lit)
+        out.update({"out_" + name: img, "sums_" + name: sums})
+    out["out_no_frames"] = render_textured(verts, faces, zbuf, ds.R, ds.T, ds.K, uv, tex, normals=normals)[0]
+    return out
+
+
 # The skip rules of the face walker, which no other test reaches: ten faces in one 64 x 96 frame, given as (u, w, depth) per corner and
 # unprojected through K (R = I, T = 0).  Faces 0..3 must be rejected whole; face 4 has no pixel; 5..8 are clipped by one border each;
 # face 9 is 60 px wide (the wave phase).
@@ -202,7 +297,16 @@ CASES = {
     "moments_plane": functools.partial(_moments, True),
     "simplify": _simplify,
     "skip_rules": _skip_rules,
+    "shade_colors": _shade_colors,
+    "shade_counts": _shade_counts,
+    "texture_bake": _texture_bake,
+    "shade_tex": _shade_tex,
 }
+DRAW_CASES = ("shade_colors", "shade_counts", "texture_bake", "shade_tex")       # recorded in GOLDEN_DRAW, the rest in GOLDEN
+
+
+def golden_path(case):
+    return GOLDEN_DRAW if case in DRAW_CASES else GOLDEN
 
 
 def hashes(case):
@@ -212,7 +316,7 @@ def hashes(case):
 # ------------------------------------------------------------------------------------------------ the tests
 @pytest.mark.parametrize("case", list(CASES))
 def test_outputs_equal_the_recorded_bits(case):
-    golden = json.load(open(GOLDEN))
+    golden = json.load(open(golden_path(case)))
     want = golden["hashes"][case]
     got = hashes(case)
     assert sorted(got) == sorted(want), (sorted(got), sorted(want))
