@@ -81,6 +81,11 @@ SIGNATURES = {
     "dh_render_scan_bwd_rays": (_i32, [_vp] * 7 + [_f32, _f32, _vp, _i64, _i32] + [_vp] * 12),
     "dh_march_count": (_i32, [_vp] * 6 + [_i32, _f32, _f32, _f32, _i32, _i64, _vp, _vp]),
     "dh_march_emit": (_i32, [_vp] * 6 + [_i32, _f32, _f32, _f32, _i32, _i64] + [_vp] * 7),
+    "dh_trace_init": (_i32, [_vp] * 3 + [_i32, _i32, _i32, _i32, _f32] + [_vp] * 6),
+    "dh_trace_step": (_i32, [_vp] * 5 + [_i64, _i64] + [_vp] * 10 + [_f32, _f32, _f32, _f32, _i32, _i64, _vp, _vp]),
+    "dh_trace_points": (_i32, [_vp] * 4 + [_i64, _i64, _i64, _vp, _vp]),
+    "dh_trace_compact": (_i32, [_vp] * 6 + [_i64, _i64, _i64] + [_vp] * 5),
+    "dh_trace_compose": (_i32, [_vp] * 6 + [_i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32] + [_vp] * 5),
     "dh_render_scan_fwd_packed": (_i32, [_vp] * 7 + [_f32, _f32, _vp, _i64] + [_vp] * 11),
     "dh_render_scan_bwd_packed": (_i32, [_vp] * 7 + [_f32, _f32, _vp, _i64] + [_vp] * 13),
     "dh_neus_loss": (_i32, [_vp] * 6 + [_i64, _f32, _f32, _f32] + [_vp] * 6),

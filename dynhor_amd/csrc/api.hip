@@ -902,4 +902,73 @@ int dh_simplify_faces(const int64_t* faces, int64_t nf, const int32_t* vrank, in
     return launch_simplify_faces(faces, nf, vrank, nv, n_runs, tri, keep, key, static_cast<hipStream_t>(stream));
 }
 
+// ---- sphere tracing of the SDF (trace.hip)
+static inline bool trace_dims(int n_views, int H, int W, int level, int64_t& h, int64_t& w, int64_t& N) {
+    if (n_views < 0 || H < 1 || W < 1 || level < 1) return false;
+    h = ((int64_t)H + level - 1) / level;
+    w = ((int64_t)W + level - 1) / level;
+    N = (int64_t)n_views * h * w;
+    return true;
+}
+
+int dh_trace_init(const float* R, const float* T, const float* Kinv, int n_views, int H, int W, int level, float bound, float* o,
+                  float* d, float* t, float* t_far, uint8_t* state, void* stream) {
+    int64_t h, w, N;
+    if (!trace_dims(n_views, H, W, level, h, w, N) || !(bound > 0.f)) return DH_ERR_BAD_ARG;
+    if (N >= (1ll << 31)) return DH_ERR_UNSUPPORTED;
+    if (N == 0) return DH_OK;
+    if (!R || !T || !Kinv || !o || !d || !t || !t_far || !state) return DH_ERR_BAD_ARG;
+    return launch_trace_init(R, T, Kinv, (int)h, (int)w, level, bound, N, o, d, t, t_far, state, static_cast<hipStream_t>(stream));
+}
+
+int dh_trace_step(const int32_t* idx, const int32_t* count, const float* s, const float* o, const float* d, int64_t rays_per_view,
+                  int64_t N, float* t, const float* t_far, float* t_lo, float* s_lo, float* t_hi, float* s_hi, uint8_t* state,
+                  uint16_t* nq, uint8_t* nref, uint8_t* flags, float eps, float relax, float min_step, float max_step, int refine_steps,
+                  int64_t n_max, float* pts, void* stream) {
+    if (N < 0 || n_max < 0 || rays_per_view < 1 || !(eps > 0.f) || !(relax > 0.f) || !(min_step > 0.f) || !(max_step >= min_step) ||
+        refine_steps < 1 || refine_steps > 255)
+        return DH_ERR_BAD_ARG;
+    if (N >= (1ll << 31) || n_max >= (1ll << 31)) return DH_ERR_UNSUPPORTED;
+    if (n_max == 0 || N == 0) return DH_OK;
+    if (!idx || !s || !o || !d || !t || !t_far || !t_lo || !s_lo || !t_hi || !s_hi || !state || !nq || !nref || !flags || !pts)
+        return DH_ERR_BAD_ARG;
+    return launch_trace_step(idx, count, s, o, d, rays_per_view, N, t, t_far, t_lo, s_lo, t_hi, s_hi, state, nq, nref, flags, eps, relax,
+                             min_step, max_step, refine_steps, n_max, pts, static_cast<hipStream_t>(stream));
+}
+
+int dh_trace_points(const int32_t* idx, const float* o, const float* d, const float* t, int64_t rays_per_view, int64_t N, int64_t n,
+                    float* pts, void* stream) {
+    if (N < 0 || n < 0 || rays_per_view < 1) return DH_ERR_BAD_ARG;
+    if (N >= (1ll << 31) || n >= (1ll << 31)) return DH_ERR_UNSUPPORTED;
+    if (n == 0 || N == 0) return DH_OK;
+    if (!idx || !o || !d || !t || !pts) return DH_ERR_BAD_ARG;
+    return launch_trace_points(idx, o, d, t, rays_per_view, N, n, pts, static_cast<hipStream_t>(stream));
+}
+
+int dh_trace_compact(const int32_t* idx, const int32_t* count, const uint8_t* state, const float* o, const float* d, const float* t,
+                     int64_t rays_per_view, int64_t N, int64_t n_max, int32_t* ws, int32_t* idx_out, int32_t* count_out,
+                     float* pts_out, void* stream) {
+    if (N < 0 || n_max < 0 || rays_per_view < 1 || !count_out || count_out == count) return DH_ERR_BAD_ARG;
+    if (N >= (1ll << 31) || n_max >= (1ll << 31)) return DH_ERR_UNSUPPORTED;
+    if (n_max > 0 && (!state || !o || !d || !t || !ws || !idx_out || !pts_out || idx_out == idx)) return DH_ERR_BAD_ARG;
+    return launch_trace_compact(idx, count, state, o, d, t, rays_per_view, N, n_max, ws, idx_out, count_out, pts_out,
+                                static_cast<hipStream_t>(stream));
+}
+
+int dh_trace_compose(const uint8_t* state, const float* t, const float* d, const int32_t* slot, const float* normals,
+                     const float* colors, int64_t n_hits, const float* R, int n_views, int H, int W, int level, int background,
+                     const uint8_t* frame_rgb, const int32_t* frame_idx, int n_frames, uint8_t* rgb, float* depth, uint8_t* normal,
+                     uint8_t* hit, void* stream) {
+    int64_t h, w, N;
+    if (!trace_dims(n_views, H, W, level, h, w, N) || n_hits < 0 || background < 0 || background > 2 || n_frames < 0)
+        return DH_ERR_BAD_ARG;
+    if (N >= (1ll << 31) || n_hits >= (1ll << 31)) return DH_ERR_UNSUPPORTED;
+    if (N == 0) return DH_OK;
+    if (!state || !t || !d || !slot || !R || !rgb || !depth || !normal || !hit) return DH_ERR_BAD_ARG;
+    if (n_hits > 0 && (!normals || !colors)) return DH_ERR_BAD_ARG;
+    if (background == 2 && (!frame_rgb || !frame_idx || n_frames < 1)) return DH_ERR_BAD_ARG;
+    return launch_trace_compose(state, t, d, slot, normals, colors, n_hits, R, (int)h, (int)w, level, H, W, background, frame_rgb,
+                                frame_idx, n_frames, N, rgb, depth, normal, hit, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -104,6 +104,22 @@ int launch_march_count(const float* o, const float* d, const float* near, const 
 int launch_march_emit(const float* o, const float* d, const float* near, const float* far, const float* u, const uint8_t* occ,
                       int res, float radius, float step, float half_step, int max_samples, int64_t B, const int64_t* off,
                       const int32_t* keep, float* t_start, float* pts, float* dirs_pts, int32_t* ray_idx, hipStream_t st);
+// sphere tracing of the SDF (trace.hip): rays of F poses, one state-machine step, order-preserving compaction, image buffers
+int launch_trace_init(const float* R, const float* T, const float* Kinv, int h, int w, int level, float bound, int64_t N, float* o,
+                      float* d, float* t, float* t_far, uint8_t* state, hipStream_t st);
+int launch_trace_step(const int32_t* idx, const int32_t* count, const float* s, const float* o, const float* d, int64_t rays_per_view,
+                      int64_t N, float* t, const float* t_far, float* t_lo, float* s_lo, float* t_hi, float* s_hi, uint8_t* state,
+                      uint16_t* nq, uint8_t* nref, uint8_t* flags, float eps, float relax, float min_step, float max_step,
+                      int refine_steps, int64_t n_max, float* pts, hipStream_t st);
+int launch_trace_points(const int32_t* idx, const float* o, const float* d, const float* t, int64_t rays_per_view, int64_t N, int64_t n,
+                        float* pts, hipStream_t st);
+int launch_trace_compact(const int32_t* idx, const int32_t* count, const uint8_t* state, const float* o, const float* d, const float* t,
+                         int64_t rays_per_view, int64_t N, int64_t n_max, int32_t* block_off, int32_t* idx_out, int32_t* count_out,
+                         float* pts_out, hipStream_t st);
+int launch_trace_compose(const uint8_t* state, const float* t, const float* d, const int32_t* slot, const float* normals,
+                         const float* colors, int64_t n_hits, const float* R, int h, int w, int level, int H, int W, int background,
+                         const uint8_t* frame_rgb, const int32_t* frame_idx, int n_frames, int64_t N, uint8_t* rgb, float* depth,
+                         uint8_t* normal, uint8_t* hit, hipStream_t st);
 int launch_loss(const float* color, const float* wsum, const float* nmap, const float* eik, const float* rays,
                 const float* R, int64_t B, float igr_w, float mask_w, float normal_w, float* stats, float* d_color,
                 float* d_wsum, float* d_nmap, float* eik_coef, hipStream_t st);

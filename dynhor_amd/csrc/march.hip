@@ -11,18 +11,13 @@
 // Positions and cell indices use separately rounded fp32 operations in the order the oracle's tensor expressions evaluate, so
 // the two select exactly the same cells and produce bit-identical interval starts.  HIP's __fmul_rn / __fadd_rn are plain
 // operators that hipcc contracts into fma (also under `#pragma clang fp contract(off)` once inlined): the multiplies go
-// through a one-instruction asm, which nothing can fuse.
+// through a one-instruction asm, which nothing can fuse (mul_rn.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "mul_rn.h"
 
 namespace dh {
-
-__device__ __forceinline__ float mul_rn(float a, float b) {
-    float r;
-    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 
 struct MarchRay {
     float o[3], d[3], near, far, u;

@@ -13,6 +13,10 @@
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode refine_poses --is_continue --pose_frames worst:5   # silhouette fit
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode export_poses --is_continue    # obj_infos/<stem>.npz of the poses
     python -m dynhor_amd.run --config_path X.yaml --mode init_poses --vis_mesh template.obj --vis_normalize reference   # poses from masks
+    python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode render_views --is_continue   # every frame sphere-traced: png, normal, depth, PSNR, IoU
+    python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode render_views --is_continue --views orbit:36 --view_level 2
+    python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode interpolate_0_38 --is_continue   # upstream's video: volume rendering, level 2
+    python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode interpolate_0_38 --is_continue --view_method surface
 
 With --gpus N > 1 this process starts N ranks (one per GPU) through dynhor_amd.launch before it touches the GPU and exits
 with their code; under an external `torch.distributed.run` (WORLD_SIZE set) it is one of the ranks.
@@ -22,12 +26,22 @@ import os
 import sys
 
 
+MODES = ("train", "validate_image", "validate_mesh", "evaluate_mesh", "visualize_mesh", "refine_poses", "export_poses", "init_poses",
+         "render_views")
+
+
+def mode_arg(value: str) -> str:
+    """--mode: one of MODES, or upstream's interpolate_<i>_<j> (two frame indices)."""
+    import re
+    if value in MODES or re.fullmatch(r"interpolate_\d+_\d+", value):
+        return value
+    raise argparse.ArgumentTypeError(f"invalid choice: {value!r} (choose from {', '.join(MODES)}, interpolate_<i>_<j>)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config_path", type=str, required=True)
-    ap.add_argument("--mode", type=str, default="train",
-                    choices=["train", "validate_image", "validate_mesh", "evaluate_mesh", "visualize_mesh", "refine_poses",
-                             "export_poses", "init_poses"])
+    ap.add_argument("--mode", type=mode_arg, default="train", metavar="{" + ",".join(MODES) + ",interpolate_<i>_<j>}")
     ap.add_argument("--is_continue", action="store_true")
     ap.add_argument("--iters", type=int, default=None)
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks on this node (one process per GPU)")
@@ -79,6 +93,13 @@ def main():
     ap.add_argument("--pose_frames", type=str, default=None,
                     help="refine_poses: the frames that move: all (default), worst:N (the N lowest silhouette IoUs) or stems a,b,c")
     ap.add_argument("--pose_dir", type=str, default=None, help="export_poses: write the .npz files here (default <exp>/poses/<iter>/obj_infos)")
+    # render_views / interpolate_<i>_<j> (defaults: the config's surface_render: block)
+    ap.add_argument("--views", type=str, default="frames", help="render_views: frames | interpolate:i:j:n | orbit:n")
+    ap.add_argument("--view_level", type=int, default=None, help="render_views: pixel stride of the pictures")
+    ap.add_argument("--view_method", type=str, default=None, choices=["surface", "volume"],
+                    help="render_views: sphere-trace the SDF (colour, depth and normal maps) or volume-render (interpolate_<i>_<j>: "
+                         "volume unless given)")
+    ap.add_argument("--view_background", type=str, default=None, choices=["white", "black", "frame"])
     args = ap.parse_args()
 
     from . import launch
@@ -139,6 +160,19 @@ def main():
         if runner.rank == 0:
             import json
             print(json.dumps({k: v for k, v in res.items() if k not in ("frames", "refine")}), flush=True)
+    elif args.mode == "render_views" or args.mode.startswith("interpolate_"):
+        if args.mode == "render_views":
+            views, level, method = args.views, args.view_level, args.view_method
+        else:       # upstream's spelling: 60 poses there and back at half resolution, volume-rendered unless --view_method says otherwise
+            _, i, j = args.mode.split("_")
+            views = f"interpolate:{int(i)}:{int(j)}:60"
+            level = 2 if args.view_level is None else args.view_level
+            method = "volume" if args.view_method is None else args.view_method
+        res = runner.render_views(views=views, level=level, method=method, background=args.view_background)
+        if runner.rank == 0:
+            import json
+            print(json.dumps({k: v for k, v in res.items() if k not in ("rgb", "depth", "normal", "hit", "names", "psnr", "iou")}),
+                  flush=True)
     elif args.mode == "export_poses":
         d = runner.export_poses(args.pose_dir)
         if runner.rank == 0:

@@ -70,6 +70,12 @@ MESH_CLEAN_DEFAULTS = {"mode": "none", "dilate_px": 2, "min_bg_votes": 1, "min_a
 # the optional mesh_color: block of the YAML (validate_mesh; dynhor_amd/mesh_color.py)
 MESH_COLOR_DEFAULTS = {"mode": "none", "erode_px": 1, "min_cos": 0.1, "depth_eps": 0.01}
 
+# the optional surface_render: block of the YAML (render_views; dynhor_amd/surface_render.py): method surface | volume, level = the
+# pixel stride, background white | black | frame, and the tracer's parameters (surface_render.TRACE_DEFAULTS; compact_every stays 1
+# until the two settings have been timed on a GPU: DESIGN_NEXT_ROWS.md section 17)
+SURFACE_RENDER_DEFAULTS = {"method": "surface", "level": 1, "background": "white", "eps": 2e-4, "relax": 0.8, "min_step": 1e-3,
+                           "max_step": 0.1, "refine_steps": 8, "max_steps": 48, "scan_step": 0.01, "compact_every": 1}
+
 # the optional mesh_texture: block of the YAML (validate_mesh; dynhor_amd/mesh_texture.py): mode none | views | views+network, size = the
 # atlas edge in texels; erode_px / min_cos / depth_eps as in mesh_color; sharpen: the weight is cos^(2^sharpen); image: png | jpg
 MESH_TEXTURE_DEFAULTS = {"mode": "none", "size": 1024, "erode_px": 1, "min_cos": 0.1, "depth_eps": 0.01, "sharpen": 2, "image": "png"}
@@ -191,6 +197,7 @@ class Runner:
         self.last_extract_stats = None   # validate_mesh / evaluate_mesh / visualize_mesh with sparse extraction: its counts
         self.last_vis_dir = None         # visualize_mesh: the render_res/<iter> directory it wrote
         self.last_pose_dir = None        # refine_poses_silhouette / export_poses: the directory the .npz files went to
+        self.last_view_dir = None        # render_views: the novel_views/<iter> directory it wrote
         if is_continue:
             ck_dir = os.path.join(self.base_exp_dir, "checkpoints")
             ck = sorted(f for f in os.listdir(ck_dir) if f.endswith(".pth")) if os.path.isdir(ck_dir) else []
@@ -821,6 +828,150 @@ class Runner:
                     self._board.add_scalar("vis/" + k, float(res[k]), self.iter_step)
             self._board.flush()
         return res
+
+    # ------------------------------------------------------------------ novel views, depth and normal maps (surface_render.py)
+    def _surface_conf(self, method=None, level=None, background=None):
+        """The YAML's optional surface_render: block over SURFACE_RENDER_DEFAULTS; arguments that are not None override it."""
+        from .surface_render import BACKGROUNDS
+        c = dict(SURFACE_RENDER_DEFAULTS)
+        c.update(self.conf.get("surface_render") or {})
+        for k, v in (("method", method), ("level", level), ("background", background)):
+            if v is not None:
+                c[k] = v
+        unknown = set(c) - set(SURFACE_RENDER_DEFAULTS)
+        if unknown:
+            raise ValueError(f"surface_render: unknown keys {sorted(unknown)}")
+        if c["method"] not in ("surface", "volume"):
+            raise ValueError(f"surface_render method must be 'surface' or 'volume', got {c['method']!r}")
+        if c["background"] not in BACKGROUNDS:
+            raise ValueError(f"surface_render background must be one of {BACKGROUNDS}, got {c['background']!r}")
+        if isinstance(c["level"], bool) or not isinstance(c["level"], int) or c["level"] < 1:
+            raise ValueError(f"surface_render level must be an integer >= 1, got {c['level']!r}")
+        if c["method"] == "volume" and c["background"] == "frame":
+            raise ValueError("surface_render: method 'volume' has no hit mask to lay over a frame; use background 'white' or 'black'")
+        return c
+
+    @torch.no_grad()
+    def _render_views_volume(self, R, T, level, background, chunk=4096):
+        """The views by renderer.render_rays on surface_render.volume_rays: (rgb u8 [V,h,w,3], normal u8 [V,h,w,3])."""
+        from .surface_render import volume_rays
+        ds = self.dataset
+        bg = torch.ones(3, device=self.device) if background == "white" else None
+        rgbs, nrms = [], []
+        for v in range(R.shape[0]):
+            o, d, near, far, h, w = volume_rays(R[v:v + 1], T[v:v + 1], ds.K, ds.H, ds.W, level)
+            cols, ns = [], []
+            for s in range(0, o.shape[0], chunk):
+                c, nm = self.renderer.render_rays(o[s:s + chunk].contiguous(), d[s:s + chunk].contiguous(), near[s:s + chunk],
+                                                  far[s:s + chunk], self.get_cos_anneal_ratio(), bg)
+                cols.append(c); ns.append(nm)
+            img, nrm = torch.cat(cols).view(h, w, 3), torch.cat(ns).view(h, w, 3)
+            n_cam = nrm @ R[v].T
+            nimg = ((n_cam / (n_cam.norm(dim=-1, keepdim=True) + 1e-6)) * 0.5 + 0.5).clamp(0, 1)
+            rgbs.append((img.clamp(0, 1) * 255.0).round().to(torch.uint8)); nrms.append((nimg * 255).byte())
+        return torch.stack(rgbs), torch.stack(nrms)
+
+    @torch.no_grad()
+    def render_views(self, views="frames", level=None, method=None, background=None, save=True):
+        """Pictures of the networks themselves from any pose (dynhor_amd/surface_render.py): views "frames" (every training frame at its
+        current pose), "interpolate:i:j:n" (n poses from frame i to frame j and back, upstream's interpolate_<i>_<j> video) or "orbit:n"
+        (frame 0's pose with the object turned about its z axis).  method "surface" sphere-traces the SDF (render_surface: colour, depth
+        and normal maps, hit mask); "volume" draws the same views with render_rays (no depth map, no hit mask; the yardstick of the
+        timing).  level = pixel stride; background white | black | frame (the view's own frame behind the object: "frames" only).
+        Arguments left at None take the YAML's optional surface_render: block over SURFACE_RENDER_DEFAULTS.
+        Rank 0 writes novel_views/<iter:08d>/<name>.png, <name>_normal.png, <name>_depth.npy (surface only), views.gif (100 ms per
+        view, looping) and views.json, and returns its content plus `dir` and the images on the host: `rgb` u8 [V,h,w,3], `normal`
+        and, for method surface, `depth` and `hit` (the other ranks return None).  Views are drawn, scored and written in chunks of at
+        most surface_render.MAX_RAYS rays, so the device never holds more than a chunk's images and ground truth.  For "frames" views.json holds per-frame PSNR (validate_image's mask and formula) and, for method surface, the IoU of the
+        hit mask against label > 0 with hand pixels excluded (the rule of vis/iou_*), their means and the five worst frames; view/psnr
+        and view/iou are logged to <exp>/board."""
+        from . import surface_render as sr
+        if self.rank != 0:
+            return None
+        ds = self.dataset
+        c = self._surface_conf(method, level, background)
+        spec = sr.parse_views(views, ds.n_images)
+        if c["background"] == "frame" and spec[0] != "frames":
+            raise ValueError("render_views: background 'frame' needs views 'frames' (another pose has no frame of its own)")
+        names, R64, T64, frame_of = sr.view_poses(spec, ds.R, ds.T)
+        if spec[0] == "frames" and ds.stems is not None:
+            names = list(ds.stems)
+        R = R64.to(self.device, torch.float32).contiguous()
+        T = T64.to(self.device, torch.float32).contiguous()
+        L = int(c["level"])
+        res = {"iter": self.iter_step, "views": views, "method": c["method"], "level": L, "background": c["background"], "names": names}
+        surface = c["method"] == "surface"
+        score = spec[0] == "frames"
+        d = os.path.join(self.base_exp_dir, "novel_views", "{:0>8d}".format(self.iter_step))
+        if save:
+            from PIL import Image
+            os.makedirs(d, exist_ok=True)
+        h, w = sr.image_size(ds.H, ds.W, L)
+        per = max(1, sr.MAX_RAYS // (h * w))                   # views per chunk: images, ground truth and scores never hold more
+        keys = ("rgb", "normal", "depth", "hit") if surface else ("rgb", "normal")
+        host = {k: [] for k in keys}
+        stats, psnr, iou = None, [], []
+        for v0 in range(0, R.shape[0], per):
+            v1 = min(R.shape[0], v0 + per)
+            if surface:
+                targs = {k: c[k] for k in sr.TRACE_DEFAULTS}
+                out = sr.render_surface(self.renderer, R[v0:v1], T[v0:v1], ds.K, ds.H, ds.W, level=L, background=c["background"],
+                                        frames=frame_of[v0:v1] if frame_of is not None else None,
+                                        frame_rgb=ds.rgb if c["background"] == "frame" else None, **targs)
+                stats = sr.merge_stats(stats, out["stats"])
+            else:
+                rgb, normal = self._render_views_volume(R[v0:v1], T[v0:v1], L, c["background"])
+                out = {"rgb": rgb, "normal": normal}
+            if score:
+                gt = ds.rgb[v0:v1, ::L, ::L].float() / 255.0
+                lab = ds.label[v0:v1, ::L, ::L]
+                m = (lab > 0).float()[..., None]
+                mse = (((out["rgb"].float() / 255.0 - gt) ** 2) * m).sum(dim=(1, 2, 3)) / (m.sum(dim=(1, 2, 3)) * 3.0 + 1e-5)
+                psnr += [float(p) for p in (20.0 * torch.log10(1.0 / mse.sqrt())).tolist()]
+                if surface:
+                    keep, obj, hb = lab >= 0, lab > 0, out["hit"] > 0
+                    inter = (hb & obj & keep).sum(dim=(1, 2)).double()
+                    union = ((hb | obj) & keep).sum(dim=(1, 2)).double()
+                    iou += [float(x) for x in torch.where(union > 0, inter / union.clamp(min=1), torch.ones_like(union)).tolist()]
+            chunk = {k: out[k].cpu() for k in keys}
+            for k in keys:
+                host[k].append(chunk[k])
+            if save:
+                for n in range(v1 - v0):
+                    name = names[v0 + n]
+                    Image.fromarray(chunk["rgb"][n].numpy()).save(os.path.join(d, name + ".png"))
+                    Image.fromarray(chunk["normal"][n].numpy()).save(os.path.join(d, name + "_normal.png"))
+                    if surface:
+                        np.save(os.path.join(d, name + "_depth.npy"), chunk["depth"][n].numpy())
+        host = {k: torch.cat(v) for k, v in host.items()}
+        if surface:
+            res["stats"] = stats
+        if score:
+            res["psnr"] = psnr
+            finite = [p for p in psnr if math.isfinite(p)]
+            res["psnr_mean"] = float(np.mean(finite)) if finite else None
+            order = sorted(range(len(psnr)), key=lambda k: psnr[k])
+            res["worst_psnr"] = [{"frame": names[k], "psnr": psnr[k]} for k in order[:5]]
+            if surface:
+                res["iou"] = iou
+                res["iou_mean"] = float(np.mean(iou))
+                order = sorted(range(len(iou)), key=lambda k: iou[k])
+                res["worst_iou"] = [{"frame": names[k], "iou": iou[k]} for k in order[:5]]
+        if save:
+            frames = [Image.fromarray(im) for im in host["rgb"].numpy()]
+            frames[0].save(os.path.join(d, "views.gif"), save_all=True, append_images=frames[1:], duration=100, loop=0)
+            with open(os.path.join(d, "views.json"), "w") as f:
+                json.dump(res, f, indent=1)
+            if score:
+                if self._board is None:
+                    from .tb_events import make_writer
+                    self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+                for k in ("psnr", "iou"):
+                    if res.get(k + "_mean") is not None:
+                        self._board.add_scalar("view/" + k, float(res[k + "_mean"]), self.iter_step)
+                self._board.flush()
+        self.last_view_dir = d if save else None
+        return dict(res, dir=self.last_view_dir, **host)
 
     # ------------------------------------------------------------------ poses out (the reference's hand-off format)
     def export_poses(self, dir=None):

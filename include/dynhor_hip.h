@@ -670,6 +670,56 @@ int dh_simplify_quadrics(const float* verts, int64_t nv, const int64_t* faces, i
 int dh_simplify_faces(const int64_t* faces, int64_t nf, const int32_t* vrank, int64_t nv, int64_t n_runs, int64_t* tri, uint8_t* keep,
                       int64_t* key, void* stream);
 
+/* ---- sphere tracing of the SDF: novel views, depth and normal maps (dynhor_amd/surface_render.py; csrc/trace.hip) --------------
+ * The network query is the caller's (dh_sdf_nograd / dh_hash_sdf_nograd, or any field); these entry points are the per-ray work
+ * around it.  All are stateless: the per-ray state lives in caller-owned arrays over the N = F h w rays of F views (ray index
+ * (view h + row) w + column; h = ceil(H / level), w = ceil(W / level), pixel (row level, column level) as Dataset.gen_rays_at):
+ *   o [F,3] (one origin per view), d [N,3], t [N] (the next query is o + t d), t_far [N], t_lo / s_lo / t_hi / s_hi [N] (the bracket:
+ *   last positive and first negative sample), state u8 [N] (dh_trace_state), nq u16 [N] (queries made), nref u8 [N] (REFINE steps
+ *   counted), flags u8 [N] (dh_trace_flag bits).  No float atomics anywhere: the same inputs give the same bits.
+ * dh_trace_init: rays of the poses R [F,9], T [F,3] (x_cam = R x_obj + T) with Kinv [9]; o and d are dh_gen_rays' expressions term for
+ *   term (bitwise equal at a dataset pose).  With b = o.d, disc = b^2 - (|o|^2 - bound^2), near, far = -b -+ sqrt(disc) (fp64 from the
+ *   fp32 o, d): t = max(near, 0), t_far = far, state MARCH; disc <= 0 or far <= 0: state MISS (t = t_far = 0 when disc <= 0).  The
+ *   other per-ray arrays are the caller's to zero.
+ * dh_trace_step: one step for the rays idx[0 .. min(*count, n_max)) (count: device, null = n_max), s[k] = sdf(o + t d) of ray idx[k].
+ *   A ray in state MARCH or REFINE:  s not finite -> FAIL;  |s| <= eps -> HIT at t;  MARCH, s < 0: nq == 0 -> HIT at t with flag
+ *   INSIDE, else t_hi = t, s_hi = s, REFINE, first secant point in the same step;  MARCH, s > eps: t_lo = t, s_lo = s, t' = t +
+ *   clamp(relax s, min_step, max_step), t' > t_far -> MISS else t = t';  REFINE: (t, s) replaces the bracket end of its sign, nref += 1,
+ *   nref >= refine_steps -> HIT at t with flag CAPPED, else t_hi - t_lo <= eps -> HIT at t, else the secant point.  Secant point:
+ *   t_lo + w s_lo / (s_lo - s_hi), w = t_hi - t_lo, clamped to [t_lo + 0.1 w, t_hi - 0.1 w].  nq += 1 (saturating).  Every product is
+ *   rounded on its own (no fma).  A listed ray in any other state is left as it is.  pts [n_max,3]: pts[k] = fma(t, d, o) of ray idx[k]
+ *   after the step (the next query point, in list order).  List entries outside [0, N) are skipped.
+ * dh_trace_points: pts[k] = fma(t, d, o) of ray idx[k], k < n, whatever the ray's state: the point the tracer queried last (at a hit:
+ *   where it saw |s| <= eps), bit for bit.  List entries outside [0, N) are skipped.
+ * dh_trace_compact: the listed rays (idx null: 0 .. n_max-1) that are MARCH or REFINE, densely and in list order: idx_out, their
+ *   points pts_out = o + t d, *count_out (device) their number.  Per-block counts, one scan, emit; ws: int32 [ceil(n_max / 256)].
+ *   idx_out must not be idx, count_out not count (the emit reads both again).  n_max == 0 writes *count_out = 0.
+ * dh_trace_compose: the image buffers of the N rays.  A ray is drawn as a hit iff state == HIT and 0 <= slot[ray] < n_hits; normals /
+ *   colors [n_hits,3] are the network's at the hit points (object frame; colour in [0, 1]).  rgb u8 [N,3] = round(255 clamp(colour)) over
+ *   the background: 0 white, 1 black, 2 the pixel of frame frame_idx[view] of frame_rgb u8 [n_frames,H,W,3] (black for an index outside it);  depth f32 [N] = t (R d)_z,
+ *   the camera z of the hit, +inf elsewhere;  normal u8 [N,3] = trunc(255 clamp(0.5 n_cam / (|n_cam| + 1e-6) + 0.5)), n_cam = R n (127
+ *   elsewhere);  hit u8 [N].
+ * N == 0 / n_max == 0: no-op (dh_trace_compact still writes the count).  DH_ERR_BAD_ARG: null pointer, negative count, H, W, h, w or
+ * level < 1, bound, eps, min_step not > 0, max_step < min_step, relax not > 0, refine_steps outside [1, 255], background outside
+ * 0 .. 2 (or 2 without frames), idx_out == idx, count_out == count.  DH_ERR_UNSUPPORTED: N or n_max >= 2^31. */
+enum dh_trace_state { DH_TRACE_MARCH = 0, DH_TRACE_REFINE = 1, DH_TRACE_HIT = 2, DH_TRACE_MISS = 3, DH_TRACE_FAIL = 4 };
+enum dh_trace_flag { DH_TRACE_INSIDE = 1, DH_TRACE_CAPPED = 2, DH_TRACE_SCANNED = 4 /* set by the caller's chord scan */ };
+int dh_trace_init(const float* R, const float* T, const float* Kinv, int n_views, int H, int W, int level, float bound, float* o,
+                  float* d, float* t, float* t_far, uint8_t* state, void* stream);
+int dh_trace_step(const int32_t* idx, const int32_t* count, const float* s, const float* o, const float* d, int64_t rays_per_view,
+                  int64_t N, float* t, const float* t_far, float* t_lo, float* s_lo, float* t_hi, float* s_hi, uint8_t* state,
+                  uint16_t* nq, uint8_t* nref, uint8_t* flags, float eps, float relax, float min_step, float max_step, int refine_steps,
+                  int64_t n_max, float* pts, void* stream);
+int dh_trace_points(const int32_t* idx, const float* o, const float* d, const float* t, int64_t rays_per_view, int64_t N, int64_t n,
+                    float* pts, void* stream);
+int dh_trace_compact(const int32_t* idx, const int32_t* count, const uint8_t* state, const float* o, const float* d, const float* t,
+                     int64_t rays_per_view, int64_t N, int64_t n_max, int32_t* ws, int32_t* idx_out, int32_t* count_out,
+                     float* pts_out, void* stream);
+int dh_trace_compose(const uint8_t* state, const float* t, const float* d, const int32_t* slot, const float* normals,
+                     const float* colors, int64_t n_hits, const float* R, int n_views, int H, int W, int level, int background,
+                     const uint8_t* frame_rgb, const int32_t* frame_idx, int n_frames, uint8_t* rgb, float* depth, uint8_t* normal,
+                     uint8_t* hit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
