@@ -92,6 +92,10 @@ SIGNATURES = {
     "dh_corr_loss": (_i32, [_vp] * 7 + [_i32, _vp, _i64, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "dh_nearest_sqdist_workspace": (_i64, [_i64, _i64]),
     "dh_nearest_sqdist": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "dh_mesh_sdf_record_floats": (_i32, []),
+    "dh_mesh_sdf_prepare": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    "dh_mesh_sdf_query_workspace": (_i64, [_i64, _i64]),
+    "dh_mesh_sdf_query": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "dh_icp_correspond_workspace": (_i64, [_i64, _i64, _i64]),
     "dh_icp_correspond": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "dh_icp_moments_sums": (_i32, [_i32]),

@@ -578,6 +578,33 @@ int dh_nearest_sqdist(const float* q, int64_t nq, const float* ref, int64_t nr, 
     return launch_nearest_sqdist(q, nq, ref, nr, d2, idx, ws, static_cast<hipStream_t>(stream));
 }
 
+int dh_mesh_sdf_record_floats(void) { return mesh_sdf_record_floats(); }
+
+int dh_mesh_sdf_prepare(const float* verts, int64_t nv, const int32_t* faces, int64_t nf, float* rec, void* stream) {
+    if (nv < 0 || nf < 0) return DH_ERR_BAD_ARG;
+    if (nf >= ((int64_t)1 << 31) || nv >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;     // indices are int32
+    if (nf == 0) return DH_OK;
+    if (!faces || !rec || (!verts && nv > 0) || misaligned16(rec)) return DH_ERR_BAD_ARG;
+    return launch_mesh_sdf_prepare(verts, nv, faces, nf, rec, static_cast<hipStream_t>(stream));
+}
+
+int64_t dh_mesh_sdf_query_workspace(int64_t n, int64_t nf) {
+    if (n < 0 || nf < 0) return DH_ERR_BAD_ARG;
+    if (nf >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;
+    return mesh_sdf_query_workspace(n, nf);
+}
+
+int dh_mesh_sdf_query(const float* rec, int64_t nf, const float* pts, int64_t n, float* sqdist, int32_t* face, float* wind, void* ws,
+                      void* stream) {
+    if (n < 0 || nf < 0) return DH_ERR_BAD_ARG;
+    if (nf >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;      // face indices are int32; grid.x
+    if (n == 0) return DH_OK;
+    if (nf == 0 || !rec || !pts || !sqdist || misaligned16(rec) || misaligned16(ws)) return DH_ERR_BAD_ARG;
+    if (nf > mesh_sdf_max_faces()) return DH_ERR_UNSUPPORTED;                                 // one slab per grid.y index
+    if (!ws && mesh_sdf_query_workspace(n, nf) > 0) return DH_ERR_BAD_ARG;                    // more than one slab needs the scratch
+    return launch_mesh_sdf_query(rec, nf, pts, n, sqdist, face, wind, ws, static_cast<hipStream_t>(stream));
+}
+
 // shared limits of the ICP entry points: the grid's y / z dimensions carry slabs and hypotheses (65535 each), indices are int32
 static int icp_args(int64_t n, int64_t m, int64_t h) {
     if (n < 0 || m < 0 || h < 0) return DH_ERR_BAD_ARG;

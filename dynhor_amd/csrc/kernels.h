@@ -180,6 +180,15 @@ int launch_hash_weight_grads(const float* params, const float* hp, int64_t n, fl
 int64_t nearest_sqdist_workspace(int64_t nq, int64_t nr);
 int launch_nearest_sqdist(const float* q, int64_t nq, const float* ref, int64_t nr, float* d2, int32_t* idx, void* ws, hipStream_t st);
 
+// signed distance to a triangle mesh (mesh_sdf.hip): one record of mesh_sdf_record_floats() floats per face, then the brute-force query;
+// ws = mesh_sdf_query_workspace(n, nf) bytes (0: one slab, ws unused); mesh_sdf_max_faces(): the slabs must fit grid.y
+int mesh_sdf_record_floats();
+int64_t mesh_sdf_query_workspace(int64_t n, int64_t nf);
+int64_t mesh_sdf_max_faces();
+int launch_mesh_sdf_prepare(const float* verts, int64_t nv, const int32_t* faces, int64_t nf, float* rec, hipStream_t st);
+int launch_mesh_sdf_query(const float* rec, int64_t nf, const float* pts, int64_t n, float* sqdist, int32_t* face, float* wind, void* ws,
+                          hipStream_t st);
+
 // similarity ICP (dynhor_amd/mesh_align.py).  Correspondences (nn.hip): the sweep of launch_nearest_sqdist for h hypotheses at once,
 // the source transformed on load by xf [h,12]; ws = icp_correspond_workspace(n, m, h) bytes, or null (one slab).  Moment sums of the
 // pairs inside the trim threshold (icp.hip): icp_moments_sums(plane) doubles per hypothesis, ws = icp_moments_workspace(n, h, plane) bytes

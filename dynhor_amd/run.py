@@ -13,6 +13,8 @@
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode refine_poses --is_continue --pose_frames worst:5   # silhouette fit
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode export_poses --is_continue    # obj_infos/<stem>.npz of the poses
     python -m dynhor_amd.run --config_path X.yaml --mode init_poses --vis_mesh template.obj --vis_normalize reference   # poses from masks
+    python -m dynhor_amd.run --config_path X.yaml --mode init_sdf --vis_mesh template.obj --vis_normalize reference     # SDF warm start
+    python -m dynhor_amd.run --config_path X.yaml --mode init_sdf --mesh_simplify faces:5000   # template: data_info.obj_path, simplified
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode render_views --is_continue   # every frame sphere-traced: png, normal, depth, PSNR, IoU
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode render_views --is_continue --views orbit:36 --view_level 2
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode interpolate_0_38 --is_continue   # upstream's video: volume rendering, level 2
@@ -27,7 +29,7 @@ import sys
 
 
 MODES = ("train", "validate_image", "validate_mesh", "evaluate_mesh", "visualize_mesh", "refine_poses", "export_poses", "init_poses",
-         "render_views")
+         "init_sdf", "render_views")
 
 
 def mode_arg(value: str) -> str:
@@ -71,8 +73,8 @@ def main():
                     help="validate_mesh: colour the mesh and also write <iter>_color.ply; visualize_mesh: shade with the vertex colours "
                          "(default: the config's mesh_color.mode, else none)")
     ap.add_argument("--mesh_simplify", type=str, default=None,
-                    help="validate_mesh / evaluate_mesh / visualize_mesh / refine_poses: none | cells:N | faces:T -- simplify the "
-                         "(cleaned) mesh by quadric vertex clustering on N cells along its longest axis, or to at most T faces; "
+                    help="validate_mesh / evaluate_mesh / visualize_mesh / refine_poses / init_sdf: none | cells:N | faces:T -- simplify "
+                         "the (cleaned) mesh, or init_sdf's template, by quadric vertex clustering on N cells along its longest axis, or to at most T faces; "
                          "validate_mesh also writes <iter>_simple.ply (default: the config's mesh_simplify.mode, else none)")
     ap.add_argument("--mesh_texture", type=str, default=None, choices=["none", "views", "views+network"],
                     help="validate_mesh: bake a texture atlas for the (cleaned, simplified) mesh from the frames and also write "
@@ -84,7 +86,7 @@ def main():
     # visualize_mesh only (defaults: the config's mesh_vis: block, else the reconstruction at --mesh_resolution, no turntable)
     ap.add_argument("--vis_mesh", type=str, default=None,
                     help="visualize_mesh: draw this mesh (.ply / .obj; an .obj with a texture is drawn with it) instead of the "
-                         "reconstruction; refine_poses: fit the poses to it; init_poses: the template (default: the config's "
+                         "reconstruction; refine_poses: fit the poses to it; init_poses / init_sdf: the template (default: the config's "
                          "data_info.obj_path with normalize_mesh)")
     ap.add_argument("--vis_normalize", type=str, default=None, choices=["none", "reference"],
                     help="visualize_mesh: 'reference' = bring --vis_mesh into the canonical frame (mean 0, max vertex norm 0.5)")
@@ -160,6 +162,12 @@ def main():
         if runner.rank == 0:
             import json
             print(json.dumps({k: v for k, v in res.items() if k not in ("frames", "refine")}), flush=True)
+    elif args.mode == "init_sdf":
+        res = runner.init_sdf(mesh=args.vis_mesh, normalize=args.vis_normalize, simplify_mode=args.mesh_simplify)
+        runner.close()
+        if runner.rank == 0:
+            import json
+            print(json.dumps({k: v for k, v in res.items() if k != "loss"}), flush=True)
     elif args.mode == "render_views" or args.mode.startswith("interpolate_"):
         if args.mode == "render_views":
             views, level, method = args.views, args.view_level, args.view_method

@@ -397,6 +397,33 @@ int dh_hash_set_scatter_mode(int mode);
 int64_t dh_nearest_sqdist_workspace(int64_t nq, int64_t nr);
 int dh_nearest_sqdist(const float* q, int64_t nq, const float* ref, int64_t nr, float* d2, int32_t* idx, void* ws, void* stream);
 
+/* ---- signed distance to a triangle mesh (dynhor_amd/mesh_sdf.py: the template prior of the SDF warm start, sdf_init.py) -----------
+ * dh_mesh_sdf_prepare: verts [nv,3] fp32, faces [nf,3] int32 -> rec, one record of dh_mesh_sdf_record_floats() (12) floats per face
+ * (caller-owned, 16-byte aligned): corner a and |e0|^2, e0 = b - a and e0.e1, e1 = c - a and |e1|^2, whose sign bit marks a face that
+ * adds exactly 0 to the winding sum.  A face with an index outside [0, nv) or a non-finite corner becomes a record that is never the
+ * nearest face and adds 0 to the winding sum.  A zero-area face (the fp32 cross product of its edges is exactly zero: a repeated
+ * corner always is) is kept as the segment, or point, between its two corners farthest apart: it counts for the distance and adds
+ * exactly 0 to the winding sum; it never yields a NaN.  nf == 0: no-op.
+ * dh_mesh_sdf_query: for each of n points pts [n,3] fp32:
+ *   sqdist[i] = the squared distance to the closest point of any triangle (closest point by the corner / edge / interior regions,
+ *               chosen with selects; the distance itself in the difference form |(p - a) - v e0 - w e1|^2, never an expanded one);
+ *   face[i]   = the lowest face index that attains it (face may be NULL);
+ *   wind[i]   = the generalised winding number sum_f omega_f(p) / 4 pi, omega = 2 atan2(a.(b x c), |a||b||c| + (a.b)|c| + (b.c)|a| +
+ *               (c.a)|b|) with a, b, c = corners - p in fp32, added in fp64 in ascending face order (wind may be NULL).
+ * A non-finite point gets sqdist = +inf, face = -1, wind = 0.  n == 0: no-op.
+ * The face range is swept in slabs of a fixed number of faces, so the slab boundaries depend on nf alone: all three outputs are the
+ * same bits from launch to launch and however the points are chunked over launches (no atomics, no cross-lane operation).
+ * ws: caller-owned scratch of dh_mesh_sdf_query_workspace(n, nf) bytes (16-byte aligned), required when that is not 0 (more than one
+ * slab); the slabs' (sqdist, face) pairs merge lexicographically and their fp64 winding partials add, both in slab order.
+ * DH_ERR_BAD_ARG: null pointer, negative count, misaligned rec / ws, nf == 0 with n > 0, ws NULL where scratch is needed.
+ * DH_ERR_UNSUPPORTED: nf >= 2^31, nv >= 2^31 or n >= 2^31; more than 65535 slabs (nf > 33,553,920).  The cost is n x nf pairs: simplify a
+ * template beyond about 10^5 faces first (dynhor_amd/mesh_simplify.py). */
+int dh_mesh_sdf_record_floats(void);
+int dh_mesh_sdf_prepare(const float* verts, int64_t nv, const int32_t* faces, int64_t nf, float* rec, void* stream);
+int64_t dh_mesh_sdf_query_workspace(int64_t n, int64_t nf);
+int dh_mesh_sdf_query(const float* rec, int64_t nf, const float* pts, int64_t n, float* sqdist, int32_t* face, float* wind, void* ws,
+                      void* stream);
+
 /* ---- similarity ICP (dynhor_amd/mesh_align.py: the ground-truth mesh registered to the reconstruction before it is scored) -------
  * dh_icp_correspond: dh_nearest_sqdist for H hypotheses at once, the query transformed on load.  xf [H,12] fp32: A row-major (9), then
  * t (3).  For source point p = src[i] and hypothesis h the query is, for every row r, x_r = fma(A_r2, p.z, fma(A_r1, p.y,
