@@ -212,7 +212,7 @@ int dh_weight_grads_gemm_ex(int arithmetic, int64_t npts, float* ws, void* strea
     if (npts <= 0 || bad_arith(arithmetic)) return DH_ERR_BAD_ARG;
     if (!ws || misaligned16(ws)) return DH_ERR_BAD_ARG;
     const Workspace w = carve_workspace(ws, npts);
-    return launch_weight_grads_gemm(w, w.slabs, DW_G, arithmetic, static_cast<hipStream_t>(stream));
+    return launch_weight_grads_gemm(w, w.slabs, w.tred, DW_G, DW_NS, arithmetic, static_cast<hipStream_t>(stream));
 }
 
 int dh_weight_grads_fold(const float* packed, const float* params, int64_t npts, float* ws, float* grad_flat, void* stream) {

@@ -4,8 +4,9 @@
 // are saved "native" tiles (tile.h): a float4 at ((..m..t..)*4 + r4)*64 + lane IS four consecutive A (or B)
 // fragments of v_mfma_f32_32x32x2_f32 for the k-pairs {row, row+4} (and two consecutive ones the 8 k-values of one
 // v_mfma_f32_32x32x16_bf16 operand), so operands leave HBM as 1 KiB coalesced wave loads.  8 waves per workgroup,
-// split-K over tiles across gridDim.x persistent workgroups, slabs reduced in slab_reduce_kernel / fold_kernel
-// (deterministic: no float atomics).
+// split-K over tiles across gridDim.x persistent workgroups, slabs reduced and folded row by row in reduce_fold_kernel
+// (deterministic: no float atomics).  The tile partials (bias gradients and the two small linears) are reduced by the GEMM kernel's
+// own workgroups behind their jobs (dw_tpart_tail), so the stage is two launches.
 #include "tile16h.h"
 #include "kernels.h"
 #include "workspace.h"
@@ -26,7 +27,7 @@ struct DwJobs { DwJob j[16]; int n; };
 // the workgroups proportional to its MFMA cost; a workgroup of group k runs ONLY that group's jobs, over ntiles / (its group's
 // size) tiles.  Work per workgroup is unchanged (fewer jobs x more tiles) and still equal across workgroups, but a job now has
 // as many split-K slabs as its group has workgroups (~G / DW_GROUPS) instead of G: the slab traffic (0.84 GB written by this
-// kernel + read back by slab_reduce_kernel with one group) falls by that factor.  DW_GROUPS = 1 is the round-2 kernel.
+// kernel + read back by the reduction with one group) falls by that factor.  DW_GROUPS = 1 is the round-2 kernel.
 #ifndef DW_GROUPS
 #define DW_GROUPS 8
 #endif
@@ -655,9 +656,47 @@ __device__ __forceinline__ void dw_body_aux_h(const DwJob& J, const DwScales& sc
     }
 }
 
+// ---------------------------------------------------------------- per-tile partial sums -> tred[S][N_TILE_PART][256]
+// tred[s][slot][c] = sum of tpart[t][slot][c] over the tiles t of split s, [ntiles s / S, ntiles (s + 1) / S), added in tile order
+// (one fixed order per word: bitwise reproducible).  One WAVE per (s, slot) unit, a float4 of columns per lane, TP_BATCH 1 KiB loads
+// in flight before the dependent adds.  The units depend on nothing the GEMMs produce, so the persistent workgroups of the GEMM
+// kernels take them behind their jobs (unit = wave * G + g: five of a workgroup's eight waves at S = 64, G = 256), where the 84 MB
+// ride on the kernel's own HBM stream instead of a launch of their own in the serial tail behind it.
+constexpr int TP_BATCH = 16;
+__device__ __forceinline__ void tpart_unit(const float* __restrict__ tpart, int64_t ntiles, float* __restrict__ tred, int nS, int u,
+                                           int lane) {
+    const int slot = u % N_TILE_PART, s = u / N_TILE_PART;
+    const int64_t t0 = ntiles * s / nS, t1 = ntiles * (s + 1) / nS;
+    const f32x4* p = reinterpret_cast<const f32x4*>(tpart + slot * 256) + lane;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t t = t0; t < t1; t += TP_BATCH) {
+        f32x4 v[TP_BATCH];
+        DH_UNROLL for (int i = 0; i < TP_BATCH; ++i) {
+            v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (t + i < t1) v[i] = __builtin_nontemporal_load(p + (t + i) * (N_TILE_PART * 64));
+        }
+        DH_UNROLL for (int i = 0; i < TP_BATCH; ++i) if (t + i < t1) acc += v[i];
+    }
+    *(reinterpret_cast<f32x4*>(tred + ((int64_t)s * N_TILE_PART + slot) * 256) + lane) = acc;
+}
+struct TpartArgs { const float* tpart; float* tred; int nS; };
+__device__ __forceinline__ void dw_tpart_tail(const TpartArgs& tp, int64_t ntiles, int g, int G, int wave, int lane) {
+    for (int u = wave * G + g; u < tp.nS * N_TILE_PART; u += 8 * G) tpart_unit(tp.tpart, ntiles, tp.tred, tp.nS, u, lane);
+}
+#ifdef DW_TPART_FRONT
+// (development, scripts/build_variant.sh: the same units as a launch of their own in front of the GEMM kernel)
+__global__ __launch_bounds__(256) void tpart_reduce_kernel(TpartArgs tp, int64_t ntiles) {
+    const int u = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (u < tp.nS * N_TILE_PART) tpart_unit(tp.tpart, ntiles, tp.tred, tp.nS, u, threadIdx.x & 63);
+}
+#define DW_TPART_TAIL(tp, ntiles, g, G, wave, lane)
+#else
+#define DW_TPART_TAIL(tp, ntiles, g, G, wave, lane) dw_tpart_tail(tp, ntiles, g, G, wave, lane)
+#endif
+
 __global__ __launch_bounds__(512, 1) void dw_f16x2_kernel(DwJobs jobs, DwGroups groups, int64_t ntiles, float* __restrict__ slabs,
                                                           int64_t gstride, const unsigned* __restrict__ absmax,
-                                                          const unsigned* __restrict__ tmax) {
+                                                          const unsigned* __restrict__ tmax, TpartArgs tp) {
     // (sized for the aux jobs' three-piece image, below)
     __shared__ __attribute__((aligned(16))) char pieces[2 * (DWP_BUF > DWH_BUF ? DWP_BUF : DWH_BUF)];
     const int g = blockIdx.x;
@@ -674,10 +713,11 @@ __global__ __launch_bounds__(512, 1) void dw_f16x2_kernel(DwJobs jobs, DwGroups 
         if (J.nb == 8) dw_body_pieces_h<8>(J, sc, t0, t1, base + J.off, wave, lane, pieces);
         else dw_body_aux_h(J, sc, t0, t1, base + J.off, wave, lane, pieces);
     }
+    DW_TPART_TAIL(tp, ntiles, g, (int)gridDim.x, wave, lane);
 }
 
 __global__ __launch_bounds__(512, 1) void dw_bf16x3_kernel(DwJobs jobs, DwGroups groups, int64_t ntiles, float* __restrict__ slabs,
-                                                           int64_t gstride) {
+                                                           int64_t gstride, TpartArgs tp) {
     __shared__ __attribute__((aligned(16))) char pieces[2 * DWP_BUF];
     const int g = blockIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -689,10 +729,11 @@ __global__ __launch_bounds__(512, 1) void dw_bf16x3_kernel(DwJobs jobs, DwGroups
         if (J.nb == 8) dw_body_pieces<8>(J, t0, t1, base + J.off, wave, lane, pieces);
         else dw_body_pieces<2>(J, t0, t1, base + J.off, wave, lane, pieces);
     }
+    DW_TPART_TAIL(tp, ntiles, g, (int)gridDim.x, wave, lane);
 }
 
 __global__ __launch_bounds__(512, 2) void dw_lds_kernel(DwJobs jobs, DwGroups groups, int64_t ntiles, float* __restrict__ slabs,
-                                                        int64_t gstride) {
+                                                        int64_t gstride, TpartArgs tp) {
     __shared__ __attribute__((aligned(16))) char ring[DW_STAGES * DW_STAGE_BYTES];
     const int g = blockIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -704,38 +745,7 @@ __global__ __launch_bounds__(512, 2) void dw_lds_kernel(DwJobs jobs, DwGroups gr
         if (J.nb == 8) dw_body_lds<8>(J, t0, t1, base + J.off, wave, lane, ring);
         else dw_body_lds<2>(J, t0, t1, base + J.off, wave, lane, ring);
     }
-}
-
-// red[e] = sum over the workgroups of e's job group of slabs[g*gstride + e].  Eight independent partial sums (slab g goes to
-// partial (g - first) % 8, combined pairwise in a fixed order: deterministic) keep eight 16-B loads in flight per lane; the slabs
-// are read once: non-temporal.
-__global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ slabs, int64_t gstride, DwGroups groups,
-                                                          float* __restrict__ red) {
-    const int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (e >= gstride) return;
-    int kg = 0;
-    while (kg + 1 < groups.n && e >= groups.off0[kg + 1]) ++kg;
-    const int G = groups.wg0[kg + 1] - groups.wg0[kg];
-    f32x4 s[8];
-    DH_UNROLL for (int k = 0; k < 8; ++k) s[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float* p = slabs + e + (int64_t)groups.wg0[kg] * gstride;
-    int g = 0;
-    for (; g + 8 <= G; g += 8) {
-        f32x4 v[8];
-        DH_UNROLL for (int k = 0; k < 8; ++k) v[k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + (int64_t)(g + k) * gstride));
-        DH_UNROLL for (int k = 0; k < 8; ++k) s[k] += v[k];
-    }
-    for (; g < G; ++g) s[g & 7] += *reinterpret_cast<const f32x4*>(p + (int64_t)g * gstride);
-    *reinterpret_cast<f32x4*>(red + e) = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
-}
-
-// ---------------------------------------------------------------- per-tile partial sums -> [S][N_TILE_PART][256]
-__global__ __launch_bounds__(256) void tpart_reduce_kernel(const float* __restrict__ tpart, int64_t ntiles, float* __restrict__ tred) {
-    const int slot = blockIdx.x, s = blockIdx.y, S = gridDim.y;
-    const int64_t t0 = ntiles * s / S, t1 = ntiles * (s + 1) / S;
-    float acc = 0.f;
-    for (int64_t t = t0; t < t1; ++t) acc += tpart[(t * N_TILE_PART + slot) * 256 + threadIdx.x];
-    tred[((int64_t)s * N_TILE_PART + slot) * 256 + threadIdx.x] = acc;
+    DW_TPART_TAIL(tp, ntiles, g, (int)gridDim.x, wave, lane);
 }
 
 // ---------------------------------------------------------------- slab reduction + weight-norm fold -> flat gradient
@@ -749,31 +759,139 @@ struct FoldLin {
     int special;                          // 1: sdf lin8 (row 0 from TP 9+10, bias 0 from TP 11) ; 2: colour lin4 (TP 16..18, 19)
     int row_base;                         // first global row id of this linear
 };
-struct FoldTable { FoldLin lin[N_SDF + N_COL]; int total_rows; };
-struct SlabPtrs { const float* out[16]; int nb[16]; };
+// extra_*: the slab rows no parameter row folds (job 3's rows SKIP_OUT..255) -- reduced into `red` all the same, by blocks behind the
+// parameter rows', so that the reduced block is complete
+struct FoldTable { FoldLin lin[N_SDF + N_COL]; int total_rows; int extra_job, extra_row0, extra_n; };
+// per job: float offset inside a split block, nb, first workgroup and workgroup count of its job group
+struct SlabJobs { int64_t off[16]; int nb[16]; int wg0[16]; int wgn[16]; };
 
-__device__ __forceinline__ float slab_elem(const float* __restrict__ slab, int nb, int o, int i) {
-    const int w = o >> 5, ro = o & 31, j = i >> 5;
-    const int r = (ro & 3) + 4 * (ro >> 3);
-    const int lane = (i & 31) + 32 * ((ro >> 2) & 1);
-    return slab[((int64_t)w * nb + j) * 1024 + r * 64 + lane];
+// slab_elem: element (o, i) of a job's slab lies at ((w*nb + j)*1024 + r*64 + lane) with w = o >> 5, ro = o & 31,
+// r = (ro & 3) + 4 (ro >> 3), j = i >> 5, lane = (i & 31) + 32 ((ro >> 2) & 1): ONE OUTPUT ROW is nb runs of 32 consecutive floats
+// (128 B), 4 KiB apart.
+//
+// One slab row of one job, reduced by a 256-thread block: red[row] = sum over the G workgroups of the job's group of their slabs' row,
+// also left in LDS (`row`, slab column order).  The sum is slab_reduce_kernel's of rounds 2-6, bit for bit: slab g goes to partial
+// g % 8 in increasing g, the eight partials are combined pairwise in a fixed order.  The row's NF4 float4 are dealt to 256 / NF4
+// thread sets; a set owns 8 / sets partials (two at nb = 8; one, on the first eight sets, at nb = 2) and requests ITS slabs of each
+// at once as 16-B non-temporal loads (a wave reads whole 128-B runs; 32 slabs per batch: six measured the same at twice the
+// registers); the partials meet in LDS.  issue / add / stash / combine are separate so that a block with two source rows
+// has both rows' loads in flight together and pays one LDS round (one row after the other measured 52 us against 51: within noise).
+template <int NB>
+struct RowSum {
+    static constexpr int NF4 = NB * 8, SETS = 256 / NF4, KP = SETS >= 8 ? 1 : 8 / SETS, ITS = 4;
+    const float* p; int64_t gstride, e; int G, k0; bool on;
+    f32x4 v[ITS][KP], s[KP];
+    __device__ __forceinline__ void init(const float* __restrict__ slabs, int64_t gstride_, int64_t joff, int wg0, int G_, int so, int tid) {
+        const int f = tid % NF4, set = tid / NF4;
+        const int w = so >> 5, ro = so & 31;
+        e = joff + (int64_t)(w * NB + (f >> 3)) * 1024 + ((ro & 3) + 4 * (ro >> 3)) * 64 + 32 * ((ro >> 2) & 1) + 4 * (f & 7);
+        gstride = gstride_; G = G_; k0 = set * KP; on = k0 < 8;
+        p = slabs + (int64_t)wg0 * gstride + e;
+        DH_UNROLL for (int kk = 0; kk < KP; ++kk) s[kk] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    __device__ __forceinline__ void issue(int g0) {
+        DH_UNROLL for (int it = 0; it < ITS; ++it)
+            DH_UNROLL for (int kk = 0; kk < KP; ++kk) {
+                const int g = g0 + 8 * it + k0 + kk;
+                v[it][kk] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (on && g < G) v[it][kk] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + (int64_t)g * gstride));
+            }
+    }
+    __device__ __forceinline__ void add(int g0) {
+        DH_UNROLL for (int it = 0; it < ITS; ++it)
+            DH_UNROLL for (int kk = 0; kk < KP; ++kk) if (g0 + 8 * it + k0 + kk < G) s[kk] += v[it][kk];
+    }
+    __device__ __forceinline__ void rest() {                // (job groups of more than 8 ITS workgroups)
+        for (int g0 = 8 * ITS; g0 < G; g0 += 8 * ITS) { issue(g0); add(g0); }
+    }
+    __device__ __forceinline__ void stash(f32x4* part, int tid) const {
+        if (on) { DH_UNROLL for (int kk = 0; kk < KP; ++kk) part[(k0 + kk) * NF4 + tid % NF4] = s[kk]; }
+    }
+    __device__ __forceinline__ void combine(const f32x4* part, float* __restrict__ red, float* row, int tid) const {
+        if (tid < NF4) {                                    // set 0: e is float4 `tid`'s
+            const f32x4 t = ((part[tid] + part[NF4 + tid]) + (part[2 * NF4 + tid] + part[3 * NF4 + tid])) +
+                            ((part[4 * NF4 + tid] + part[5 * NF4 + tid]) + (part[6 * NF4 + tid] + part[7 * NF4 + tid]));
+            *reinterpret_cast<f32x4*>(red + e) = t;
+            *reinterpret_cast<f32x4*>(row + 4 * tid) = t;
+        }
+    }
+};
+struct RowSrc { int64_t off; int wg0, G, so; };
+// rows of one (NBA = NBB: only A) or two jobs -> red and rowA / rowB
+template <int NBA, int NBB>
+__device__ __forceinline__ void reduce_rows(const float* __restrict__ slabs, int64_t gstride, const RowSrc& A, const RowSrc& B, bool two,
+                                            float* __restrict__ red, float* rowA, float* rowB, f32x4* partA, f32x4* partB, int tid) {
+    RowSum<NBA> a;
+    RowSum<NBB> b;
+    a.init(slabs, gstride, A.off, A.wg0, A.G, A.so, tid);
+    a.issue(0);
+    if (two) { b.init(slabs, gstride, B.off, B.wg0, B.G, B.so, tid); b.issue(0); }
+    a.add(0); a.rest(); a.stash(partA, tid);
+    if (two) { b.add(0); b.rest(); b.stash(partB, tid); }
+    __syncthreads();
+    a.combine(partA, red, rowA, tid);
+    if (two) b.combine(partB, red, rowB, tid);
+    __syncthreads();
 }
 
-__global__ __launch_bounds__(256) void fold_kernel(FoldTable T, SlabPtrs S, const float* __restrict__ tred, int nS,
-                                                   const float* __restrict__ params, const float* __restrict__ packed,
-                                                   float* __restrict__ grad) {
+// One block per parameter row: it reduces the row of the one or two jobs the row is made of (into `red` and into LDS), then folds
+// it.  Everything the fold reads besides the slabs -- the row of v, g, 1 / |v|, the tile-partial sums of the bias -- is requested
+// before the slab loads.  (Rounds 2-6 ran slab_reduce_kernel over the whole block first, 36 us at 3 TB/s, and a fold that fetched
+// `red` one float per thread, 39 us; this kernel takes 51 us for both.  A block per EIGHT rows, which reads 1 KiB runs and needs no
+// LDS round for the partials, has 420 long blocks for 256 CUs and took 163 us: profiles/r07_ab_dw_skipcols_tail.json.)
+__global__ __launch_bounds__(256) void reduce_fold_kernel(FoldTable T, SlabJobs SJ, const float* __restrict__ slabs, int64_t gstride,
+                                                          float* __restrict__ red, const float* __restrict__ tred, int nS,
+                                                          const float* __restrict__ params, const float* __restrict__ packed,
+                                                          float* __restrict__ grad) {
+    __shared__ __attribute__((aligned(16))) float s_row[2][256];
+    __shared__ f32x4 s_part[2][8 * 64];
     __shared__ float s_red[4];
     const int rowid = blockIdx.x, tid = threadIdx.x;
+    auto src = [&](int job, int so) { return RowSrc{SJ.off[job], SJ.wg0[job], SJ.wgn[job], so}; };
+    auto reduce = [&](int jobA, int jobB, int so) {
+        const RowSrc A = src(jobA, so), B = src(jobB < 0 ? jobA : jobB, so);
+        const bool two = jobB >= 0;
+        if (SJ.nb[jobA] == 8) {
+            if (two) reduce_rows<8, 2>(slabs, gstride, A, B, true, red, s_row[0], s_row[1], s_part[0], s_part[1], tid);
+            else reduce_rows<8, 8>(slabs, gstride, A, A, false, red, s_row[0], s_row[1], s_part[0], s_part[1], tid);
+        } else {
+            if (two) reduce_rows<2, 8>(slabs, gstride, A, B, true, red, s_row[0], s_row[1], s_part[0], s_part[1], tid);
+            else reduce_rows<2, 2>(slabs, gstride, A, A, false, red, s_row[0], s_row[1], s_part[0], s_part[1], tid);
+        }
+    };
+    if (rowid >= T.total_rows) {
+        reduce(T.extra_job, -1, T.extra_row0 + (rowid - T.total_rows));
+        return;
+    }
     int li = 0;
     for (int k = 1; k < N_SDF + N_COL; ++k) if (rowid >= T.lin[k].row_base) li = k;
     const FoldLin Ln = T.lin[li];
     const int o = rowid - Ln.row_base;
+    const bool from_slabs = !(Ln.special == 2 || (Ln.special == 1 && o == 0));
+    float vv[2] = {0.f, 0.f};
+    DH_UNROLL for (int q = 0; q < 2; ++q) {
+        const int i = tid + 256 * q;
+        if (i < Ln.in) vv[q] = params[Ln.voff + (int64_t)o * Ln.in + i];
+    }
+    const float inv = packed[Ln.rsoff + (PACK.invnorm - PACK.rowscale) + o];
+    const float gval = params[Ln.goff + o];
+    float b = 0.f;
+    if (tid < 64) {
+        // the row's bias gradient: nS tile-partial sums, one per lane of the first wave and a fixed shuffle tree (ONE thread adding
+        // them in a dependent chain of nS L2 loads was the critical path of this kernel: 52 -> 2x us)
+        int slot, c;
+        if (Ln.special == 2) { slot = 19; c = o; }
+        else if (Ln.special == 1 && o == 0) { slot = 11; c = 0; }
+        else { slot = Ln.bias_slot; c = o - Ln.row_shift; }
+        for (int k = tid; k < nS; k += 64) b += tred[((int64_t)k * N_TILE_PART + slot) * 256 + c];
+    }
+    if (from_slabs) reduce(Ln.jobA, Ln.jobB, o - Ln.row_shift);
     auto tsum = [&](int slot, int c) {
         float s = 0.f;
         for (int k = 0; k < nS; ++k) s += tred[((int64_t)k * N_TILE_PART + slot) * 256 + c];
         return s;
     };
-    float dw[2] = {0.f, 0.f}, vv[2] = {0.f, 0.f};
+    float dw[2] = {0.f, 0.f};
     float dot = 0.f;
     DH_UNROLL for (int q = 0; q < 2; ++q) {
         const int i = tid + 256 * q;
@@ -782,13 +900,10 @@ __global__ __launch_bounds__(256) void fold_kernel(FoldTable T, SlabPtrs S, cons
             if (Ln.special == 2) d = tsum(16 + o, i);                                     // colour lin4 rows
             else if (Ln.special == 1 && o == 0) d = tsum(9, i) + tsum(10, i);             // sdf lin8 row 0
             else {
-                const int so = o - Ln.row_shift;
-                if (i >= Ln.a_c0 && i < Ln.a_c1) d = Ln.a_scale * slab_elem(S.out[Ln.jobA], S.nb[Ln.jobA], so, i - Ln.a_c0);
-                else if (Ln.jobB >= 0 && i >= Ln.b_c0 && i < Ln.b_c1)
-                    d = Ln.b_scale * slab_elem(S.out[Ln.jobB], S.nb[Ln.jobB], so, i - Ln.b_c0);
+                if (i >= Ln.a_c0 && i < Ln.a_c1) d = Ln.a_scale * s_row[0][i - Ln.a_c0];
+                else if (Ln.jobB >= 0 && i >= Ln.b_c0 && i < Ln.b_c1) d = Ln.b_scale * s_row[1][i - Ln.b_c0];
             }
             dw[q] = d;
-            vv[q] = params[Ln.voff + (int64_t)o * Ln.in + i];
             dot = fmaf(d, vv[q], dot);
         }
     }
@@ -796,21 +911,11 @@ __global__ __launch_bounds__(256) void fold_kernel(FoldTable T, SlabPtrs S, cons
     if ((tid & 63) == 0) s_red[tid >> 6] = dot;
     __syncthreads();
     dot = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-    const float inv = packed[Ln.rsoff + (PACK.invnorm - PACK.rowscale) + o];
-    const float gval = params[Ln.goff + o];
     DH_UNROLL for (int q = 0; q < 2; ++q) {
         const int i = tid + 256 * q;
         if (i < Ln.in) grad[Ln.voff + (int64_t)o * Ln.in + i] = gval * inv * (dw[q] - dot * inv * inv * vv[q]);
     }
     if (tid < 64) {
-        // the row's bias gradient: nS tile-partial sums, one per lane of the first wave and a fixed shuffle tree (ONE thread adding
-        // them in a dependent chain of nS L2 loads was the critical path of this kernel: 52 -> 2x us)
-        int slot, c;
-        if (Ln.special == 2) { slot = 19; c = o; }
-        else if (Ln.special == 1 && o == 0) { slot = 11; c = 0; }
-        else { slot = Ln.bias_slot; c = o - Ln.row_shift; }
-        float b = 0.f;
-        for (int k = tid; k < nS; k += 64) b += tred[((int64_t)k * N_TILE_PART + slot) * 256 + c];
         DH_UNROLL for (int off = 32; off > 0; off >>= 1) b += __shfl_xor(b, off);
         if (tid == 0) {
             grad[Ln.goff + o] = dot * inv;
@@ -847,6 +952,7 @@ static FoldTable build_fold_table() {
         F.row_base = row; row += F.out;
     }
     T.total_rows = row;
+    T.extra_job = 3; T.extra_row0 = SDF_DIMS[3].out; T.extra_n = 256 - SDF_DIMS[3].out;
     return T;
 }
 
@@ -859,10 +965,10 @@ static int64_t dw_gstride() {
 }
 int64_t dw_slab_floats(int G) { return (int64_t)(G + 1) * dw_gstride(); }
 
-static void build_dw_jobs(const Workspace& w, float* red, DwJobs& J, SlabPtrs& S) {
+static void build_dw_jobs(const Workspace& w, DwJobs& J) {
     const int64_t nt = w.ntiles;
     int64_t off = 0;
-    for (int j = 0; j < 15; ++j) { J.j[j].nb = DW_NBS[j]; J.j[j].off = off; S.out[j] = red + off; S.nb[j] = DW_NBS[j]; off += (int64_t)8 * DW_NBS[j] * 1024; }
+    for (int j = 0; j < 15; ++j) { J.j[j].nb = DW_NBS[j]; J.j[j].off = off; off += (int64_t)8 * DW_NBS[j] * 1024; }
     J.n = 15;
     auto T_ = [&](float* base, int idx) { return base + (int64_t)idx * nt * TILE_F; };
     // operand classes of the two-piece fp16 kernel: (absmax class, tmax class) of A and B for each pair
@@ -923,33 +1029,37 @@ static DwGroups build_dw_groups(const DwJobs& J, int G) {
     return Gp;
 }
 
-// stage 1: the split-K weight-gradient GEMMs (one kernel)
-int launch_weight_grads_gemm(const Workspace& w, float* slabs, int G, int arith, hipStream_t st) {
+// stage 1: the split-K weight-gradient GEMMs and, behind their jobs, the tile-partial reduction (one kernel)
+int launch_weight_grads_gemm(const Workspace& w, float* slabs, float* tred, int G, int nS, int arith, hipStream_t st) {
     const int64_t gstride = dw_gstride();
     DwJobs J{};
-    SlabPtrs S{};
-    build_dw_jobs(w, slabs + (int64_t)G * gstride, J, S);
+    build_dw_jobs(w, J);
     const DwGroups Gp = build_dw_groups(J, G);
-    if (arith == ARITH_FP32) hipLaunchKernelGGL(dw_lds_kernel, dim3(G), dim3(512), 0, st, J, Gp, w.ntiles, slabs, gstride);
+    const TpartArgs tp{w.tpart, tred, nS};
+#ifdef DW_TPART_FRONT
+    hipLaunchKernelGGL(tpart_reduce_kernel, dim3((unsigned)((nS * N_TILE_PART + 3) / 4)), dim3(256), 0, st, tp, w.ntiles);
+#endif
+    if (arith == ARITH_FP32) hipLaunchKernelGGL(dw_lds_kernel, dim3(G), dim3(512), 0, st, J, Gp, w.ntiles, slabs, gstride, tp);
     else if (arith == ARITH_F16) hipLaunchKernelGGL(dw_f16x2_kernel, dim3(G), dim3(512), 0, st, J, Gp, w.ntiles, slabs, gstride,
-                                                    reinterpret_cast<const unsigned*>(w.absmax), reinterpret_cast<const unsigned*>(w.tmax));
-    else hipLaunchKernelGGL(dw_bf16x3_kernel, dim3(G), dim3(512), 0, st, J, Gp, w.ntiles, slabs, gstride);
+                                                    reinterpret_cast<const unsigned*>(w.absmax), reinterpret_cast<const unsigned*>(w.tmax), tp);
+    else hipLaunchKernelGGL(dw_bf16x3_kernel, dim3(G), dim3(512), 0, st, J, Gp, w.ntiles, slabs, gstride, tp);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-// stage 2: slab + tile-partial reductions, weight-norm fold into the flat gradient
+// stage 2: slab reduction and weight-norm fold into the flat gradient (one kernel); tred is stage 1's
 int launch_weight_grads_fold(const Workspace& w, float* slabs, float* tred, int G, int nS, const float* params,
                              const float* packed, float* grad, hipStream_t st) {
     const int64_t gstride = dw_gstride();
     float* red = slabs + (int64_t)G * gstride;
     DwJobs J{};
-    SlabPtrs S{};
-    build_dw_jobs(w, red, J, S);
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((gstride / 4 + 255) / 256)), dim3(256), 0, st, slabs, gstride,
-                       build_dw_groups(J, G), red);
-    hipLaunchKernelGGL(tpart_reduce_kernel, dim3(N_TILE_PART, nS), dim3(256), 0, st, w.tpart, w.ntiles, tred);
+    build_dw_jobs(w, J);
+    const DwGroups Gp = build_dw_groups(J, G);
+    SlabJobs SJ{};
+    for (int k = 0; k < Gp.n; ++k)
+        for (int j = Gp.job0[k]; j < Gp.job0[k + 1]; ++j) { SJ.off[j] = J.j[j].off; SJ.nb[j] = J.j[j].nb; SJ.wg0[j] = Gp.wg0[k]; SJ.wgn[j] = Gp.wg0[k + 1] - Gp.wg0[k]; }
     static const FoldTable T = build_fold_table();
-    hipLaunchKernelGGL(fold_kernel, dim3(T.total_rows), dim3(256), 0, st, T, S, tred, nS, params, packed, grad);
+    hipLaunchKernelGGL(reduce_fold_kernel, dim3(T.total_rows + T.extra_n), dim3(256), 0, st, T, SJ, slabs, gstride, red, tred, nS,
+                       params, packed, grad);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

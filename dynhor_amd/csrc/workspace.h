@@ -53,7 +53,7 @@ struct Workspace {
     float* zbar;    // [8][nt][TILE_F]   d loss / d z_l, l = 0..7
     float* czbar;   // [4][nt][TILE_F]   colour d loss / d z_l
     float* tpart;   // [nt][N_TILE_PART][256]
-    float* tred;    // [DW_NS][N_TILE_PART][256]
+    float* tred;    // [DW_NS][N_TILE_PART][256]   (written by the weight-gradient GEMM kernel, read by the fold)
     float* slabs;   // dW split-K slabs (dw.hip)
     float* gesave;  // [nt*TM][40]       embedding-gradient vector ge of the normal pass (pose refinement only: dh_sdf_gradient save = 2)
     int64_t infer_floats, fwd_floats, total_floats;   // forward-only (no saves for backward) / forward / everything

@@ -150,6 +150,9 @@ int dh_color_backward_rays(const float* packed, const float* colors, const float
                            int64_t npts, float* ws, float* d_normals, float* d_pts, float* d_dirs_pts, void* stream);
 int dh_sdf_backward_rays(const float* packed, const float* d_sdf, const float* pts, const float* d_normals, int64_t npts,
                          float* ws, float* d_pts, void* stream);
+/* Weight gradients, two launches: _gemm writes the split-K slabs AND the reduced tile partials (bias gradients; its workgroups take
+ * that reduction behind their GEMM jobs), _fold reduces the slabs and folds the weight norm.  _fold therefore follows a _gemm on
+ * the same workspace with the tile partials unchanged in between. */
 int dh_weight_grads_gemm(int64_t npts, float* ws, void* stream);
 int dh_weight_grads_fold(const float* packed, const float* params, int64_t npts, float* ws, float* grad_flat, void* stream);
 
