@@ -843,6 +843,42 @@ int dh_sil_loss_grad(const uint64_t* near, const float* verts, int64_t nv, const
                                 ws, static_cast<hipStream_t>(stream));
 }
 
+int dh_image_blur(const uint8_t* rgb, const uint8_t* usable, int64_t n_frames, int H, int W, const float* taps, int radius, float* tmp,
+                  float* out, void* stream) {
+    const int rc = sil_args(n_frames, H, W);
+    if (rc != DH_OK) return rc;
+    if (radius < 0) return DH_ERR_BAD_ARG;
+    if (n_frames == 0) return DH_OK;
+    if (!rgb || !usable || !taps || !tmp || !out || misaligned16(tmp) || misaligned16(out)) return DH_ERR_BAD_ARG;
+    if (n_frames * H >= ((int64_t)1 << 31) || W > 65535 * 256 || radius > image_blur_max_radius()) return DH_ERR_UNSUPPORTED;
+    const int64_t floats = n_frames * H * W * 4;
+    if (tmp < out + floats && out < tmp + floats) return DH_ERR_BAD_ARG;                             // the column pass reads tmp's other rows
+    return launch_image_blur(rgb, usable, n_frames, H, W, taps, radius, tmp, out, static_cast<hipStream_t>(stream));
+}
+
+int dh_photo_loss_sums(void) { return photo_loss_sums(); }
+
+int64_t dh_photo_loss_grad_workspace(int64_t n_frames, int64_t n_points) {
+    if (n_frames < 0 || n_points < 0) return DH_ERR_BAD_ARG;
+    if (n_frames > 65535 || n_points >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;
+    return photo_loss_grad_workspace(n_frames, n_points);
+}
+
+int dh_photo_loss_grad(const float* pts, const float* normals, const float* colors, int64_t n_points, const float* img,
+                       const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
+                       float depth_eps, float min_cos, float a_min, float delta, double* out, void* ws, void* stream) {
+    if (n_points < 0) return DH_ERR_BAD_ARG;
+    const int rc = sil_args(n_frames, H, W);
+    if (rc != DH_OK) return rc;
+    if (!(depth_eps >= 0.f) || min_cos != min_cos || !(a_min >= 0.f) || !(delta > 0.f)) return DH_ERR_BAD_ARG;   // NaN, negative
+    if (n_points >= ((int64_t)1 << 31) || n_frames > 65535) return DH_ERR_UNSUPPORTED;               // grid (blocks, frames)
+    if (n_frames == 0) return DH_OK;
+    if (!R || !T || !K || !out || !ws || misaligned16(ws)) return DH_ERR_BAD_ARG;
+    if (n_points > 0 && (!pts || !normals || !colors || !img || !zbuf || misaligned16(img))) return DH_ERR_BAD_ARG;
+    return launch_photo_loss_grad(pts, normals, colors, n_points, img, zbuf, R, T, K, n_frames, H, W, depth_eps, min_cos, a_min, delta,
+                                  out, ws, static_cast<hipStream_t>(stream));
+}
+
 int dh_label_boxes(const int8_t* label, int64_t n, int H, int W, int32_t* boxes, void* stream) {
     const int rc = sil_args(n, H, W);
     if (rc != DH_OK) return rc;

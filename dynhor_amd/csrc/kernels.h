@@ -245,6 +245,17 @@ int launch_sil_loss_grad(const uint64_t* near, const float* verts, int64_t nv, c
                          const float* T, const float* K, const float* d2_obj, const float* d2_hand, const int8_t* label, int64_t n_frames,
                          int H, int W, float sigma, float cut, float edge_offset, double* out, void* ws, hipStream_t st);
 
+// photometric pose term (pose_photo.hip): masked separable Gaussian of the frames (radius <= image_blur_max_radius()), loss /
+// pose-gradient sums per frame of coloured surface points (photo_loss_sums() doubles, ws = photo_loss_grad_workspace bytes)
+int image_blur_max_radius();
+int launch_image_blur(const uint8_t* rgb, const uint8_t* usable, int64_t n_frames, int H, int W, const float* taps, int radius,
+                      float* tmp, float* out, hipStream_t st);
+int photo_loss_sums();
+int64_t photo_loss_grad_workspace(int64_t n_frames, int64_t n_points);
+int launch_photo_loss_grad(const float* pts, const float* normals, const float* colors, int64_t n, const float* img,
+                           const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
+                           float depth_eps, float min_cos, float a_min, float delta, double* out, void* ws, hipStream_t st);
+
 // pose initialisation by silhouette retrieval (pose_init.hip): tight box of label == 1 per image, the label resampled on an S x S
 // square and packed one bit per sample (obj / keep planes), intersection / union counts of every frame against every bank view
 // (label_boxes_chunks / sil_bank_score_*_tiles: the grid sizes, for the limits)

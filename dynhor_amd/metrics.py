@@ -98,7 +98,13 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def _load_ply(path):
+def load_ply_colors(path: str):
+    """u8 [V,3] CPU tensor of the red / green / blue vertex properties of a .ply (the file mesh.write_ply writes for a coloured mesh), in
+    load_mesh's vertex order; None when the file has none."""
+    return _load_ply(path, with_colors=True)[2]
+
+
+def _load_ply(path, with_colors=False):
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.find(b"end_header")
@@ -122,10 +128,13 @@ def _load_ply(path):
     if fmt not in ("ascii", "binary_little_endian"):
         raise ValueError(f"load_mesh: PLY format {fmt!r} of {path} is not supported (ascii or binary_little_endian)")
     reader = _PlyAscii(data[body:]) if fmt == "ascii" else _PlyBinary(data, body)
-    verts, polys = None, []
+    verts, polys, colors = None, [], None
     for name, count, props in elements:
         rows = reader.element(count, props)
         if name == "vertex":
+            if with_colors and all(c in rows for c in ("red", "green", "blue")):
+                colors = torch.from_numpy(np.stack([np.asarray(rows[c], np.float64) for c in ("red", "green", "blue")], axis=1)
+                                          .round().clip(0, 255).astype(np.uint8))
             verts = np.stack([np.asarray(rows["x"], np.float64), np.asarray(rows["y"], np.float64),
                               np.asarray(rows["z"], np.float64)], axis=1)
         elif name == "face":
@@ -139,7 +148,7 @@ def _load_ply(path):
     else:
         f = _fan([[int(i) for i in p] for p in polys])
     _check_indices(f, v.shape[0], path)
-    return v, f
+    return (v, f, colors) if with_colors else (v, f)
 
 
 class _PlyBinary:

@@ -25,6 +25,9 @@ The loss (csrc/sil.hip, include/dynhor_hip.h).  Per frame f, with the projection
 ``silhouette_loss_grad`` (dh_sil_loss_grad) reduces a frame to sum w (S - M)^2, sum w, d/dR (9), d/dT (3) and the (tp, fp, fn) counts
 of ``mesh_vis.shade``, in fp64 with block-ordered sums: bitwise reproducible for every frame chunking.
 
+An optional photometric term (dynhor_amd/pose_photo.py: coloured surface points aligned to blurred frames) runs next to the silhouette:
+``SilhouettePoseOptimizer(photo=, lw_photo=)`` and ``refine_poses(photo=)``.  Without it nothing of this module changes.
+
 The kernels run on the current stream; there is no CPU path.
 """
 from __future__ import annotations
@@ -38,6 +41,7 @@ from . import _lib
 from .mesh_clean import _device_tensor, _faces
 from .mesh_color import _cams, _verts
 from .pose import rot6d_to_matrix
+from .pose_photo import DEFAULTS as PHOTO_DEFAULTS, level_at
 
 # defaults of the YAML's pose_sil: block (runner.POSE_SIL_DEFAULTS); DESIGN_NEXT_ROWS.md section 13 says where each comes from
 DEFAULTS = {"iters": 120, "lr": 5e-3, "rot_lr_mult": 10.0, "sigma_px": 6.0, "sigma_end_px": 1.5, "cut": 3.0, "edge_offset_px": 0.5,
@@ -151,7 +155,8 @@ class SilhouettePoseOptimizer:
 
     def __init__(self, verts, faces, label, R0, T0, K, lr=DEFAULTS["lr"], rot_lr_mult=DEFAULTS["rot_lr_mult"],
                  sigma_px=DEFAULTS["sigma_px"], cut=DEFAULTS["cut"], edge_offset_px=DEFAULTS["edge_offset_px"],
-                 lw_sil=DEFAULTS["lw_sil"], lw_smooth=DEFAULTS["lw_smooth"], frame_chunk=DEFAULTS["frame_chunk"], active=None):
+                 lw_sil=DEFAULTS["lw_sil"], lw_smooth=DEFAULTS["lw_smooth"], frame_chunk=DEFAULTS["frame_chunk"], active=None,
+                 photo=None, lw_photo=0.0):
         fn = "SilhouettePoseOptimizer"
         self.verts = _verts(fn, verts)
         self.faces = _faces(fn, faces)
@@ -193,6 +198,15 @@ class SilhouettePoseOptimizer:
         self.d2_hand = label_edt(self.label, -1, self.rmax)
         self.last_sums = None            # float64 [n_active,17] of the most recent step (before its update)
         self.last_smooth = None
+        # the optional photometric term (pose_photo.PhotometricTerm): its blurred frames follow the active frames
+        self.photo, self.lw_photo = photo, float(lw_photo)
+        self.last_photo = None           # float64 [n_active,16] of the most recent step
+        self.last_photo_eval = None      # ... of the most recent evaluate()
+        if photo is not None:
+            if tuple(photo.rgb.shape[:3]) != (self.F, self.H, self.W) or photo.rgb.device != dev:
+                raise ValueError(f"{fn}: photo holds frames {tuple(photo.rgb.shape[:3])} on {photo.rgb.device}, the labels are "
+                                 f"{(self.F, self.H, self.W)} on {dev}")
+            photo.set_frames(self.active_idx if len(idx) != self.F else None)
 
     def poses64(self):
         return rot6d_to_matrix(self.rot6d).transpose(1, 2), self.trans
@@ -212,13 +226,14 @@ class SilhouettePoseOptimizer:
 
     @torch.no_grad()
     def evaluate(self, sigma: float) -> torch.Tensor:
-        """float64 [n_active,17]: silhouette_sums of the active frames at the current poses, in chunks of frame_chunk frames."""
+        """float64 [n_active,17]: silhouette_sums of the active frames at the current poses, in chunks of frame_chunk frames.  With a
+        photometric term its sums of the same chunks (z-buffer, dh_photo_loss_grad) go to self.last_photo_eval [n_active,16]."""
         if float(sigma) > self.sigma_px * (1.0 + 1e-9):
             raise ValueError(f"SilhouettePoseOptimizer: sigma {sigma} exceeds sigma_px {self.sigma_px} the distance transforms were made for")
         R32, T32 = self.poses()
         R32, T32 = R32[self.active_idx], T32[self.active_idx]
         n = len(self.active_list)
-        out = []
+        out, pout = [], []
         for f0 in range(0, n, self.frame_chunk):
             f1 = min(n, f0 + self.frame_chunk)
             Rc, Tc = R32[f0:f1].contiguous(), T32[f0:f1].contiguous()
@@ -226,6 +241,9 @@ class SilhouettePoseOptimizer:
             out.append(silhouette_sums(self.verts, self.faces, near, Rc, Tc, self.K, self.d2_obj[f0:f1], self.d2_hand[f0:f1],
                                        self.label[f0:f1], sigma, self.cut, self.edge_offset_px))
             del near
+            if self.photo is not None:
+                pout.append(self.photo.sums(self.verts, self.faces, Rc, Tc, self.K, f0, f1))
+        self.last_photo_eval = torch.cat(pout) if pout else None
         return torch.cat(out)
 
     def step(self, sigma: float):
@@ -238,6 +256,12 @@ class SilhouettePoseOptimizer:
         gT = torch.zeros(self.F, 3, dtype=torch.float64, device=self.device)
         gR[self.active_idx] = sums[:, 2:11].reshape(n, 3, 3) * scale[:, None, None]
         gT[self.active_idx] = sums[:, 11:14] * scale[:, None]
+        if self.photo is not None:
+            ps = self.last_photo_eval
+            pscale = (self.lw_photo / n) / ps[:, 1].clamp(min=1e-12)
+            gR[self.active_idx] += ps[:, 2:11].reshape(n, 3, 3) * pscale[:, None, None]
+            gT[self.active_idx] += ps[:, 11:14] * pscale[:, None]
+            self.last_photo = ps
         for p in (self.rot6d, self.trans):
             p.grad = None
         R, T = self.poses64()
@@ -268,8 +292,14 @@ class SilhouettePoseOptimizer:
         l_sil = float((s[:, 0] / s[:, 1].clamp(min=1.0)).mean())
         l_sm = float(self.last_smooth) if self.last_smooth is not None else float(self.smoothness(*self.poses64()))
         iou = s[:, 14] / s[:, 14:17].sum(dim=1).clamp(min=1.0)
-        return {"iter": self.n_steps, "loss": self.lw_sil * l_sil + self.lw_smooth * l_sm, "loss_sil": l_sil, "loss_smooth": l_sm,
-                "iou_mean": float(iou.mean()), "iou_min": float(iou.min())}
+        st = {"iter": self.n_steps, "loss": self.lw_sil * l_sil + self.lw_smooth * l_sm, "loss_sil": l_sil, "loss_smooth": l_sm,
+              "iou_mean": float(iou.mean()), "iou_min": float(iou.min())}
+        if self.photo is not None:
+            p = self.last_photo.cpu()
+            l_photo = float((p[:, 0] / p[:, 1].clamp(min=1e-12)).mean())
+            st.update(loss=st["loss"] + self.lw_photo * l_photo, loss_photo=l_photo, photo_pairs=[int(x) for x in p[:, 14].round().tolist()],
+                      photo_inliers=float(p[:, 15].sum() / p[:, 14].sum().clamp(min=1.0)))
+        return st
 
 
 def _iou(counts) -> list:
@@ -311,14 +341,20 @@ def select_frames(frames, stems, iou) -> list:
 def refine_poses(verts, faces, dataset, iters=DEFAULTS["iters"], lr=DEFAULTS["lr"], rot_lr_mult=DEFAULTS["rot_lr_mult"],
                  sigma_px=DEFAULTS["sigma_px"], sigma_end_px=DEFAULTS["sigma_end_px"], cut=DEFAULTS["cut"],
                  edge_offset_px=DEFAULTS["edge_offset_px"], lw_sil=DEFAULTS["lw_sil"], lw_smooth=DEFAULTS["lw_smooth"],
-                 frame_chunk=DEFAULTS["frame_chunk"], report_freq=DEFAULTS["report_freq"], frames=None, log=None) -> dict:
+                 frame_chunk=DEFAULTS["frame_chunk"], report_freq=DEFAULTS["report_freq"], frames=None, log=None, photo=None,
+                 lw_photo=None) -> dict:
     """Refine the dataset's poses against the mesh (verts, faces) and write them into dataset.R / dataset.T in place.  frames: None /
     "all", "worst:N", or stems / indices: restricts the silhouette term and the update to those frames; the others stay fixed and
     still anchor the smoothness term.  log(stats dict) is called every report_freq iterations.  Returns {frames (the indices refined),
     stems, iou_before, iou_after (per frame of the dataset, None where a frame has neither object nor mesh pixels), iou_mean_before /
-    after, curve (the stats of the reported iterations), R, T (float32 device tensors), settings}."""
+    after, curve (the stats of the reported iterations), R, T (float32 device tensors), settings}.
+    photo: a pose_photo.PhotometricTerm of coloured points on this mesh over the dataset's frames, or None.  With it the colour term is
+    added at weight lw_photo (default pose_photo.DEFAULTS), iteration k at the blur level photo.levels[floor(k len(levels) / iters)]
+    (the frames are blurred again when the level changes); every curve entry gains loss_photo, photo_pairs (per refined frame),
+    photo_inliers and blur_sigma, and the result gains photo_pairs (the last iteration's) and settings["photo"]."""
     from .mesh_vis import overlay_frames
     iters, report_freq = int(iters), int(report_freq)
+    lw_photo = float(PHOTO_DEFAULTS["lw_photo"] if lw_photo is None else lw_photo)
     if iters < 1:
         raise ValueError(f"refine_poses: iters must be >= 1, got {iters}")
     if not 0.0 < float(sigma_end_px) <= float(sigma_px):
@@ -333,13 +369,18 @@ def refine_poses(verts, faces, dataset, iters=DEFAULTS["iters"], lr=DEFAULTS["lr
     active[sel] = True
     opt = SilhouettePoseOptimizer(verts, faces, ds.label, ds.R, ds.T, ds.K, lr=lr, rot_lr_mult=rot_lr_mult, sigma_px=sigma_px, cut=cut,
                                   edge_offset_px=edge_offset_px, lw_sil=lw_sil, lw_smooth=lw_smooth, frame_chunk=frame_chunk,
-                                  active=None if len(sel) == ds.n_images else active)
+                                  active=None if len(sel) == ds.n_images else active, photo=photo,
+                                  lw_photo=lw_photo if photo is not None else 0.0)
     curve = []
     for k in range(iters):
         sigma = sigma_at(k, iters, sigma_px, sigma_end_px)
+        if photo is not None:
+            photo.set_level(level_at(k, iters, photo.levels))
         opt.step(sigma)
         if (report_freq > 0 and k % report_freq == 0) or k == iters - 1:
             st = dict(opt.stats(), sigma=sigma)
+            if photo is not None:
+                st["blur_sigma"] = photo.sigma
             curve.append(st)
             if log is not None:
                 log(st)
@@ -353,9 +394,14 @@ def refine_poses(verts, faces, dataset, iters=DEFAULTS["iters"], lr=DEFAULTS["lr
     after = _iou(overlay_frames(verts, faces, ds, frame_chunk=frame_chunk))
     scored_before, scored_after = [x for x in before if x is not None], [x for x in after if x is not None]
     mean = lambda xs: sum(xs) / len(xs) if xs else None
-    return {"frames": sel, "stems": stems, "iou_before": before, "iou_after": after, "iou_mean_before": mean(scored_before),
+    res = {"frames": sel, "stems": stems, "iou_before": before, "iou_after": after, "iou_mean_before": mean(scored_before),
             "iou_mean_after": mean(scored_after), "iou_min_before": min(scored_before, default=None),
             "iou_min_after": min(scored_after, default=None), "curve": curve, "R": R, "T": T,
             "settings": {"iters": iters, "lr": float(lr), "rot_lr_mult": float(rot_lr_mult), "sigma_px": float(sigma_px),
                          "sigma_end_px": float(sigma_end_px), "cut": float(cut), "edge_offset_px": float(edge_offset_px),
                          "lw_sil": float(lw_sil), "lw_smooth": float(lw_smooth), "frame_chunk": int(frame_chunk)}}
+    if photo is not None:
+        res["photo_pairs"] = curve[-1]["photo_pairs"]
+        res["settings"]["photo"] = {"points": int(photo.pts.shape[0]), "levels": list(photo.levels), "lw_photo": lw_photo,
+                                    "delta": photo.delta, "a_min": photo.a_min, "min_cos": photo.min_cos, "depth_eps": photo.depth_eps}
+    return res

@@ -24,6 +24,7 @@ from .dataset import Dataset
 from .fields import ParamStore, RenderingNetwork, SDFNetwork, SingleVarianceNetwork
 from .mesh_extract import DEFAULT_LIPSCHITZ
 from .pose_init import DEFAULTS as POSE_INIT_DEFAULTS
+from .pose_photo import DEFAULTS as POSE_PHOTO_DEFAULTS
 from .pose_sil import DEFAULTS as POSE_SIL_DEFAULTS
 from .renderer import NeuSRenderer
 from .sdf_init import SDF_INIT_DEFAULTS
@@ -56,6 +57,9 @@ DEFAULT_CONF = {
     # silhouette pose refinement (--mode refine_poses): dynhor_amd/pose_sil.py says what each number is, DESIGN_NEXT_ROWS.md section 13
     # where it comes from; resolution = the marching-cubes grid of the reconstruction the poses are fitted to
     "pose_sil": dict(POSE_SIL_DEFAULTS),
+    # the optional photometric term of refine_poses (--pose_photo): dynhor_amd/pose_photo.py says what each number is,
+    # DESIGN_NEXT_ROWS.md section 19 where it comes from; mode none | views | mesh
+    "pose_photo": dict(POSE_PHOTO_DEFAULTS),
     # pose initialisation from a template mesh (--mode init_poses): dynhor_amd/pose_init.py says what each number is,
     # DESIGN_NEXT_ROWS.md section 16 where it comes from; its final joint refinement takes the pose_sil: block
     "pose_init": dict(POSE_INIT_DEFAULTS),
@@ -1000,8 +1004,36 @@ class Runner:
         self.last_pose_dir = d
         return d
 
+    def _photo_term(self, mode, pp, verts, faces, mesh, cmode, smode):
+        """The pose_photo.PhotometricTerm of refine_poses_silhouette: `pp` the merged pose_photo: block.  "views": the mesh being fitted
+        coloured from the frames at the current poses (mesh_color, mode "views": unseen vertices grey); "mesh": the vertex colours of the
+        .ply file `mesh`, or the texture of the .obj file `mesh` (mesh_texture.load_textured_obj), which must reach the fit neither
+        cleaned nor simplified."""
+        from .pose_photo import make_term
+        fn = "refine_poses_silhouette"
+        kw = dict(n_points=int(pp["points"]), seed=int(pp["seed"]), erode_px=int(pp["erode_px"]), levels=tuple(pp["levels"]),
+                  delta=float(pp["delta"]), a_min=float(pp["a_min"]), min_cos=float(pp["min_cos"]), depth_eps=float(pp["depth_eps"]))
+        if mode == "views":
+            from .mesh_color import color_mesh
+            colors, _ = color_mesh(verts, faces, "views", dataset=self.dataset, erode_px=int(pp["erode_px"]),
+                                   min_cos=MESH_COLOR_DEFAULTS["min_cos"], depth_eps=float(pp["depth_eps"]))
+            return make_term(verts, faces, self.dataset, vertex_colors=colors, **kw)
+        if mesh is None or cmode != "none" or smode != "none":
+            raise ValueError(f"{fn}: pose_photo 'mesh' takes the colours of a mesh file (--vis_mesh) that is neither cleaned nor simplified")
+        if str(mesh).lower().endswith(".obj"):
+            from .mesh_texture import load_textured_obj
+            _, tfaces, uv, tex = load_textured_obj(str(mesh))
+            if uv is None or not torch.equal(tfaces, faces.cpu()):
+                raise ValueError(f"{fn}: pose_photo 'mesh' needs a textured .obj (vt lines and a map_Kd image); {mesh} has none")
+            return make_term(verts, faces, self.dataset, uv=uv.to(self.device), texture=tex.to(self.device), **kw)
+        from .metrics import load_ply_colors
+        colors = load_ply_colors(str(mesh))
+        if colors is None or colors.shape[0] != verts.shape[0]:
+            raise ValueError(f"{fn}: pose_photo 'mesh' needs a .ply with red / green / blue vertex properties; {mesh} has none")
+        return make_term(verts, faces, self.dataset, vertex_colors=colors.to(self.device), **kw)
+
     def refine_poses_silhouette(self, mesh=None, normalize=None, resolution=None, clean=None, extract=None, frames=None, save=True,
-                                simplify=None, **overrides):
+                                simplify=None, photo=None, **overrides):
         """Every frame's pose refined against a mesh by silhouette matching (dynhor_amd/pose_sil.py) and written into Dataset.R /
         Dataset.T.  The mesh is chosen as visualize_mesh chooses it (_select_mesh; `mesh` and `normalize` left at None take the config's
         mesh_vis: block): the .ply / .obj file `mesh` (normalize "none" | "reference"), else the reconstruction extracted at
@@ -1014,7 +1046,12 @@ class Runner:
         re-seeded from the new poses (its Adam state starts afresh) and, when save is on, checkpoints/ckpt_<iter>.pth is written again
         with it: load_checkpoint copies a checkpoint's PoseRefiner poses over Dataset.R / T, so that is what a later --is_continue run
         starts from.  Without train.refine_poses, point data_info.obj_infos at the written folder.  Returns the dict of refine.json
-        plus dir (single process: run it on one rank)."""
+        plus dir (single process: run it on one rank).
+        photo: None (the config's pose_photo.mode) | "none" | "views" | "mesh": add the photometric term of dynhor_amd/pose_photo.py
+        (_photo_term says where the colours come from; the other keys of the pose_photo: block are its settings).  refine.json then
+        carries `photo`, the loss_photo curve and the contributing pairs per refined frame (photo_pairs), and pose/loss_photo goes to
+        the board.  With "none" everything is exactly what it is without the term."""
+        from .pose_photo import MODES as PHOTO_MODES
         from .pose_sil import refine_poses
         if self.world > 1:
             raise ValueError("refine_poses_silhouette runs on one rank (the poses of all frames are optimised jointly)")
@@ -1024,6 +1061,13 @@ class Runner:
         if unknown:
             raise ValueError(f"refine_poses_silhouette: unknown pose_sil setting(s) {unknown}; known: {sorted(POSE_SIL_DEFAULTS)}")
         pc.update({k: v for k, v in overrides.items() if v is not None})
+        pp = dict(POSE_PHOTO_DEFAULTS)
+        pp.update(self.conf.get("pose_photo") or {})
+        unknown = sorted(set(pp) - set(POSE_PHOTO_DEFAULTS))
+        pmode = photo if photo is not None else pp["mode"]
+        if unknown or pmode not in PHOTO_MODES:
+            raise ValueError(f"refine_poses_silhouette: pose_photo mode {pmode!r} (one of {PHOTO_MODES}), unknown setting(s) {unknown}; "
+                             f"known: {sorted(POSE_PHOTO_DEFAULTS)}")
         vc = dict(MESH_VIS_DEFAULTS)
         vc.update(self.conf.get("mesh_vis") or {})
         mesh = mesh if mesh is not None else vc["mesh"]
@@ -1037,9 +1081,12 @@ class Runner:
         res = refine_poses(verts, faces, self.dataset, iters=pc["iters"], lr=pc["lr"], rot_lr_mult=pc["rot_lr_mult"],
                            sigma_px=pc["sigma_px"], sigma_end_px=pc["sigma_end_px"], cut=pc["cut"], edge_offset_px=pc["edge_offset_px"],
                            lw_sil=pc["lw_sil"], lw_smooth=pc["lw_smooth"], frame_chunk=pc["frame_chunk"], report_freq=pc["report_freq"],
-                           frames=frames)
+                           frames=frames, lw_photo=float(pp["lw_photo"]),
+                           photo=None if pmode == "none" else self._photo_term(pmode, pp, verts, faces, mesh, cmode, smode))
         res.pop("R"); res.pop("T")
         res.update(iter=self.iter_step, mesh=name, clean=cmode, faces=int(faces.shape[0]))
+        if pmode != "none":
+            res.update(photo=pmode)
         if smode != "none":
             res.update(simplify=smode)
         if self.pose_refiner is not None:
@@ -1063,6 +1110,8 @@ class Runner:
             for st in res["curve"]:
                 for k in ("loss", "loss_sil", "loss_smooth", "iou_mean", "iou_min", "sigma"):
                     self._board.add_scalar("pose_sil/" + k, float(st[k]), int(st["iter"]))
+                if "loss_photo" in st:
+                    self._board.add_scalar("pose/loss_photo", float(st["loss_photo"]), int(st["iter"]))
             for k in ("iou_mean_before", "iou_mean_after"):
                 if res[k] is not None:
                     self._board.add_scalar("pose_sil/" + k, float(res[k]), self.iter_step)

@@ -613,6 +613,45 @@ int dh_sil_loss_grad(const uint64_t* near, const float* verts, int64_t nv, const
                      const float* T, const float* K, const float* d2_obj, const float* d2_hand, const int8_t* label, int64_t n_frames,
                      int H, int W, float sigma, float cut, float edge_offset, double* out, void* ws, void* stream);
 
+/* ---- photometric pose term (dynhor_amd/pose_photo.py: coloured surface points aligned to blurred frames, next to the silhouette) ----
+ * Projection and pixel centres are dh_mesh_raster_depth's; the view test is dh_mesh_bake_colors's (the same fp32 code).
+ *
+ * dh_image_blur: a masked, normalised, separable Gaussian.  rgb u8 [n_frames,H,W,3], usable u8 [n_frames,H,W] (object pixels, eroded:
+ * mesh_color.usable_map), taps f32 [2 radius + 1] (the host forms exp(-k^2 / 2 sigma^2) / sum in fp64 and rounds once; the kernel
+ * evaluates no exponential) -> out f32 [n_frames,H,W,4].  With v = usable ? (r / 255, g / 255, b / 255, 1) : 0 and 0 outside the image:
+ * rows tmp[f,y,x] = sum_k taps[k + radius] v[f,y,x+k], columns s = sum_k taps[k + radius] tmp[f,y+k,x], both over k = -radius..radius
+ * in ascending order as acc = fma(tap, value, acc) in fp32; out = (s.rgb / s.a, s.a), all four 0 where s.a == 0.  radius 0 with the tap
+ * 1 is the identity (usable ? rgb / 255 : 0, usable).  tmp f32 [n_frames,H,W,4] is the caller's and must not overlap out; both 16-byte
+ * aligned.  Every frame is worked on alone: bitwise the same from launch to launch and for every split of the frames into calls.
+ * n_frames == 0: no-op.  DH_ERR_BAD_ARG: null pointer, misaligned or overlapping tmp / out, negative n_frames or radius, H or W < 1.
+ * DH_ERR_UNSUPPORTED: radius > 64, n_frames * H >= 2^31, W > 65535 * 256, H or W > 2^24.
+ *
+ * dh_photo_loss_grad: out f64 [n_frames, dh_photo_loss_sums() = 16] for the surface points pts f32 [n_points,3] with unit normals
+ * [n_points,3] and colours [n_points,3] in 0..1 (object frame), img f32 [n_frames,H,W,4] from dh_image_blur (16-byte aligned) and zbuf
+ * u64 [n_frames,H,W] from dh_mesh_raster_depth for the same mesh, poses and image size.  A (point, frame) pair contributes when, in
+ * fp32 and by dh_mesh_bake_colors's code: z > 1e-3; the nearest pixel (floor(u + 0.5), floor(w + 0.5)) lies in the image; zbuf is not
+ * empty there and z <= depth(zbuf) + depth_eps; cos = <n, normalize(C_f - p)> >= min_cos; with x0 = floor(u), y0 = floor(w) the taps
+ * (x0..x0+1, y0..y0+1) lie in the image; and every tap has a >= a_min.  A contributing pair recomputes x_cam, u, w, fx = u - x0,
+ * fy = w - y0 and cos in fp64 from the fp32 inputs:
+ *   I = (1-fy)((1-fx) I00 + fx I10) + fy((1-fx) I01 + fx I11) per channel,  e = I - colour,
+ *   rho = sum_channels huber(e), huber(x) = x^2 / 2 for |x| <= delta, else delta (|x| - delta / 2);  weight om = cos, constant in the gradient;
+ *   dI/du = (1-fy)(I10 - I00) + fy(I11 - I01), dI/dw = (1-fx)(I01 - I00) + fx(I11 - I10); g = om sum_channels huber'(e) (dI/du, dI/dw),
+ *   then through du/dx_cam = (K00, K01, K02 - u) / z (dw alike) to G = d/dx_cam.
+ *   [0] sum om rho   [1] sum om   [2..10] sum G p^T row-major (d/dR_f)   [11..13] sum G (d/dT_f)   [14] pairs   [15] pairs with every |e| <= delta
+ * ws: dh_photo_loss_grad_workspace(n_frames, n_points) bytes, 16-byte aligned: every workgroup stores its partial and a second kernel
+ * adds them in block order (no float atomics); the workgroups of a frame depend on n_points alone, so out is bitwise reproducible from
+ * launch to launch and for every split of the frames into calls.  n_frames == 0: no-op; n_points == 0: out is zeroed.
+ * DH_ERR_BAD_ARG: null pointer (ws included; pts, normals, colors, img, zbuf may be null with n_points == 0), misaligned img or ws,
+ * negative count, H or W < 1, depth_eps or a_min negative, delta not > 0, NaN.  DH_ERR_UNSUPPORTED: n_points >= 2^31, n_frames > 65535,
+ * H or W > 2^24. */
+int dh_image_blur(const uint8_t* rgb, const uint8_t* usable, int64_t n_frames, int H, int W, const float* taps, int radius, float* tmp,
+                  float* out, void* stream);
+int dh_photo_loss_sums(void);
+int64_t dh_photo_loss_grad_workspace(int64_t n_frames, int64_t n_points);
+int dh_photo_loss_grad(const float* pts, const float* normals, const float* colors, int64_t n_points, const float* img,
+                       const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
+                       float depth_eps, float min_cos, float a_min, float delta, double* out, void* ws, void* stream);
+
 /* ---- pose initialisation by silhouette retrieval (dynhor_amd/pose_init.py: a bank of views of a template, retrieval per frame) ----
  * Integer kernels without float atomics: every output is bitwise the same from launch to launch and for every split of the images,
  * frames or views into calls.  Pixel centres are integers, as for dh_mesh_raster_depth.
