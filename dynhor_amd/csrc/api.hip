@@ -879,6 +879,33 @@ int dh_photo_loss_grad(const float* pts, const float* normals, const float* colo
                                   out, ws, static_cast<hipStream_t>(stream));
 }
 
+int dh_match_gray(const float* img, int64_t n_frames, int H, int W, float a_min, uint8_t* gray, uint8_t* valid, void* stream) {
+    const int rc = sil_args(n_frames, H, W);
+    if (rc != DH_OK) return rc;
+    if (a_min != a_min) return DH_ERR_BAD_ARG;
+    if (n_frames * H * W >= ((int64_t)1 << 38)) return DH_ERR_UNSUPPORTED;                             // one 1-D grid of 256 pixels per workgroup
+    if (n_frames == 0) return DH_OK;
+    if (!img || !gray || !valid || misaligned16(img)) return DH_ERR_BAD_ARG;
+    return launch_match_gray(img, n_frames * H * W, a_min, gray, valid, static_cast<hipStream_t>(stream));
+}
+
+int dh_match_search(const uint8_t* gray, const uint8_t* valid, int64_t n_frames, int H, int W, const int32_t* queries, int64_t n, int P,
+                    int R, int excl, int64_t min_va, int32_t* out_i, double* out_f, void* stream) {
+    if (n < 0) return DH_ERR_BAD_ARG;
+    const int rc = sil_args(n_frames, H, W);
+    if (rc != DH_OK) return rc;
+    if (P < 1 || P > match_max_patch() || R < 0 || R > match_max_range() || excl < 0 || min_va < 1) return DH_ERR_BAD_ARG;
+    if (n >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;                                          // one workgroup per query
+    if (n == 0) return DH_OK;
+    if (!gray || !valid || !queries || !out_i || !out_f || (reinterpret_cast<uintptr_t>(out_f) & 7u) != 0 ||
+        (reinterpret_cast<uintptr_t>(out_i) & 3u) != 0 || (reinterpret_cast<uintptr_t>(queries) & 3u) != 0)
+        return DH_ERR_BAD_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int bad = match_check_frames(queries, n, n_frames, out_i, st);
+    if (bad != 0) return bad < 0 ? bad : DH_ERR_BAD_ARG;
+    return launch_match_search(gray, valid, H, W, queries, n, P, R, excl, min_va, out_i, out_f, st);
+}
+
 int dh_label_boxes(const int8_t* label, int64_t n, int H, int W, int32_t* boxes, void* stream) {
     const int rc = sil_args(n, H, W);
     if (rc != DH_OK) return rc;

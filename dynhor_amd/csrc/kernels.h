@@ -256,6 +256,16 @@ int launch_photo_loss_grad(const float* pts, const float* normals, const float* 
                            const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
                            float depth_eps, float min_cos, float a_min, float delta, double* out, void* ws, hipStream_t st);
 
+// dense frame matching (match.hip): 8-bit grey and validity of blurred frames, guided ZNCC block search per query (patch half-size
+// <= match_max_patch(), search range <= match_max_range()); match_check_frames waits for the stream: 0 = every query's frames lie in
+// [0, n_frames), 1 = one does not
+int match_max_patch();
+int match_max_range();
+int launch_match_gray(const float* img, int64_t n_pixels, float a_min, uint8_t* gray, uint8_t* valid, hipStream_t st);
+int match_check_frames(const int32_t* queries, int64_t n, int64_t n_frames, int32_t* scratch, hipStream_t st);
+int launch_match_search(const uint8_t* gray, const uint8_t* valid, int H, int W, const int32_t* queries, int64_t n, int P, int R,
+                        int excl, int64_t min_va, int32_t* out_i, double* out_f, hipStream_t st);
+
 // pose initialisation by silhouette retrieval (pose_init.hip): tight box of label == 1 per image, the label resampled on an S x S
 // square and packed one bit per sample (obj / keep planes), intersection / union counts of every frame against every bank view
 // (label_boxes_chunks / sil_bank_score_*_tiles: the grid sizes, for the limits)

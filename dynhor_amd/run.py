@@ -16,6 +16,8 @@
     python -m dynhor_amd.run --config_path X.yaml --mode init_poses --vis_mesh template.obj --vis_normalize reference   # poses from masks
     python -m dynhor_amd.run --config_path X.yaml --mode init_sdf --vis_mesh template.obj --vis_normalize reference     # SDF warm start
     python -m dynhor_amd.run --config_path X.yaml --mode init_sdf --mesh_simplify faces:5000   # template: data_info.obj_path, simplified
+    python -m dynhor_amd.run --config_path X.yaml --mode match_frames --match_offsets 1,2,5   # correspondence_infos from the frames
+    python -m dynhor_amd.run --config_path X.yaml --mode match_frames --is_continue --match_guide mesh   # guided by the reconstruction
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode render_views --is_continue   # every frame sphere-traced: png, normal, depth, PSNR, IoU
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode render_views --is_continue --views orbit:36 --view_level 2
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode interpolate_0_38 --is_continue   # upstream's video: volume rendering, level 2
@@ -30,7 +32,7 @@ import sys
 
 
 MODES = ("train", "validate_image", "validate_mesh", "evaluate_mesh", "visualize_mesh", "refine_poses", "export_poses", "init_poses",
-         "init_sdf", "render_views")
+         "init_sdf", "render_views", "match_frames")
 
 
 def mode_arg(value: str) -> str:
@@ -41,7 +43,7 @@ def mode_arg(value: str) -> str:
     raise argparse.ArgumentTypeError(f"invalid choice: {value!r} (choose from {', '.join(MODES)}, interpolate_<i>_<j>)")
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config_path", type=str, required=True)
     ap.add_argument("--mode", type=mode_arg, default="train", metavar="{" + ",".join(MODES) + ",interpolate_<i>_<j>}")
@@ -87,7 +89,8 @@ def main():
     # visualize_mesh only (defaults: the config's mesh_vis: block, else the reconstruction at --mesh_resolution, no turntable)
     ap.add_argument("--vis_mesh", type=str, default=None,
                     help="visualize_mesh: draw this mesh (.ply / .obj; an .obj with a texture is drawn with it) instead of the "
-                         "reconstruction; refine_poses: fit the poses to it; init_poses / init_sdf: the template (default: the config's "
+                         "reconstruction; refine_poses: fit the poses to it; match_frames --match_guide mesh: the guide; init_poses / init_sdf: "
+                         "the template (default: the config's "
                          "data_info.obj_path with normalize_mesh)")
     ap.add_argument("--vis_normalize", type=str, default=None, choices=["none", "reference"],
                     help="visualize_mesh: 'reference' = bring --vis_mesh into the canonical frame (mean 0, max vertex norm 0.5)")
@@ -107,7 +110,19 @@ def main():
                     help="render_views: sphere-trace the SDF (colour, depth and normal maps) or volume-render (interpolate_<i>_<j>: "
                          "volume unless given)")
     ap.add_argument("--view_background", type=str, default=None, choices=["white", "black", "frame"])
-    args = ap.parse_args()
+    # match_frames only (defaults: the config's match: block; with --match_guide mesh the mesh is chosen by --vis_mesh / --vis_normalize /
+    # --mesh_resolution as for refine_poses, cleaned, extracted and simplified as the config's mesh_* blocks say)
+    ap.add_argument("--match_guide", type=str, default=None, choices=["none", "mesh"],
+                    help="match_frames: where a query's guess comes from: 'none' = the displacement of the object's box between the two "
+                         "frames, 'mesh' = the mesh at the current poses (default: the config's match.guide, else none)")
+    ap.add_argument("--match_offsets", type=str, default=None,
+                    help="match_frames: frame i is matched to i + every offset of this comma-separated list (default: the config's "
+                         "match.offsets, else 1,2,5)")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
 
     from . import launch
     if args.gpus > 1 and not launch.launched_by_torchrun():
@@ -173,6 +188,13 @@ def main():
         if runner.rank == 0:
             import json
             print(json.dumps({k: v for k, v in res.items() if k != "loss"}), flush=True)
+    elif args.mode == "match_frames":
+        res = runner.match_frames(guide=args.match_guide, offsets=args.match_offsets, mesh=args.vis_mesh, normalize=args.vis_normalize,
+                                  resolution=args.mesh_resolution)
+        runner.close()
+        if runner.rank == 0:
+            import json
+            print(json.dumps({k: v for k, v in res.items() if k not in ("pairs", "steps")}), flush=True)
     elif args.mode == "render_views" or args.mode.startswith("interpolate_"):
         if args.mode == "render_views":
             views, level, method = args.views, args.view_level, args.view_method

@@ -22,6 +22,7 @@ from . import dist as dh_dist
 from . import schedules
 from .dataset import Dataset
 from .fields import ParamStore, RenderingNetwork, SDFNetwork, SingleVarianceNetwork
+from .match import DEFAULTS as MATCH_DEFAULTS
 from .mesh_extract import DEFAULT_LIPSCHITZ
 from .pose_init import DEFAULTS as POSE_INIT_DEFAULTS
 from .pose_photo import DEFAULTS as POSE_PHOTO_DEFAULTS
@@ -66,6 +67,9 @@ DEFAULT_CONF = {
     # SDF warm start from a template mesh (--mode init_sdf): dynhor_amd/sdf_init.py says what each number is, DESIGN_NEXT_ROWS.md
     # section 18 where it comes from
     "sdf_init": dict(SDF_INIT_DEFAULTS),
+    # dense frame matching (--mode match_frames): dynhor_amd/match.py says what each number is, DESIGN_NEXT_ROWS.md section 20 where it
+    # comes from; guide none | mesh
+    "match": dict(MATCH_DEFAULTS),
 }
 
 
@@ -206,6 +210,7 @@ class Runner:
         self.last_vis_dir = None         # visualize_mesh: the render_res/<iter> directory it wrote
         self.last_pose_dir = None        # refine_poses_silhouette / export_poses: the directory the .npz files went to
         self.last_view_dir = None        # render_views: the novel_views/<iter> directory it wrote
+        self.last_match_dir = None       # match_frames: the correspondences directory it wrote
         if is_continue:
             ck_dir = os.path.join(self.base_exp_dir, "checkpoints")
             ck = sorted(f for f in os.listdir(ck_dir) if f.endswith(".pth")) if os.path.isdir(ck_dir) else []
@@ -1182,6 +1187,68 @@ class Runner:
             for key in ("iou_fit_mean", "iou_final_mean"):
                 if res[key] is not None:
                     self._board.add_scalar("init/" + key, float(res[key]), self.iter_step)
+            self._board.flush()
+        return res
+
+    @torch.no_grad()
+    def match_frames(self, guide=None, offsets=None, mesh=None, normalize=None, resolution=None, clean=None, extract=None, simplify=None,
+                     save=True, **overrides):
+        """Dense correspondences between the frames by guided block matching (dynhor_amd/match.py), set on the dataset
+        (Dataset.set_correspondences), so that a run in the same process can train on them (train.corr_weight).  guide: None (the
+        config's match.guide) | "none" (the guess is the displacement of the object's box) | "mesh" (the guess comes from a mesh at the
+        dataset's current poses, chosen as refine_poses_silhouette chooses it: _select_mesh with `mesh`, `normalize`, `resolution`
+        (default pose_sil.resolution), `clean`, `extract`, `simplify`).  offsets: a list or "1,2,5"; overrides: any key of the config's
+        match: block.  Rank 0 writes <exp>/correspondences/correspondence_infos/<stem_i>_<stem_j>.npz
+        (scene.write_correspondences_to_disk with the dataset's stems; point data_info.correspondence_infos at that folder) and
+        <exp>/correspondences/match.json (settings, per pair queries / searched / kept and the count lost to each gate, mean s1, with a
+        mesh the median distance of the kept matches from the guide, totals, seconds), and logs match/kept and match/kept_share to
+        <exp>/board.  Returns the dict of match.json plus dir (single process: run it on one rank)."""
+        from .match import match_frames
+        from .scene import write_correspondences_to_disk
+        if self.world > 1:
+            raise ValueError("match_frames runs on one rank")
+        unknown = sorted(set(overrides) - set(MATCH_DEFAULTS))
+        if unknown:
+            raise ValueError(f"match_frames: unknown match setting(s) {unknown}; known: {sorted(MATCH_DEFAULTS)}")
+        mc = dict(self.conf.get("match") or {})
+        mc.update({k: v for k, v in overrides.items() if v is not None})
+        if guide is not None:
+            mc["guide"] = guide
+        if offsets is not None:
+            mc["offsets"] = offsets
+        verts = faces = name = None
+        if (mc.get("guide") or MATCH_DEFAULTS["guide"]) == "mesh":
+            pc = dict(POSE_SIL_DEFAULTS)
+            pc.update(self.conf.get("pose_sil") or {})
+            vc = dict(MESH_VIS_DEFAULTS)
+            vc.update(self.conf.get("mesh_vis") or {})
+            mesh = mesh if mesh is not None else vc["mesh"]
+            normalize = normalize if normalize is not None else vc["normalize"]
+            resolution = int(resolution if resolution is not None else pc["resolution"])
+            verts, faces, name, _ = self._select_mesh("match_frames", mesh, normalize, resolution, clean, extract, simplify)
+            if faces.shape[0] == 0:
+                raise ValueError(f"match_frames: the mesh {name} has no faces")
+            verts, faces = verts.to(torch.float32).contiguous(), faces.to(torch.int64).contiguous()
+        matches, res = match_frames(self.dataset, verts, faces, **mc)
+        res.update(iter=self.iter_step, mesh=name)
+        self.dataset.set_correspondences(matches)
+        if save and self.rank == 0:
+            d = os.path.join(self.base_exp_dir, "correspondences")
+            cdir = os.path.join(d, "correspondence_infos")
+            if os.path.isdir(cdir):                        # a pair that kept nothing this time must not leave an older file behind
+                for f in os.listdir(cdir):
+                    if f.endswith(".npz"):
+                        os.remove(os.path.join(cdir, f))
+            write_correspondences_to_disk(matches, d, self.dataset.stems)
+            with open(os.path.join(d, "match.json"), "w") as f:
+                json.dump(res, f, indent=1)
+            res["dir"] = d
+            self.last_match_dir = d
+            if self._board is None:
+                from .tb_events import make_writer
+                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+            self._board.add_scalar("match/kept", float(res["totals"]["kept"]), self.iter_step)
+            self._board.add_scalar("match/kept_share", float(res["totals"]["kept_share"]), self.iter_step)
             self._board.flush()
         return res
 

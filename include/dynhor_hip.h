@@ -652,6 +652,37 @@ int dh_photo_loss_grad(const float* pts, const float* normals, const float* colo
                        const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
                        float depth_eps, float min_cos, float a_min, float delta, double* out, void* ws, void* stream);
 
+/* ---- dense frame matching (dynhor_amd/match.py: guided block matching by zero-mean normalised cross-correlation, ZNCC) ----
+ * Integer sums, fp64 scores, no atomics in the search: every output is bitwise the same from launch to launch, for every order of the
+ * queries and for every split of them into calls.  Pixel centres are integers; x is the column.
+ *
+ * dh_match_gray: img f32 [n_frames,H,W,4] = (r, g, b, a) from dh_image_blur (16-byte aligned) -> gray u8 [n_frames,H,W] and valid u8
+ * [n_frames,H,W]:  valid = a >= a_min;  gray = valid ? min(max(floor(fma(255, fma(0.114f, b, fma(0.587f, g, 0.299f * r)), 0.5f)), 0),
+ * 255) : 0, every operation an fp32 IEEE operation as written.  n_frames == 0: no-op.  DH_ERR_BAD_ARG: null pointer, misaligned img,
+ * negative n_frames, H or W < 1, NaN a_min.  DH_ERR_UNSUPPORTED: H or W > 2^24, n_frames H W >= 2^38.
+ *
+ * dh_match_search: queries int32 [n,6] = (fi, fj, px, py, gx, gy): the patch about (px, py) of frame fi is searched for in frame fj
+ * about the guess (gx, gy).  P in 1..7 is the patch half-size (N = (2P+1)^2 pixels), R in 0..32 the search range, excl >= 0, min_va >= 1.
+ * A pixel outside the image is invalid; the guess is not clamped; fi == fj is allowed.  With a the source patch and b a candidate's:
+ *   source: usable when all N pixels are valid and va = N sum a^2 - (sum a)^2 >= min_va; otherwise flags = 1 and nothing is searched.
+ *   candidate (dx, dy), |dx|, |dy| <= R: the patch about (gx + dx, gy + dy); valid when all N pixels are valid and
+ *     vb = N sum b^2 - (sum b)^2 >= min_va.  num = N sum ab - sum a sum b; the sums are exact integers (sum ab in 32 bits; num, va, vb
+ *     in 64), score = (double)num / sqrt((double)va * (double)vb): one multiply, one square root, one divide, each rounded once.
+ *   selection: the best score wins, a tie goes to the smallest c = (dy + R)(2R + 1) + (dx + R).  s2 = the best score among the valid
+ *     candidates with max(|dx - dx*|, |dy - dy*|) > excl, -2 when there is none.  No valid candidate: flags = 2.  The best on the
+ *     border of the window (|dx*| == R or |dy*| == R): flags = 4.
+ *   sub-pixel step per axis from the scores m, p of the best's two neighbours along it and its own c: den = m - 2 c + p,
+ *     sub = min(max(0.5 (m - p) / den, -0.5), 0.5) when den < 0 and both neighbours are valid candidates inside the window, else 0.
+ * out_i int32 [n,4] = (qx, qy, flags, valid candidates), (qx, qy) = (gx + dx*, gy + dy*); out_f f64 [n,4] (8-byte aligned) =
+ * (s1, s2, sub_x, sub_y).  With flags 1 or 2: (gx, gy, flags, 0) and (-2, -2, 0, 0).
+ * The frame indices are checked on the device before the search and the verdict is read back: the call waits for the stream once
+ * (out_i's first word is the scratch).  n == 0: no-op.
+ * DH_ERR_BAD_ARG: null pointer, misaligned queries / out_i / out_f, negative count, H or W < 1, P outside 1..7, R outside 0..32,
+ * excl < 0, min_va < 1, a frame index outside [0, n_frames).  DH_ERR_UNSUPPORTED: n or n_frames >= 2^31, H or W > 2^24. */
+int dh_match_gray(const float* img, int64_t n_frames, int H, int W, float a_min, uint8_t* gray, uint8_t* valid, void* stream);
+int dh_match_search(const uint8_t* gray, const uint8_t* valid, int64_t n_frames, int H, int W, const int32_t* queries, int64_t n, int P,
+                    int R, int excl, int64_t min_va, int32_t* out_i, double* out_f, void* stream);
+
 /* ---- pose initialisation by silhouette retrieval (dynhor_amd/pose_init.py: a bank of views of a template, retrieval per frame) ----
  * Integer kernels without float atomics: every output is bitwise the same from launch to launch and for every split of the images,
  * frames or views into calls.  Pixel centres are integers, as for dh_mesh_raster_depth.
