@@ -906,6 +906,39 @@ int dh_match_search(const uint8_t* gray, const uint8_t* valid, int64_t n_frames,
     return launch_match_search(gray, valid, H, W, queries, n, P, R, excl, min_va, out_i, out_f, st);
 }
 
+int dh_ssim_sums(void) { return ssim_sums(); }
+
+// the scalar arguments dh_ssim_workspace and dh_ssim share
+static int ssim_args(int64_t n_frames, int H, int W) {
+    if (n_frames < 0 || H <= 0 || W <= 0) return DH_ERR_BAD_ARG;
+    if (H > (1 << 24) || W > (1 << 24) || n_frames > 65535) return DH_ERR_UNSUPPORTED;             // grid (tiles, frames)
+    if (ssim_tiles_per_frame(H, W) >= ((int64_t)1 << 22)) return DH_ERR_UNSUPPORTED;
+    return DH_OK;
+}
+
+int64_t dh_ssim_workspace(int64_t n_frames, int H, int W) {
+    const int rc = ssim_args(n_frames, H, W);
+    if (rc != DH_OK) return rc;
+    return ssim_workspace(n_frames, H, W);
+}
+
+int dh_ssim(const uint8_t* a, const uint8_t* b, const uint8_t* usable, int64_t n_frames, int H, int W, const int32_t* taps_host,
+            int radius, uint64_t w_min, float* map, double* out, void* ws, void* stream) {
+    if (n_frames < 0 || H <= 0 || W <= 0 || radius < 0 || w_min == 0 || w_min > ((uint64_t)1 << 32)) return DH_ERR_BAD_ARG;
+    const int rc = ssim_args(n_frames, H, W);
+    if (rc != DH_OK) return rc;
+    if (radius > ssim_max_radius()) return DH_ERR_UNSUPPORTED;
+    if (n_frames == 0) return DH_OK;
+    if (!a || !b || !taps_host || !out || !ws || misaligned16(ws)) return DH_ERR_BAD_ARG;
+    int64_t sum = 0;
+    for (int k = 0; k < 2 * radius + 1; ++k) {
+        if (taps_host[k] < 0) return DH_ERR_BAD_ARG;
+        sum += taps_host[k];
+    }
+    if (sum != 65536) return DH_ERR_BAD_ARG;                                                         // the row sums rest on it
+    return launch_ssim(a, b, usable, n_frames, H, W, taps_host, radius, w_min, map, out, ws, static_cast<hipStream_t>(stream));
+}
+
 int dh_label_boxes(const int8_t* label, int64_t n, int H, int W, int32_t* boxes, void* stream) {
     const int rc = sil_args(n, H, W);
     if (rc != DH_OK) return rc;

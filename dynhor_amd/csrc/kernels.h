@@ -266,6 +266,16 @@ int match_check_frames(const int32_t* queries, int64_t n, int64_t n_frames, int3
 int launch_match_search(const uint8_t* gray, const uint8_t* valid, int H, int W, const int32_t* queries, int64_t n, int P, int R,
                         int excl, int64_t min_va, int32_t* out_i, double* out_f, hipStream_t st);
 
+// image metrics (image_metrics.hip): masked SSIM of u8 images with integer window sums and an fp64 formula, squared / absolute error
+// sums of the usable pixels (ssim_sums() doubles per frame, ws = ssim_workspace bytes; radius <= ssim_max_radius(); taps_host is read
+// on the host and passed to the kernel by value; ssim_tiles_per_frame: the grid size, for the limit)
+int ssim_sums();
+int ssim_max_radius();
+int64_t ssim_tiles_per_frame(int H, int W);
+int64_t ssim_workspace(int64_t n_frames, int H, int W);
+int launch_ssim(const uint8_t* a, const uint8_t* b, const uint8_t* usable, int64_t n_frames, int H, int W, const int32_t* taps_host,
+                int radius, uint64_t w_min, float* map, double* out, void* ws, hipStream_t st);
+
 // pose initialisation by silhouette retrieval (pose_init.hip): tight box of label == 1 per image, the label resampled on an S x S
 // square and packed one bit per sample (obj / keep planes), intersection / union counts of every frame against every bank view
 // (label_boxes_chunks / sil_bank_score_*_tiles: the grid sizes, for the limits)

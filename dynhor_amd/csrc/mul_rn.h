@@ -12,4 +12,11 @@ __device__ __forceinline__ float mul_rn(float a, float b) {
     return r;
 }
 
+// the same for doubles (image_metrics.hip: an fp64 formula that a numpy restatement repeats bit for bit)
+__device__ __forceinline__ double mul_rn(double a, double b) {
+    double r;
+    asm("v_mul_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
 }  // namespace dh

@@ -20,6 +20,8 @@
     python -m dynhor_amd.run --config_path X.yaml --mode match_frames --is_continue --match_guide mesh   # guided by the reconstruction
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode render_views --is_continue   # every frame sphere-traced: png, normal, depth, PSNR, IoU
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode render_views --is_continue --views orbit:36 --view_level 2
+    python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode evaluate_views --is_continue   # masked SSIM, PSNR, L1 of the held-out frames
+    python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode evaluate_views --is_continue --eval_frames all --eval_maps
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode interpolate_0_38 --is_continue   # upstream's video: volume rendering, level 2
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode interpolate_0_38 --is_continue --view_method surface
 
@@ -32,7 +34,7 @@ import sys
 
 
 MODES = ("train", "validate_image", "validate_mesh", "evaluate_mesh", "visualize_mesh", "refine_poses", "export_poses", "init_poses",
-         "init_sdf", "render_views", "match_frames")
+         "init_sdf", "render_views", "match_frames", "evaluate_views")
 
 
 def mode_arg(value: str) -> str:
@@ -110,6 +112,13 @@ def build_parser():
                     help="render_views: sphere-trace the SDF (colour, depth and normal maps) or volume-render (interpolate_<i>_<j>: "
                          "volume unless given)")
     ap.add_argument("--view_background", type=str, default=None, choices=["white", "black", "frame"])
+    # evaluate_views only (defaults: the config's image_eval: block; the pictures are drawn as --view_level / --view_method /
+    # --view_background and the surface_render: block say)
+    ap.add_argument("--eval_frames", type=str, default=None,
+                    help="evaluate_views: the frames that are scored: auto (the frames of train.holdout if there are any, else all), "
+                         "all, train, holdout, every:K[:offset] or stems a,b,c (default: the config's image_eval.frames, else auto)")
+    ap.add_argument("--eval_maps", action="store_true", default=None,
+                    help="evaluate_views: also write <name>_ssim.png, the per-pixel SSIM in grey (black: not counted)")
     # match_frames only (defaults: the config's match: block; with --match_guide mesh the mesh is chosen by --vis_mesh / --vis_normalize /
     # --mesh_resolution as for refine_poses, cleaned, extracted and simplified as the config's mesh_* blocks say)
     ap.add_argument("--match_guide", type=str, default=None, choices=["none", "mesh"],
@@ -208,6 +217,12 @@ def main():
             import json
             print(json.dumps({k: v for k, v in res.items() if k not in ("rgb", "depth", "normal", "hit", "names", "psnr", "iou")}),
                   flush=True)
+    elif args.mode == "evaluate_views":
+        res = runner.evaluate_views(frames=args.eval_frames, maps=args.eval_maps, level=args.view_level, method=args.view_method,
+                                    background=args.view_background)
+        if runner.rank == 0:
+            import json
+            print(json.dumps({k: v for k, v in res.items() if k not in ("frames", "map")}), flush=True)
     elif args.mode == "export_poses":
         d = runner.export_poses(args.pose_dir)
         if runner.rank == 0:

@@ -37,6 +37,9 @@ DEFAULT_CONF = {
               "warm_up_end": 5000, "anneal_end": 50000, "igr_weight": 0.1, "mask_weight": 0.1, "normal_weight": 0.0,
               "save_freq": 10000, "val_freq": 2500, "report_freq": 100, "use_white_bkgd": False, "keep_only": False,
               "seed": 1234, "ray_seed": 4321,
+              # frames kept out of training, to score renderings on (--mode evaluate_views): none | every:K[:offset] | a list of stems;
+              # a held-out frame keeps its input pose
+              "holdout": "none",
               # roctx: put every C-ABI stage call into a ROCm marker range (rocprofv3 --marker-trace); off by default
               "roctx": False,
               # full loss stack (BASELINE.json configs[4]): dense-correspondence reprojection term, DESIGN.md section 9
@@ -87,6 +90,12 @@ MESH_COLOR_DEFAULTS = {"mode": "none", "erode_px": 1, "min_cos": 0.1, "depth_eps
 # until the two settings have been timed on a GPU: DESIGN_NEXT_ROWS.md section 17)
 SURFACE_RENDER_DEFAULTS = {"method": "surface", "level": 1, "background": "white", "eps": 2e-4, "relax": 0.8, "min_step": 1e-3,
                            "max_step": 0.1, "refine_steps": 8, "max_steps": 48, "scan_step": 0.01, "compact_every": 1}
+
+# the optional image_eval: block of the YAML (evaluate_views; dynhor_amd/image_metrics.py): frames auto (the held-out frames if there are
+# any, else all) | all | train | holdout | every:K[:offset] | stems; sigma / radius = the SSIM window (the usual 11 x 11 Gaussian);
+# min_weight = the share of the window's weight that must lie on usable pixels for a pixel to count; erode_px as in mesh_color; maps:
+# also write <name>_ssim.png
+IMAGE_EVAL_DEFAULTS = {"frames": "auto", "sigma": 1.5, "radius": 5, "min_weight": 0.5, "erode_px": 0, "maps": False}
 
 # the optional mesh_texture: block of the YAML (validate_mesh; dynhor_amd/mesh_texture.py): mode none | views | views+network, size = the
 # atlas edge in texels; erode_px / min_cos / depth_eps as in mesh_color; sharpen: the weight is cos^(2^sharpen); image: png | jpg
@@ -197,7 +206,12 @@ class Runner:
             self.pose_start_iter = tr["pose_start_iter"]
         self.ray_gen = torch.Generator(device=self.device)
         self.ray_gen.manual_seed(tr["ray_seed"] * 1000003 + self.rank)
-        self.frame_perm = schedules.FramePermutation(self.dataset.n_images, tr["ray_seed"])   # same on every rank
+        self.train_frames, self.holdout_frames = schedules.split_holdout(tr["holdout"], self.dataset.n_images, self.dataset.stems)
+        if self.holdout_frames and self.corr_weight > 0.0:
+            raise ValueError("train.holdout with train.corr_weight > 0 is not supported: a correspondence pair would pull rays from a "
+                             "held-out frame into the loss")
+        self.frame_perm = schedules.FramePermutation(self.dataset.n_images, tr["ray_seed"],    # same on every rank
+                                                     frames=self.train_frames if self.holdout_frames else None)
         self.scalars = []
         self._board = None
         self.last_clean_stats = None     # validate_mesh / evaluate_mesh with cleaning: mesh_clean.clean_mesh's counts
@@ -211,6 +225,7 @@ class Runner:
         self.last_pose_dir = None        # refine_poses_silhouette / export_poses: the directory the .npz files went to
         self.last_view_dir = None        # render_views: the novel_views/<iter> directory it wrote
         self.last_match_dir = None       # match_frames: the correspondences directory it wrote
+        self.last_eval_dir = None        # evaluate_views: the image_eval/<iter> directory it wrote
         if is_continue:
             ck_dir = os.path.join(self.base_exp_dir, "checkpoints")
             ck = sorted(f for f in os.listdir(ck_dir) if f.endswith(".pth")) if os.path.isdir(ck_dir) else []
@@ -220,7 +235,7 @@ class Runner:
     # ------------------------------------------------------------------ schedules (App. A.8)
     @property
     def image_perm(self):
-        """Upstream name of the current epoch's frame permutation."""
+        """Upstream name of the current epoch's frame permutation (with train.holdout: of the positions in train_frames)."""
         return self.frame_perm.perm
 
     def get_cos_anneal_ratio(self):
@@ -237,7 +252,7 @@ class Runner:
     def frame_for_slot(self, slot: int) -> int:
         """Frame of permutation slot `slot`: the permutation is re-drawn once per epoch (upstream re-permutes when
         iter_step % n_images == 0) from the SHARED perm_gen, so every rank holds the same e-th permutation for epoch e
-        whatever the world size."""
+        whatever the world size.  Never a frame of train.holdout."""
         return self.frame_perm.frame(slot)
 
     # ------------------------------------------------------------------ one iteration (the hot loop)
@@ -408,6 +423,8 @@ class Runner:
         path = checkpoint_name if os.path.isabs(checkpoint_name) or os.path.exists(checkpoint_name) else \
             os.path.join(self.base_exp_dir, "checkpoints", checkpoint_name)
         ck = torch.load(path, map_location=self.device, weights_only=False)
+        if ck.get("dynhor_rng") is not None:
+            self.frame_perm.check_state(ck["dynhor_rng"]["frame_perm"])   # another train.holdout: raise before anything is loaded
         self.sdf_network.load_state_dict(ck["sdf_network_fine"])
         self.deviation_network.load_state_dict(ck["variance_network_fine"])
         self.color_network.load_state_dict(ck["color_network_fine"])
@@ -885,6 +902,19 @@ class Runner:
         return torch.stack(rgbs), torch.stack(nrms)
 
     @torch.no_grad()
+    def _draw_views(self, c, R, T, frame_of):
+        """One chunk of views (R [V,3,3], T [V,3] float32 on the device) drawn as the surface_render settings `c` say: render_surface's
+        dict, or {"rgb", "normal"} for method volume.  frame_of: the views' frames (background frame), or None."""
+        from . import surface_render as sr
+        ds = self.dataset
+        if c["method"] == "surface":
+            targs = {k: c[k] for k in sr.TRACE_DEFAULTS}
+            return sr.render_surface(self.renderer, R, T, ds.K, ds.H, ds.W, level=int(c["level"]), background=c["background"],
+                                     frames=frame_of, frame_rgb=ds.rgb if c["background"] == "frame" else None, **targs)
+        rgb, normal = self._render_views_volume(R, T, int(c["level"]), c["background"])
+        return {"rgb": rgb, "normal": normal}
+
+    @torch.no_grad()
     def render_views(self, views="frames", level=None, method=None, background=None, save=True):
         """Pictures of the networks themselves from any pose (dynhor_amd/surface_render.py): views "frames" (every training frame at its
         current pose), "interpolate:i:j:n" (n poses from frame i to frame j and back, upstream's interpolate_<i>_<j> video) or "orbit:n"
@@ -926,15 +956,9 @@ class Runner:
         stats, psnr, iou = None, [], []
         for v0 in range(0, R.shape[0], per):
             v1 = min(R.shape[0], v0 + per)
+            out = self._draw_views(c, R[v0:v1], T[v0:v1], frame_of[v0:v1] if frame_of is not None else None)
             if surface:
-                targs = {k: c[k] for k in sr.TRACE_DEFAULTS}
-                out = sr.render_surface(self.renderer, R[v0:v1], T[v0:v1], ds.K, ds.H, ds.W, level=L, background=c["background"],
-                                        frames=frame_of[v0:v1] if frame_of is not None else None,
-                                        frame_rgb=ds.rgb if c["background"] == "frame" else None, **targs)
                 stats = sr.merge_stats(stats, out["stats"])
-            else:
-                rgb, normal = self._render_views_volume(R[v0:v1], T[v0:v1], L, c["background"])
-                out = {"rgb": rgb, "normal": normal}
             if score:
                 gt = ds.rgb[v0:v1, ::L, ::L].float() / 255.0
                 lab = ds.label[v0:v1, ::L, ::L]
@@ -985,6 +1009,123 @@ class Runner:
                 self._board.flush()
         self.last_view_dir = d if save else None
         return dict(res, dir=self.last_view_dir, **host)
+
+    # ------------------------------------------------------------------ renderings scored against the frames (image_metrics.py)
+    def _image_eval_conf(self, frames=None, maps=None):
+        """The YAML's optional image_eval: block over IMAGE_EVAL_DEFAULTS; arguments that are not None override it."""
+        block = self.conf.get("image_eval") or {}
+        unknown = sorted(set(block) - set(IMAGE_EVAL_DEFAULTS))
+        if unknown:
+            raise ValueError(f"image_eval: unknown keys {unknown}; known: {sorted(IMAGE_EVAL_DEFAULTS)}")
+        c = dict(IMAGE_EVAL_DEFAULTS)
+        c.update(block)
+        if frames is not None:
+            c["frames"] = frames
+        if maps is not None:
+            c["maps"] = bool(maps)
+        if isinstance(c["erode_px"], bool) or not isinstance(c["erode_px"], int) or c["erode_px"] < 0:
+            raise ValueError(f"image_eval erode_px must be an integer >= 0, got {c['erode_px']!r}")
+        return c
+
+    def eval_frame_indices(self, spec="auto"):
+        """Sorted frame indices of an image_eval.frames value: auto (the held-out frames if there are any, else all), all, train,
+        holdout, every:K[:offset] or frame names.  An empty selection raises."""
+        n = self.dataset.n_images
+        if spec == "auto":
+            idx = list(self.holdout_frames) if self.holdout_frames else list(range(n))
+        elif spec == "train":
+            idx = list(self.train_frames)
+        elif spec == "holdout":
+            idx = list(self.holdout_frames)
+        else:
+            idx = schedules.select_frames(spec, n, self.dataset.stems, "image_eval.frames")
+        if not idx:
+            raise ValueError(f"image_eval.frames {spec!r} selects no frame (train.holdout is {self.conf['train']['holdout']!r})")
+        return idx
+
+    @torch.no_grad()
+    def evaluate_views(self, frames=None, maps=None, level=None, method=None, background=None, save=True):
+        """Image metrics of the networks' renderings against the frames (dynhor_amd/image_metrics.py): the chosen frames are drawn at
+        their current poses as render_views draws them (surface_render: block or the arguments; chunks of at most
+        surface_render.MAX_RAYS rays) and scored against the frames' pixels 0, level, 2 level, ... over usable =
+        mesh_color.usable_map(label, erode_px) subsampled the same way: masked SSIM over the counted pixels, PSNR and L1 over the
+        usable ones (image_metrics.ssim_frames).  frames / maps: None takes the YAML's optional image_eval: block over
+        IMAGE_EVAL_DEFAULTS (eval_frame_indices says what `frames` may be).  A held-out frame (train.holdout) is scored at its input
+        pose.  Rank 0 writes image_eval/<iter:08d>/eval.json (settings, method, per frame name / split / psnr / ssim / ssim_std / l1 /
+        counted / usable, the means per split and overall, the five worst frames by SSIM) and, with maps, <name>_ssim.png (grey
+        clamp(s, 0, 1), black where the pixel is not counted), logs eval_img/{psnr,ssim}_{train,holdout} to <exp>/board and returns
+        the JSON's content plus `dir` and, with maps, `map` float32 [n,h,w] on the host (the other ranks return None)."""
+        from . import image_metrics as im
+        from . import surface_render as sr
+        from .mesh_color import usable_map
+        if self.rank != 0:
+            return None
+        ds = self.dataset
+        c = self._surface_conf(method, level, background)
+        ec = self._image_eval_conf(frames, maps)
+        idx = self.eval_frame_indices(ec["frames"])
+        names = schedules.frame_names(ds.n_images, ds.stems)
+        held = set(self.holdout_frames)
+        _, R64, T64, _ = sr.view_poses(("frames",), ds.R, ds.T)
+        R = R64.to(self.device, torch.float32).contiguous()
+        T = T64.to(self.device, torch.float32).contiguous()
+        L = int(c["level"])
+        h, w = sr.image_size(ds.H, ds.W, L)
+        per = max(1, sr.MAX_RAYS // (h * w))
+        d = os.path.join(self.base_exp_dir, "image_eval", "{:0>8d}".format(self.iter_step))
+        if save:
+            os.makedirs(d, exist_ok=True)
+        rows, host_maps = [], []
+        for v0 in range(0, len(idx), per):
+            sel = idx[v0:v0 + per]
+            st = torch.tensor(sel, dtype=torch.long, device=self.device)
+            out = self._draw_views(c, R[st].contiguous(), T[st].contiguous(), sel)
+            gt = ds.rgb[st][:, ::L, ::L].contiguous()
+            usable = usable_map(ds.label[st].contiguous(), ec["erode_px"])[:, ::L, ::L].contiguous()
+            r = im.ssim_frames(out["rgb"].contiguous(), gt, usable, sigma=ec["sigma"], radius=ec["radius"],
+                               min_weight=ec["min_weight"], want_map=ec["maps"], chunk=per)
+            for k, f in enumerate(sel):
+                rows.append({"frame": names[f], "index": f, "split": "holdout" if f in held else "train", "psnr": r["psnr"][k],
+                             "ssim": r["ssim"][k], "ssim_std": r["ssim_std"][k], "l1": r["l1"][k], "counted": r["counted"][k],
+                             "usable": r["usable"][k]})
+            if ec["maps"]:
+                m = r["map"].cpu()
+                host_maps.append(m)
+                if save:
+                    from PIL import Image
+                    grey = (m.clamp(0.0, 1.0) * 255.0).round().to(torch.uint8).numpy()
+                    for k, f in enumerate(sel):
+                        Image.fromarray(grey[k]).save(os.path.join(d, names[f] + "_ssim.png"))
+
+        def mean(split, key):
+            v = [x[key] for x in rows if (split is None or x["split"] == split) and x[key] is not None and math.isfinite(x[key])]
+            return float(np.mean(v)) if v else None
+
+        res = {"iter": self.iter_step, "method": c["method"], "level": L, "background": c["background"], "settings": dict(ec),
+               "frames": rows, "n_train": sum(x["split"] == "train" for x in rows),
+               "n_holdout": sum(x["split"] == "holdout" for x in rows)}
+        for key in ("psnr", "ssim", "l1"):
+            res[key + "_mean"] = mean(None, key)
+            for split in ("train", "holdout"):
+                res[f"{key}_{split}"] = mean(split, key)
+        scored = sorted((x for x in rows if x["ssim"] is not None), key=lambda x: x["ssim"])
+        res["worst_ssim"] = [{"frame": x["frame"], "ssim": x["ssim"], "psnr": x["psnr"]} for x in scored[:5]]
+        if save:
+            with open(os.path.join(d, "eval.json"), "w") as f:
+                json.dump(res, f, indent=1)
+            if self._board is None:
+                from .tb_events import make_writer
+                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+            for key in ("psnr", "ssim"):
+                for split in ("train", "holdout"):
+                    if res[f"{key}_{split}"] is not None:
+                        self._board.add_scalar(f"eval_img/{key}_{split}", res[f"{key}_{split}"], self.iter_step)
+            self._board.flush()
+        self.last_eval_dir = d if save else None
+        res = dict(res, dir=self.last_eval_dir)
+        if ec["maps"]:
+            res["map"] = torch.cat(host_maps)
+        return res
 
     # ------------------------------------------------------------------ poses out (the reference's hand-off format)
     def export_poses(self, dir=None):

@@ -683,6 +683,37 @@ int dh_match_gray(const float* img, int64_t n_frames, int H, int W, float a_min,
 int dh_match_search(const uint8_t* gray, const uint8_t* valid, int64_t n_frames, int H, int W, const int32_t* queries, int64_t n, int P,
                     int R, int excl, int64_t min_va, int32_t* out_i, double* out_f, void* stream);
 
+/* ---- image metrics (dynhor_amd/image_metrics.py: renderings scored against the frames, Runner.evaluate_views) ----
+ * Integer window sums, a short fp64 formula, no atomics: map and out are bitwise the same from launch to launch and for every split
+ * of the frames into calls.
+ *
+ * dh_ssim: a, b u8 [n_frames,H,W,3] (the rendering and the frame), usable u8 [n_frames,H,W] (non-zero = usable; null: every pixel is),
+ * taps_host int32 [2 radius + 1] in HOST memory: a Gaussian in Q16, every tap >= 0 and their sum exactly 65536 (validated on the host
+ * and passed to the kernel by value; the kernel evaluates no exponential).  With u = usable ? 1 : 0 (0 outside the image) and
+ * w(dx, dy) = taps[dx + radius] taps[dy + radius], every pixel has the integer sums over |dx|, |dy| <= radius
+ *   Wt = sum w u;  per channel  Sx = sum w u a,  Sy = sum w u b,  Sxx = sum w u a^2,  Syy = sum w u b^2,  Sxy = sum w u a b,
+ * formed separably (rows, then columns) and exactly: a per-pixel quantity is at most 255^2 = 65025 and the taps sum to 2^16, so a
+ * ROW SUM IS BELOW 2^32 (65025 * 65536 = 0xFE010000; the row pass keeps 32-bit registers and LDS words on the strength of this) and
+ * a COLUMN SUM IS BELOW 2^48 (exact in 64-bit integers and as a double).  Wt <= 2^32.
+ * A pixel is counted when it is usable and Wt >= w_min.  For a counted pixel, in fp64 from the integers, every operation rounded once
+ * as written and nothing contracted into an fma:
+ *   mx = Sx / Wt,  my = Sy / Wt,  vx = Sxx / Wt - mx mx,  vy = Syy / Wt - my my,  cxy = Sxy / Wt - mx my,
+ *   s_c = ((2 mx my + C1)(2 cxy + C2)) / ((mx mx + my my + C1)(vx + vy + C2)),  2 mx my = (2 mx) my, sums from the left,
+ *   C1 = k1 k1 with k1 = 0.01 * 255,  C2 = k2 k2 with k2 = 0.03 * 255 (doubles),   s = ((s_0 + s_1) + s_2) / 3.
+ * map f32 [n_frames,H,W] (may be null) = (float)s for a counted pixel, 0 for any other.  out f64 [n_frames, dh_ssim_sums() = 6]:
+ *   [0] sum s over the counted pixels   [1] counted pixels   [2] sum over usable pixels and channels of (a - b)^2
+ *   [3] sum |a - b| over the same       [4] usable pixels    [5] sum s^2 over the counted pixels
+ * [1]..[4] are integers below 2^53, hence exact.  ws: dh_ssim_workspace(n_frames, H, W) bytes, 16-byte aligned: every workgroup (one
+ * per 32 x 16 pixel tile) stores its partial and a second kernel adds a frame's partials in tile order (no float atomics); the tiles
+ * depend on H and W alone.  The filtered planes are never written to memory.  n_frames == 0: no-op.
+ * DH_ERR_BAD_ARG: null a, b, taps_host, out or ws, misaligned ws, negative n_frames or radius, H or W < 1, a negative tap, taps that
+ * do not sum to 65536, w_min == 0 or > 2^32.  DH_ERR_UNSUPPORTED: radius > 16, n_frames > 65535, H or W > 2^24, 2^22 or more tiles
+ * in a frame. */
+int dh_ssim_sums(void);
+int64_t dh_ssim_workspace(int64_t n_frames, int H, int W);
+int dh_ssim(const uint8_t* a, const uint8_t* b, const uint8_t* usable, int64_t n_frames, int H, int W, const int32_t* taps_host,
+            int radius, uint64_t w_min, float* map, double* out, void* ws, void* stream);
+
 /* ---- pose initialisation by silhouette retrieval (dynhor_amd/pose_init.py: a bank of views of a template, retrieval per frame) ----
  * Integer kernels without float atomics: every output is bitwise the same from launch to launch and for every split of the images,
  * frames or views into calls.  Pixel centres are integers, as for dh_mesh_raster_depth.
