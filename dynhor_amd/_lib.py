@@ -104,6 +104,7 @@ SIGNATURES = {
     "dh_label_dilate": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dh_mesh_mask_votes": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "dh_mesh_components": (_i32, [_vp, _i64, _i64, _vp, _vp]),
+    "dh_hull_accumulate": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "dh_mesh_raster_depth": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "dh_mesh_bake_colors": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _vp, _vp, _vp]),
     "dh_mesh_shade": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp]),

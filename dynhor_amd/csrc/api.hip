@@ -665,6 +665,16 @@ int dh_mesh_mask_votes(const float* verts, int64_t nv, const uint8_t* keep, cons
     return launch_mesh_mask_votes(verts, nv, keep, R, T, K, n_frames, H, W, bg_votes, seen, static_cast<hipStream_t>(stream));
 }
 
+int dh_hull_accumulate(const float* pts, int64_t n, const float* sd, const float* R, const float* T, const float* K, int64_t n_frames,
+                       int H, int W, int frame0, int m, float* topk, int32_t* arg, int32_t* seen, void* stream) {
+    if (n < 0 || n_frames < 0 || frame0 < 0 || H < 2 || W < 2 || m < 1 || m > 8) return DH_ERR_BAD_ARG;
+    if (H > (1 << 24) || W > (1 << 24) || n >= ((int64_t)1 << 31) * 256) return DH_ERR_UNSUPPORTED;
+    if (n_frames > ((int64_t)1 << 31) - 1 - frame0 || n_frames > (((int64_t)1 << 58) / H) / W) return DH_ERR_UNSUPPORTED;
+    if (n == 0 || n_frames == 0) return DH_OK;
+    if (!pts || !sd || !R || !T || !K || !topk || !arg || !seen) return DH_ERR_BAD_ARG;
+    return launch_hull_accumulate(pts, n, sd, R, T, K, (int)n_frames, H, W, frame0, m, topk, arg, seen, static_cast<hipStream_t>(stream));
+}
+
 int dh_mesh_components(const int64_t* faces, int64_t nf, int64_t nv, int32_t* labels, void* stream) {
     if (nf < 0 || nv < 0) return DH_ERR_BAD_ARG;
     if (nv >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;               // labels are int32

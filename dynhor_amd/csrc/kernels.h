@@ -211,6 +211,10 @@ int launch_mesh_mask_votes(const float* verts, int64_t nv, const uint8_t* keep, 
                            int64_t n_frames, int H, int W, int32_t* bg_votes, int32_t* seen, hipStream_t st);
 int launch_mesh_components(const int64_t* faces, int64_t nf, int64_t nv, int32_t* labels, hipStream_t st);
 
+// visual hull (visual_hull.hip): the m largest signed mask distances per point over a chunk of frames (m in 1..8)
+int launch_hull_accumulate(const float* pts, int64_t n, const float* sd, const float* R, const float* T, const float* K, int n_frames,
+                           int H, int W, int frame0, int m, float* topk, int32_t* arg, int32_t* seen, hipStream_t st);
+
 // mesh colouring (mesh_color.hip): z-buffer of the mesh in every frame, per-vertex colour gathered over the frames
 int launch_mesh_raster_depth(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* R, const float* T,
                              const float* K, int64_t n_frames, int H, int W, uint64_t* zbuf, hipStream_t st);

@@ -16,6 +16,9 @@
     python -m dynhor_amd.run --config_path X.yaml --mode init_poses --vis_mesh template.obj --vis_normalize reference   # poses from masks
     python -m dynhor_amd.run --config_path X.yaml --mode init_sdf --vis_mesh template.obj --vis_normalize reference     # SDF warm start
     python -m dynhor_amd.run --config_path X.yaml --mode init_sdf --mesh_simplify faces:5000   # template: data_info.obj_path, simplified
+    python -m dynhor_amd.run --config_path X.yaml --mode visual_hull   # <exp>/hull/hull.ply from masks and poses alone; no template
+    python -m dynhor_amd.run --config_path X.yaml --mode visual_hull --hull_resolution 256 --hull_votes 2   # simplified too when the config's mesh_simplify.mode says so
+    python -m dynhor_amd.run --config_path X.yaml --mode refine_poses --vis_mesh exps/<seq>/<exp>/hull/hull.ply   # poses fitted to the hull
     python -m dynhor_amd.run --config_path X.yaml --mode match_frames --match_offsets 1,2,5   # correspondence_infos from the frames
     python -m dynhor_amd.run --config_path X.yaml --mode match_frames --is_continue --match_guide mesh   # guided by the reconstruction
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode render_views --is_continue   # every frame sphere-traced: png, normal, depth, PSNR, IoU
@@ -34,7 +37,7 @@ import sys
 
 
 MODES = ("train", "validate_image", "validate_mesh", "evaluate_mesh", "visualize_mesh", "refine_poses", "export_poses", "init_poses",
-         "init_sdf", "render_views", "match_frames", "evaluate_views")
+         "init_sdf", "render_views", "match_frames", "evaluate_views", "visual_hull")
 
 
 def mode_arg(value: str) -> str:
@@ -127,6 +130,13 @@ def build_parser():
     ap.add_argument("--match_offsets", type=str, default=None,
                     help="match_frames: frame i is matched to i + every offset of this comma-separated list (default: the config's "
                          "match.offsets, else 1,2,5)")
+    # visual_hull only (defaults: the config's visual_hull: block; with the config's mesh_simplify.mode it also writes hull_simple.ply)
+    ap.add_argument("--hull_resolution", type=int, default=None,
+                    help="visual_hull: grid points per axis of the fine grid, at most 512 (default: the config's visual_hull.resolution, "
+                         "else 128)")
+    ap.add_argument("--hull_votes", type=int, default=None,
+                    help="visual_hull: a point is outside the hull when this many frames say so; K > 1 tolerates K - 1 frames with a "
+                         "wrong pose or mask (default: the config's visual_hull.min_carve_votes, else 1)")
     return ap
 
 
@@ -197,6 +207,15 @@ def main():
         if runner.rank == 0:
             import json
             print(json.dumps({k: v for k, v in res.items() if k != "loss"}), flush=True)
+    elif args.mode == "visual_hull":
+        res = runner.visual_hull(resolution=args.hull_resolution, min_carve_votes=args.hull_votes)
+        runner.close()
+        if runner.rank == 0:
+            import json
+            res["silhouette"] = {k: v for k, v in res["silhouette"].items() if k != "frames"}
+            res["stats"] = dict(res["stats"], sole_carved={k: v for k, v in res["stats"]["sole_carved"].items()
+                                                           if k not in ("cells", "share")})
+            print(json.dumps(res), flush=True)
     elif args.mode == "match_frames":
         res = runner.match_frames(guide=args.match_guide, offsets=args.match_offsets, mesh=args.vis_mesh, normalize=args.vis_normalize,
                                   resolution=args.mesh_resolution)

@@ -226,6 +226,7 @@ class Runner:
         self.last_view_dir = None        # render_views: the novel_views/<iter> directory it wrote
         self.last_match_dir = None       # match_frames: the correspondences directory it wrote
         self.last_eval_dir = None        # evaluate_views: the image_eval/<iter> directory it wrote
+        self.last_hull = None            # visual_hull: (verts, faces) of the hull it meshed
         if is_continue:
             ck_dir = os.path.join(self.base_exp_dir, "checkpoints")
             ck = sorted(f for f in os.listdir(ck_dir) if f.endswith(".pth")) if os.path.isdir(ck_dir) else []
@@ -1479,6 +1480,68 @@ class Runner:
             res["dir"] = d
             for k in ("heldout_before", "heldout_after", "seconds"):
                 self._board.add_scalar("sdf_init/" + k, float(res[k]), self.iter_step)
+            self._board.flush()
+        return res
+
+    def _visual_hull_conf(self, **overrides):
+        """The YAML's optional visual_hull: block over VISUAL_HULL_DEFAULTS, then the overrides that are not None; an unknown or bad
+        key raises."""
+        from .visual_hull import merge_settings
+        return merge_settings(self.conf.get("visual_hull"), **overrides)
+
+    @torch.no_grad()
+    def visual_hull(self, save=True, simplify=None, **overrides):
+        """The visual hull of the object masks at the dataset's current poses (dynhor_amd/visual_hull.py): a mesh of the object's own
+        shape, up to its concavities, from the label maps and the poses alone -- no checkpoint, no template.  It uses every frame:
+        train.holdout does not apply (the hull is geometry from masks, not a rendering that is scored).  overrides: any key of the
+        config's visual_hull: block; simplify: a mesh_simplify mode (None: the config's mesh_simplify.mode).  Rank 0 writes
+        <exp>/hull/hull.ply, with simplification also hull_simple.ply, and hull.json (settings, stats -- grid, cell, volume,
+        radius_max, touches_bound, sole_carved: per frame the cells that frame alone carves, the frames to distrust first --,
+        silhouette: mesh_vis.silhouette_summary of the hull drawn over the frames, seconds per phase), and logs hull/iou_mean,
+        hull/volume and hull/sole_carved_max to <exp>/board.  Returns the dict of hull.json plus dir (single process: run it on one
+        rank)."""
+        import time
+        from .mesh_vis import overlay_frames, silhouette_summary
+        from .visual_hull import visual_hull
+        if self.world > 1:
+            raise ValueError("visual_hull runs on one rank")
+        hc = self._visual_hull_conf(**overrides)
+        seconds = {}
+        verts, faces, stats = visual_hull(self.dataset, timer=seconds, **hc)
+        smode = self._simplify_conf(simplify)["mode"]
+        sv = sf = None
+        self.last_simplify_stats = None
+        if smode != "none":
+            t0 = time.perf_counter()
+            sv, sf = self._simplify_mesh(verts, faces, simplify)
+            torch.cuda.synchronize(self.device)
+            seconds["simplify"] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        names = schedules.frame_names(self.dataset.n_images, self.dataset.stems)
+        sil = silhouette_summary(overlay_frames(verts, faces, self.dataset, frame_chunk=hc["frame_chunk"]).cpu(), names)
+        seconds["silhouette"] = time.perf_counter() - t0
+        res = {"iter": self.iter_step, "settings": hc, "stats": stats, "silhouette": sil, "seconds": seconds, "simplify": smode,
+               "simplify_stats": self.last_simplify_stats}
+        self.last_hull = (verts, faces)
+        if save and self.rank == 0:
+            from .mesh import write_ply
+            d = os.path.join(self.base_exp_dir, "hull")
+            os.makedirs(d, exist_ok=True)
+            res["mesh"] = os.path.join(d, "hull.ply")
+            write_ply(res["mesh"], verts, faces)
+            if sv is not None:
+                res["mesh_simple"] = os.path.join(d, "hull_simple.ply")
+                write_ply(res["mesh_simple"], sv, sf)
+            with open(os.path.join(d, "hull.json"), "w") as f:
+                json.dump(res, f, indent=1)
+            res["dir"] = d
+            if self._board is None:
+                from .tb_events import make_writer
+                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+            if sil["iou_mean"] is not None:
+                self._board.add_scalar("hull/iou_mean", float(sil["iou_mean"]), self.iter_step)
+            self._board.add_scalar("hull/volume", float(stats["volume"]), self.iter_step)
+            self._board.add_scalar("hull/sole_carved_max", float(stats["sole_carved"]["share_max"]), self.iter_step)
             self._board.flush()
         return res
 
