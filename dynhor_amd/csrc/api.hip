@@ -899,8 +899,9 @@ int dh_match_gray(const float* img, int64_t n_frames, int H, int W, float a_min,
     return launch_match_gray(img, n_frames * H * W, a_min, gray, valid, static_cast<hipStream_t>(stream));
 }
 
-int dh_match_search(const uint8_t* gray, const uint8_t* valid, int64_t n_frames, int H, int W, const int32_t* queries, int64_t n, int P,
-                    int R, int excl, int64_t min_va, int32_t* out_i, double* out_f, void* stream) {
+// dh_match_search and dh_match_search_warp: the same rules, queries of 6 or 10 words
+static int match_search_api(const uint8_t* gray, const uint8_t* valid, int64_t n_frames, int H, int W, const int32_t* queries, int64_t n,
+                            bool warp, int P, int R, int excl, int64_t min_va, int32_t* out_i, double* out_f, void* stream) {
     if (n < 0) return DH_ERR_BAD_ARG;
     const int rc = sil_args(n_frames, H, W);
     if (rc != DH_OK) return rc;
@@ -911,9 +912,19 @@ int dh_match_search(const uint8_t* gray, const uint8_t* valid, int64_t n_frames,
         (reinterpret_cast<uintptr_t>(out_i) & 3u) != 0 || (reinterpret_cast<uintptr_t>(queries) & 3u) != 0)
         return DH_ERR_BAD_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int bad = match_check_frames(queries, n, n_frames, out_i, st);
+    const int bad = match_check_frames(queries, n, n_frames, warp, out_i, st);
     if (bad != 0) return bad < 0 ? bad : DH_ERR_BAD_ARG;
-    return launch_match_search(gray, valid, H, W, queries, n, P, R, excl, min_va, out_i, out_f, st);
+    return launch_match_search(gray, valid, H, W, queries, n, warp, P, R, excl, min_va, out_i, out_f, st);
+}
+
+int dh_match_search(const uint8_t* gray, const uint8_t* valid, int64_t n_frames, int H, int W, const int32_t* queries, int64_t n, int P,
+                    int R, int excl, int64_t min_va, int32_t* out_i, double* out_f, void* stream) {
+    return match_search_api(gray, valid, n_frames, H, W, queries, n, false, P, R, excl, min_va, out_i, out_f, stream);
+}
+
+int dh_match_search_warp(const uint8_t* gray, const uint8_t* valid, int64_t n_frames, int H, int W, const int32_t* queries, int64_t n,
+                         int P, int R, int excl, int64_t min_va, int32_t* out_i, double* out_f, void* stream) {
+    return match_search_api(gray, valid, n_frames, H, W, queries, n, true, P, R, excl, min_va, out_i, out_f, stream);
 }
 
 int dh_ssim_sums(void) { return ssim_sums(); }

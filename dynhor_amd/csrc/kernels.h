@@ -262,13 +262,14 @@ int launch_photo_loss_grad(const float* pts, const float* normals, const float* 
 
 // dense frame matching (match.hip): 8-bit grey and validity of blurred frames, guided ZNCC block search per query (patch half-size
 // <= match_max_patch(), search range <= match_max_range()); match_check_frames waits for the stream: 0 = every query's frames lie in
-// [0, n_frames), 1 = one does not
+// [0, n_frames), 1 = one does not.  warp: the queries have 10 words, the last four a 2 x 2 map in Q16 through which the source patch is
+// sampled, and the check also answers 1 for an entry beyond +-2^19
 int match_max_patch();
 int match_max_range();
 int launch_match_gray(const float* img, int64_t n_pixels, float a_min, uint8_t* gray, uint8_t* valid, hipStream_t st);
-int match_check_frames(const int32_t* queries, int64_t n, int64_t n_frames, int32_t* scratch, hipStream_t st);
-int launch_match_search(const uint8_t* gray, const uint8_t* valid, int H, int W, const int32_t* queries, int64_t n, int P, int R,
-                        int excl, int64_t min_va, int32_t* out_i, double* out_f, hipStream_t st);
+int match_check_frames(const int32_t* queries, int64_t n, int64_t n_frames, bool warp, int32_t* scratch, hipStream_t st);
+int launch_match_search(const uint8_t* gray, const uint8_t* valid, int H, int W, const int32_t* queries, int64_t n, bool warp, int P,
+                        int R, int excl, int64_t min_va, int32_t* out_i, double* out_f, hipStream_t st);
 
 // image metrics (image_metrics.hip): masked SSIM of u8 images with integer window sums and an fp64 formula, squared / absolute error
 // sums of the usable pixels (ssim_sums() doubles per frame, ws = ssim_workspace bytes; radius <= ssim_max_radius(); taps_host is read

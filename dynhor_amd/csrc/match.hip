@@ -4,10 +4,13 @@
 // match_gray_kernel: one lane per pixel of dh_image_blur's output; every operation is an fp32 IEEE operation written out (fmaf), so a
 // float32 restatement gives the same bytes.
 //
-// match_search_kernel<P>: one workgroup of MS_THREADS lanes per query, dynamic LDS sized by (P, R):
+// match_search_kernel<P, WARP>: one workgroup of MS_THREADS lanes per query, dynamic LDS sized by (P, R):
 //   source  the (2P+1)^2 patch about (px, py) of frame fi, rows padded with zero bytes to NW = ceil((2P+1) / 4) words; after a barrier
 //           every lane keeps all of it in registers (P is a template argument: the rows are unrolled).  A patch with a pixel that is
-//           invalid or outside the image, or with va < min_va, ends the query (flag 1) before any search.
+//           invalid or outside the image, or with va < min_va, ends the query (flag 1) before any search.  WARP (dh_match_search_warp,
+//           queries of 10 words): the lane of cell (c, r) samples frame fi at (px, py) + A (c, r), A the query's 2 x 2 map in Q16, from
+//           up to four bytes with 8-bit bilinear weights (ms_warp_cell); only this staging differs, the registers, the window and the
+//           search are those of the plain kernel.
 //   window  the (2(R+P)+1)^2 pixels about (gx, gy) of frame fj: a wave stages one row per step, lane = column, the bytes of `gray`
 //           (0 where invalid or outside) at a row stride that is a multiple of 4 with NW+1 words readable from every candidate's
 //           column, and the wave's ballot of `valid` as the row's bit mask (no atomics).
@@ -35,6 +38,7 @@ constexpr int MG_THREADS = 256;
 constexpr int MS_THREADS = 256;
 constexpr int MS_WAVES = MS_THREADS / 64;
 constexpr int MS_MAX_P = 7, MS_MAX_R = 32;
+constexpr int MS_MAX_AFFINE = 1 << 19;         // Q16: a scale of 8
 constexpr double MS_NONE = -2.0;               // the score of an invalid candidate; real scores lie in [-1, 1]
 constexpr uint32_t MS_ROW_BAD = 0xFFFFFFFFu;   // no valid row packs to this: sum b^2 <= 15 * 255^2 < 0xEE210 leaves the top bits short of all ones
 
@@ -70,6 +74,37 @@ __host__ __device__ inline MsGeom ms_geom(int P, int R) {
     return g;
 }
 
+// One cell of a warped source patch: the sample of frame f (gray, valid at its first pixel) at (X, Y) / 65536, X = px 65536 + a00 c + a01 r,
+// Y = py 65536 + a10 c + a11 r in int64.  (x0, y0) = floor, the fractions' top 8 bits weigh the four neighbours by (256 - fx, fx) x
+// (256 - fy, fy); a neighbour of weight 0 is not read.  False when a neighbour that is read lies outside the image or is invalid; else
+// *out = (sum w gray + 32768) >> 16 (the weights sum to 65536: the sum stays below 2^24).
+__device__ __forceinline__ bool ms_warp_cell(const uint8_t* __restrict__ gray, const uint8_t* __restrict__ valid, int H, int W, int64_t X,
+                                             int64_t Y, uint8_t* out) {
+    const int64_t x0 = X >> 16, y0 = Y >> 16;
+    const uint32_t fx = (uint32_t)(X & 0xFFFF) >> 8, fy = (uint32_t)(Y & 0xFFFF) >> 8;
+    const uint32_t wx[2] = {256u - fx, fx}, wy[2] = {256u - fy, fy};
+    uint32_t sum = 32768u;
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const uint32_t w = wx[i] * wy[j];
+            if (w == 0u) continue;
+            const int64_t x = x0 + i, y = y0 + j;
+            if (x < 0 || x >= W || y < 0 || y >= H) {
+                ok = false;
+                continue;
+            }
+            const int64_t pix = y * W + x;
+            if (valid[pix] == 0) ok = false;
+            else sum += w * gray[pix];
+        }
+    }
+    *out = (uint8_t)(sum >> 16);
+    return ok;
+}
+
 // (score, candidate) order of the selection: the larger score, then the smaller index
 __device__ __forceinline__ bool ms_better(double s, int c, double s0, int c0) { return s > s0 || (s == s0 && c < c0); }
 }  // namespace
@@ -86,16 +121,24 @@ __global__ __launch_bounds__(MG_THREADS) void match_gray_kernel(const float4* __
     gray[i] = ok ? (uint8_t)(int)y : (uint8_t)0;
 }
 
-// *bad (zeroed by the caller) becomes 1 when a query names a frame outside [0, n_frames)
+// *bad (zeroed by the caller) becomes 1 when a query names a frame outside [0, n_frames) or, WARP, has an affine entry beyond
+// +-MS_MAX_AFFINE
+template <bool WARP>
 __global__ __launch_bounds__(MG_THREADS) void match_check_kernel(const int32_t* __restrict__ queries, int64_t n, int n_frames,
                                                                   int32_t* __restrict__ bad) {
     const int64_t i = (int64_t)blockIdx.x * MG_THREADS + threadIdx.x;
     if (i >= n) return;
-    const int fi = queries[i * 6 + 0], fj = queries[i * 6 + 1];
-    if (fi < 0 || fi >= n_frames || fj < 0 || fj >= n_frames) atomicOr(bad, 1);
+    const int32_t* Q = queries + i * (WARP ? 10 : 6);
+    const int fi = Q[0], fj = Q[1];
+    bool wrong = fi < 0 || fi >= n_frames || fj < 0 || fj >= n_frames;
+    if constexpr (WARP) {
+#pragma unroll
+        for (int k = 6; k < 10; ++k) wrong |= Q[k] > MS_MAX_AFFINE || Q[k] < -MS_MAX_AFFINE;
+    }
+    if (wrong) atomicOr(bad, 1);
 }
 
-template <int P>
+template <int P, bool WARP>
 __global__ __launch_bounds__(MS_THREADS) void match_search_kernel(const uint8_t* __restrict__ gray, const uint8_t* __restrict__ valid,
                                                                    int H, int W, const int32_t* __restrict__ queries, int R, int excl,
                                                                    int64_t min_va, int32_t* __restrict__ out_i,
@@ -114,7 +157,7 @@ __global__ __launch_bounds__(MS_THREADS) void match_search_kernel(const uint8_t*
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t q = blockIdx.x;
-    const int32_t* Q = queries + q * 6;
+    const int32_t* Q = queries + q * (WARP ? 10 : 6);
     const int fi = Q[0], fj = Q[1], px = Q[2], py = Q[3], gx = Q[4], gy = Q[5];
     const int64_t HW = (int64_t)H * W;
     int32_t* oi = out_i + q * 4;
@@ -126,12 +169,21 @@ __global__ __launch_bounds__(MS_THREADS) void match_search_kernel(const uint8_t*
         const int r = tid / (4 * NW), c = tid - r * (4 * NW);
         uint8_t b = 0;
         if (c < S) {
-            const int64_t x = (int64_t)px - P + c, y = (int64_t)py - P + r;
-            if (x >= 0 && x < W && y >= 0 && y < H) {
-                const int64_t pix = (int64_t)fi * HW + y * W + x;
-                if (valid[pix] != 0) {
-                    src_ok = true;
-                    b = gray[pix];
+            if constexpr (WARP) {
+                const int64_t cc = c - P, rr = r - P;
+                const int64_t X = (int64_t)px * 65536 + (int64_t)Q[6] * cc + (int64_t)Q[7] * rr;
+                const int64_t Y = (int64_t)py * 65536 + (int64_t)Q[8] * cc + (int64_t)Q[9] * rr;
+                uint8_t v;
+                src_ok = ms_warp_cell(gray + (int64_t)fi * HW, valid + (int64_t)fi * HW, H, W, X, Y, &v);
+                if (src_ok) b = v;
+            } else {
+                const int64_t x = (int64_t)px - P + c, y = (int64_t)py - P + r;
+                if (x >= 0 && x < W && y >= 0 && y < H) {
+                    const int64_t pix = (int64_t)fi * HW + y * W + x;
+                    if (valid[pix] != 0) {
+                        src_ok = true;
+                        b = gray[pix];
+                    }
                 }
             }
         }
@@ -328,12 +380,13 @@ int launch_match_gray(const float* img, int64_t n_pixels, float a_min, uint8_t* 
     return launch_status();
 }
 
-// 0 = every frame index lies in [0, n_frames), 1 = one does not; out_i's first word is the scratch (the search overwrites it).
-// Waits for the stream.
-int match_check_frames(const int32_t* queries, int64_t n, int64_t n_frames, int32_t* scratch, hipStream_t st) {
+// 0 = every frame index lies in [0, n_frames) (warp: and every affine entry within +-2^19), 1 = one does not; out_i's first word is the
+// scratch (the search overwrites it).  warp: the queries have 10 words, else 6.  Waits for the stream.
+int match_check_frames(const int32_t* queries, int64_t n, int64_t n_frames, bool warp, int32_t* scratch, hipStream_t st) {
     if (hipMemsetAsync(scratch, 0, sizeof(int32_t), st) != hipSuccess) return DH_ERR_LAUNCH;
-    hipLaunchKernelGGL(match_check_kernel, dim3((unsigned)((n + MG_THREADS - 1) / MG_THREADS)), dim3(MG_THREADS), 0, st, queries, n,
-                       (int)n_frames, scratch);
+    const dim3 grid((unsigned)((n + MG_THREADS - 1) / MG_THREADS)), block(MG_THREADS);
+    if (warp) hipLaunchKernelGGL(match_check_kernel<true>, grid, block, 0, st, queries, n, (int)n_frames, scratch);
+    else hipLaunchKernelGGL(match_check_kernel<false>, grid, block, 0, st, queries, n, (int)n_frames, scratch);
     if (launch_status() != DH_OK) return DH_ERR_LAUNCH;
     int32_t bad = 0;
     if (hipMemcpyAsync(&bad, scratch, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess) return DH_ERR_LAUNCH;
@@ -341,13 +394,18 @@ int match_check_frames(const int32_t* queries, int64_t n, int64_t n_frames, int3
     return bad != 0 ? 1 : 0;
 }
 
-int launch_match_search(const uint8_t* gray, const uint8_t* valid, int H, int W, const int32_t* queries, int64_t n, int P, int R,
-                        int excl, int64_t min_va, int32_t* out_i, double* out_f, hipStream_t st) {
+int launch_match_search(const uint8_t* gray, const uint8_t* valid, int H, int W, const int32_t* queries, int64_t n, bool warp, int P,
+                        int R, int excl, int64_t min_va, int32_t* out_i, double* out_f, hipStream_t st) {
     const size_t lds = ms_geom(P, R).bytes;
     const dim3 grid((unsigned)n), block(MS_THREADS);
-#define DH_MS_CASE(p)                                                                                                               \
-    case p:                                                                                                                         \
-        hipLaunchKernelGGL(match_search_kernel<p>, grid, block, lds, st, gray, valid, H, W, queries, R, excl, min_va, out_i, out_f); \
+#define DH_MS_CASE(p)                                                                                                                  \
+    case p:                                                                                                                            \
+        if (warp)                                                                                                                      \
+            hipLaunchKernelGGL((match_search_kernel<p, true>), grid, block, lds, st, gray, valid, H, W, queries, R, excl, min_va,      \
+                               out_i, out_f);                                                                                          \
+        else                                                                                                                           \
+            hipLaunchKernelGGL((match_search_kernel<p, false>), grid, block, lds, st, gray, valid, H, W, queries, R, excl, min_va,     \
+                               out_i, out_f);                                                                                          \
         break;
     switch (P) {
         DH_MS_CASE(1) DH_MS_CASE(2) DH_MS_CASE(3) DH_MS_CASE(4) DH_MS_CASE(5) DH_MS_CASE(6) DH_MS_CASE(7)

@@ -18,10 +18,17 @@ DINOv2 in ``pose_init`` and direct alignment for a learned photometric prior in 
     s1 >= zncc_min, s1 - s2 >= peak_margin, the way back within fb_px of p.  kpts0 = p, kpts1 = q + sub, conf = s1 min(1, (s1 - s2) /
     peak_full).
   * ``match_frames``: all of it for a Dataset; returns the list ``Dataset.set_correspondences`` takes, and the counts.
+  * ``warp="affine"`` (with ``guide="mesh"``; ``mesh_affines``, ``search_warp`` = dh_match_search_warp): the plane of the face seen
+    at p induces a 2 x 2 affine map J between the two images; the forward search samples its source patch through J^-1 and the
+    backward search through J (Q16 entries, 8-bit bilinear weights, integers throughout), so the integer ZNCC search compares patches
+    of the same shape again across wide baselines and in-plane rotation.  A query whose J mirrors or scales beyond ``warp_max`` is
+    dropped.
 
-Limits: a patch knows neither scale nor rotation (beyond roughly 20 degrees of viewpoint change or 10 degrees in the image plane the
-score fades); there is no pyramid, a displacement beyond R from the guess is lost; the result is semi-dense, on a grid; a highlight
-that moves with the hand matches itself.  DESIGN_NEXT_ROWS.md section 20 has the numbers.
+Limits: without the warp a patch knows neither scale nor rotation (beyond roughly 20 degrees of viewpoint change or 10 degrees in the
+image plane the score fades); with it the patch follows one plane per query: the faceted normal of a coarse mesh, a depth edge inside
+the patch and a scale beyond ``warp_max`` (no anti-aliasing beyond the blur) are not followed; there is no pyramid, a displacement
+beyond R from the guess is lost; the result is semi-dense, on a grid; a highlight that moves with the hand matches itself.
+DESIGN_NEXT_ROWS.md sections 20 and 23 have the numbers.
 
 The kernels run on the current stream; there is no CPU path.
 """
@@ -41,7 +48,9 @@ GUIDES = ("none", "mesh")
 # (guide mesh); min_va None: 4 N^2, N = (2 patch + 1)^2 (a patch variance of 4 grey levels^2)
 DEFAULTS = {"guide": "none", "offsets": (1, 2, 5), "sigma": 1.0, "a_min": 0.5, "erode_px": 1, "patch": 4, "range": None, "excl": 2,
             "min_va": None, "zncc_min": 0.8, "peak_margin": 0.05, "peak_full": 0.2, "fb_px": 1, "step": 1, "max_per_pair": 4096,
-            "depth_eps": 0.01, "min_cos": 0.2, "frame_chunk": 16}
+            "depth_eps": 0.01, "min_cos": 0.2, "frame_chunk": 16, "warp": "none", "warp_max": 3.0}
+WARPS = ("none", "affine")
+WARP_MAX_LIMIT = 8.0                                         # dh_match_search_warp takes no entry beyond 2^19 in Q16
 RANGE_DEFAULT = {"none": 16, "mesh": 12}
 QUERY_CHUNK = 1 << 20
 MAX_STEP = 1 << 12
@@ -82,23 +91,27 @@ def gray_frames(rgb, usable, sigma: float = DEFAULTS["sigma"], a_min: float = DE
 def search(gray, valid, queries, patch: int = DEFAULTS["patch"], rng: int = 16, excl: int = DEFAULTS["excl"], min_va=None):
     """(out_i int32 [n,4] = (qx, qy, flags, valid candidates), out_f f64 [n,4] = (s1, s2, sub_x, sub_y)) of the queries int32 [n,6] =
     (fi, fj, px, py, gx, gy) on gray, valid u8 [F,H,W] (dh_match_search, in calls of at most QUERY_CHUNK queries)."""
-    fn = "search"
+    return _search("search", 6, gray, valid, queries, patch, rng, excl, min_va)
+
+
+def _search(fn, words, gray, valid, queries, patch, rng, excl, min_va):
+    """search (words 6, dh_match_search) and search_warp (words 10, dh_match_search_warp)."""
     gray = _device_tensor(fn, "gray", gray, torch.uint8, lambda s: len(s) == 3 and s[1] > 0 and s[2] > 0, "[F,H,W]")
     F, H, W = gray.shape
     valid = _device_tensor(fn, "valid", valid, torch.uint8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
-    queries = _device_tensor(fn, "queries", queries, torch.int32, lambda s: len(s) == 2 and s[1] == 6, "[n,6]")
+    queries = _device_tensor(fn, "queries", queries, torch.int32, lambda s: len(s) == 2 and s[1] == words, f"[n,{words}]")
     if valid.device != gray.device or queries.device != gray.device:
         raise ValueError(f"{fn}: every tensor must be on {gray.device}")
     min_va = default_min_va(patch) if min_va is None else int(min_va)
     n = queries.shape[0]
     out_i = torch.empty(n, 4, dtype=torch.int32, device=gray.device)
     out_f = torch.empty(n, 4, dtype=torch.float64, device=gray.device)
-    L = _lib.lib()
+    entry = _lib.lib().dh_match_search_warp if words == 10 else _lib.lib().dh_match_search
     with torch.cuda.device(gray.device):
         for q0 in range(0, n, QUERY_CHUNK):
             q1 = min(n, q0 + QUERY_CHUNK)
-            _lib.check(L.dh_match_search(_lib.ptr(gray), _lib.ptr(valid), F, H, W, _lib.ptr(queries[q0:q1]), q1 - q0, int(patch), int(rng),
-                                         int(excl), min_va, _lib.ptr(out_i[q0:q1]), _lib.ptr(out_f[q0:q1]), _lib.stream()))
+            _lib.check(entry(_lib.ptr(gray), _lib.ptr(valid), F, H, W, _lib.ptr(queries[q0:q1]), q1 - q0, int(patch), int(rng), int(excl),
+                             min_va, _lib.ptr(out_i[q0:q1]), _lib.ptr(out_f[q0:q1]), _lib.stream()))
     return out_i, out_f
 
 
@@ -205,12 +218,11 @@ def guide_none(pix, rows, pid, pairs, label):
     return torch.cat([fi[:, None], fj[:, None], p, p + d], 1).to(torch.int32).contiguous()
 
 
-def mesh_guesses(fi, fj, p, zbuf, verts, faces, R, T, K, depth_eps: float = DEFAULTS["depth_eps"], min_cos: float = DEFAULTS["min_cos"]):
-    """(g int64 [n,2], keep bool [n], guide f64 [n,2]) for the pixels p int64 [n,2] = (x, y) of the frames fi seen in the frames fj
-    (int64 [n]) through the mesh: with z the z-buffer depth at p (zbuf int64 [F,H,W], mesh_color.raster_depth at R, T, K) the point
-    X = R_i^T (z K^-1 (x, y, 1) - T_i) is projected into frame j, (u, w) = guide, g = floor(guide + 0.5).  keep: p has a depth; X lies
-    in front of camera j (z_j > 1e-3) and g in the image; j's z-buffer is not empty at g and z_j <= its depth + depth_eps; and the
-    face seen at p, its normal turned towards camera i, has cos = <n, normalize(C_j - X)> >= min_cos.  fp64 torch on the device."""
+def _mesh_points(fi, fj, p, zbuf, verts, faces, R, T, K):
+    """What mesh_guesses and mesh_affines share, fp64 on the device: has bool [n] (p has a depth), ci f64 [n,3] = z K^-1 (x, y, 1) the
+    point in camera i (z = 1 where there is no depth), X = R_i^T (ci - T_i), cam = R_j X + T_j, zs = cam's z kept away from 0,
+    guide f64 [n,2] = the projection of cam, nrm the normal of the face seen at p turned towards camera i (not normalised), Ci, Cj
+    the camera centres, Rd, Td, Kd."""
     from .mesh_color import zbuf_depth
     F, H, W = zbuf.shape
     Rd, Td, Kd = R.double().reshape(F, 3, 3), T.double().reshape(F, 3), K.double()
@@ -220,35 +232,118 @@ def mesh_guesses(fi, fj, p, zbuf, verts, faces, R, T, K, depth_eps: float = DEFA
     z = zbuf_depth(zbuf)[fi, p[:, 1], p[:, 0]].double()
     z = torch.where(has, z, torch.ones_like(z))
     ray = torch.cat([p.double(), torch.ones(p.shape[0], 1, dtype=torch.float64, device=p.device)], 1) @ Kinv.T
-    X = torch.einsum("nji,nj->ni", Rd[fi], ray * z[:, None] - Td[fi])
+    ci = ray * z[:, None]
+    X = torch.einsum("nji,nj->ni", Rd[fi], ci - Td[fi])
     cam = torch.einsum("nij,nj->ni", Rd[fj], X) + Td[fj]
     zj = cam[:, 2]
     zs = torch.where(zj.abs() > 1e-12, zj, torch.full_like(zj, 1e-12))
     guide = torch.stack([(cam @ Kd[0]) / zs, (cam @ Kd[1]) / zs], 1)
-    g = torch.floor(guide + 0.5)
-    ins = (zj > 1e-3) & (g[:, 0] >= 0) & (g[:, 0] < W) & (g[:, 1] >= 0) & (g[:, 1] < H)
-    g = torch.where(ins[:, None], g, torch.zeros_like(g)).long()
-    dj = zbuf_depth(zbuf)[fj, g[:, 1], g[:, 0]].double()
-    seen = ins & torch.isfinite(dj) & (zj <= dj + float(depth_eps))
     face = (key & 0xFFFFFFFF).clamp(0, max(faces.shape[0] - 1, 0))
     tri = verts.double()[faces[face]]
     nrm = torch.linalg.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
     Ci = -torch.einsum("nji,nj->ni", Rd[fi], Td[fi])
     Cj = -torch.einsum("nji,nj->ni", Rd[fj], Td[fj])
     nrm = torch.where(((nrm * (Ci - X)).sum(1) < 0)[:, None], -nrm, nrm)
+    return {"has": has, "ci": ci, "X": X, "cam": cam, "zs": zs, "guide": guide, "nrm": nrm, "Ci": Ci, "Cj": Cj, "Rd": Rd, "Td": Td, "Kd": Kd}
+
+
+def mesh_guesses(fi, fj, p, zbuf, verts, faces, R, T, K, depth_eps: float = DEFAULTS["depth_eps"], min_cos: float = DEFAULTS["min_cos"]):
+    """(g int64 [n,2], keep bool [n], guide f64 [n,2]) for the pixels p int64 [n,2] = (x, y) of the frames fi seen in the frames fj
+    (int64 [n]) through the mesh: with z the z-buffer depth at p (zbuf int64 [F,H,W], mesh_color.raster_depth at R, T, K) the point
+    X = R_i^T (z K^-1 (x, y, 1) - T_i) is projected into frame j, (u, w) = guide, g = floor(guide + 0.5).  keep: p has a depth; X lies
+    in front of camera j (z_j > 1e-3) and g in the image; j's z-buffer is not empty at g and z_j <= its depth + depth_eps; and the
+    face seen at p, its normal turned towards camera i, has cos = <n, normalize(C_j - X)> >= min_cos.  fp64 torch on the device."""
+    from .mesh_color import zbuf_depth
+    F, H, W = zbuf.shape
+    m = _mesh_points(fi, fj, p, zbuf, verts, faces, R, T, K)
+    has, X, zj, guide, nrm, Cj = m["has"], m["X"], m["cam"][:, 2], m["guide"], m["nrm"], m["Cj"]
+    g = torch.floor(guide + 0.5)
+    ins = (zj > 1e-3) & (g[:, 0] >= 0) & (g[:, 0] < W) & (g[:, 1] >= 0) & (g[:, 1] < H)
+    g = torch.where(ins[:, None], g, torch.zeros_like(g)).long()
+    dj = zbuf_depth(zbuf)[fj, g[:, 1], g[:, 0]].double()
+    seen = ins & torch.isfinite(dj) & (zj <= dj + float(depth_eps))
     dj3 = Cj - X
     cos = (nrm * dj3).sum(1) / (nrm.norm(dim=1) * dj3.norm(dim=1)).clamp(min=1e-300)
     return g, has & seen & (cos >= float(min_cos)), guide
 
 
+def _projection_jacobian(c, uw, Kd, Rf):
+    """D f64 [n,2,3] = (1 / c_z) [K0 - u e3^T; K1 - w e3^T] R_f: the derivative of frame f's projection (u, w) = uw by the object point,
+    c f64 [n,3] the point in the camera (K's last row is e3)."""
+    e3 = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float64, device=c.device)
+    M = torch.stack([Kd[0][None, :] - uw[:, 0:1] * e3, Kd[1][None, :] - uw[:, 1:2] * e3], 1) / c[:, 2, None, None]
+    return M @ Rf
+
+
+def quantise_affine(A):
+    """int64 [n,4] = floor(A 65536 + 0.5) of A f64 [n,2,2], row-major (a00, a01, a10, a11): dh_match_search_warp's Q16."""
+    return torch.floor(A.reshape(-1, 4) * 65536.0 + 0.5).long()
+
+
+def mesh_affines(fi, fj, p, zbuf, verts, faces, R, T, K, warp_max: float = DEFAULTS["warp_max"]):
+    """(J f64 [n,2,2], fwd int64 [n,4], bwd int64 [n,4], keep bool [n]) for mesh_guesses' queries: the plane through the surface point X
+    of p with the normal n of the face seen there induces an affine map between the two images.  With D_f the 2 x 3 derivative of frame
+    f's projection at X and B_i = [D_i; n^T], an offset dp in frame i moves X by B_i^-1 (dp, 0) within the plane, so
+    J = D_j B_i^-1[:, :2] maps frame-i pixel offsets to frame-j pixel offsets.  fwd = floor(J^-1 65536 + 0.5): the forward search
+    samples frame i at target (frame j) offsets; bwd = floor(J 65536 + 0.5): the backward search (fj, fi, q, p) samples frame j at
+    frame-i offsets.  keep: det J > 0 and both singular values of J within [1 / warp_max, warp_max] (a NaN fails); where keep is
+    False, fwd and bwd are the identity.  A pixel without depth gives numbers of no meaning: mesh_guesses drops it.  fp64 torch on the
+    device."""
+    m = _mesh_points(fi, fj, p, zbuf, verts, faces, R, T, K)
+    ci = torch.einsum("nij,nj->ni", m["Rd"][fi], m["X"]) + m["Td"][fi]            # not m["ci"]: a float32 R is orthogonal to 1e-7 only
+    Di = _projection_jacobian(ci, torch.stack([(ci @ m["Kd"][0]) / ci[:, 2], (ci @ m["Kd"][1]) / ci[:, 2]], 1), m["Kd"], m["Rd"][fi])
+    cam = torch.cat([m["cam"][:, :2], m["zs"][:, None]], 1)
+    Dj = _projection_jacobian(cam, m["guide"], m["Kd"], m["Rd"][fj])
+    r0, r1, n = Di[:, 0], Di[:, 1], m["nrm"]
+    c0, c1 = torch.linalg.cross(r1, n), torch.linalg.cross(n, r0)                 # det B_i times the first two columns of B_i^-1
+    det_b = (r0 * c0).sum(1)
+    J = (Dj @ torch.stack([c0, c1], 2)) / det_b[:, None, None]
+    a, b, c, d = J[:, 0, 0], J[:, 0, 1], J[:, 1, 0], J[:, 1, 1]
+    det = a * d - b * c
+    s1 = a * a + b * b + c * c + d * d
+    s2 = torch.sqrt((a * a + b * b - c * c - d * d) ** 2 + 4.0 * (a * c + b * d) ** 2)
+    smax = torch.sqrt(0.5 * (s1 + s2))
+    smin = det.abs() / smax
+    keep = (det > 0) & (smax <= float(warp_max)) & (smin >= 1.0 / float(warp_max))
+    Jinv = torch.stack([d, -b, -c, a], 1).reshape(-1, 2, 2) / det[:, None, None]
+    eye = torch.tensor([65536, 0, 0, 65536], dtype=torch.int64, device=J.device)
+    k4 = keep[:, None]
+    fwd = torch.where(k4, quantise_affine(torch.where(k4[:, :, None], Jinv, torch.zeros_like(Jinv))), eye)
+    bwd = torch.where(k4, quantise_affine(torch.where(k4[:, :, None], J, torch.zeros_like(J))), eye)
+    return J, fwd, bwd, keep
+
+
+def search_warp(gray, valid, queries, patch: int = DEFAULTS["patch"], rng: int = 16, excl: int = DEFAULTS["excl"], min_va=None):
+    """search with the source patch sampled through a 2 x 2 map per query: queries int32 [n,10] = (fi, fj, px, py, gx, gy, a00, a01,
+    a10, a11), A = a / 65536 maps an offset in the target patch to an offset in the source image (dh_match_search_warp, in calls of
+    at most QUERY_CHUNK queries).  The identity (65536, 0, 0, 65536) gives search's outputs bit for bit."""
+    return _search("search_warp", 10, gray, valid, queries, patch, rng, excl, min_va)
+
+
 def match_pairs(gray, valid, queries, patch: int = DEFAULTS["patch"], rng: int = 16, excl: int = DEFAULTS["excl"], min_va=None,
                 zncc_min: float = DEFAULTS["zncc_min"], peak_margin: float = DEFAULTS["peak_margin"],
-                peak_full: float = DEFAULTS["peak_full"], fb_px=DEFAULTS["fb_px"]):
+                peak_full: float = DEFAULTS["peak_full"], fb_px=DEFAULTS["fb_px"], affine_fwd=None, affine_bwd=None):
     """The forward search of the queries int32 [n,6], the backward search (fj, fi, q, p) of those that pass the forward gates, and the
     verdict per query.  Returns a dict of device tensors over the n queries: keep bool, lost int64 (0 kept, else 1 + the index into
     LOST of the first gate that rejected it), kpts1 f32 [n,2] = q + sub, conf f32 = s1 min(1, (s1 - s2) / peak_full), s1 f64, and
-    out_i / out_f of the forward search."""
-    oi, of = search(gray, valid, queries, patch, rng, excl, min_va)
+    out_i / out_f of the forward search.  affine_fwd, affine_bwd (both or neither; [n,4] integers in Q16, mesh_affines): both
+    searches go through search_warp, the forward one with affine_fwd, the backward one with the same query's affine_bwd."""
+    if (affine_fwd is None) != (affine_bwd is None):
+        raise ValueError("match_pairs: affine_fwd and affine_bwd come together")
+    if affine_fwd is not None:
+        if tuple(affine_fwd.shape) != (queries.shape[0], 4) or tuple(affine_bwd.shape) != (queries.shape[0], 4):
+            raise ValueError(f"match_pairs: affine_fwd and affine_bwd must be [{queries.shape[0]},4]")
+        with_affine = lambda q, a: torch.cat([q, a.to(torch.int32)], 1).contiguous()
+        return _match_pairs(lambda q: search_warp(gray, valid, with_affine(q, affine_fwd), patch, rng, excl, min_va),
+                            lambda q, idx: search_warp(gray, valid, with_affine(q, affine_bwd[idx]), patch, rng, excl, min_va),
+                            queries, zncc_min, peak_margin, peak_full, fb_px)
+    return _match_pairs(lambda q: search(gray, valid, q, patch, rng, excl, min_va),
+                        lambda q, idx: search(gray, valid, q, patch, rng, excl, min_va), queries, zncc_min, peak_margin, peak_full, fb_px)
+
+
+def _match_pairs(forward, backward, queries, zncc_min, peak_margin, peak_full, fb_px):
+    """match_pairs' gates about the two searches: forward(queries), backward(back queries, their indices into queries)."""
+    oi, of = forward(queries)
     s1, s2 = of[:, 0], of[:, 1]
     lost = torch.zeros(queries.shape[0], dtype=torch.int64, device=queries.device)
     lost[oi[:, 2] != 0] = 1
@@ -257,7 +352,7 @@ def match_pairs(gray, valid, queries, patch: int = DEFAULTS["patch"], rng: int =
     idx = (lost == 0).nonzero().reshape(-1)
     qf = queries[idx]
     back = torch.stack([qf[:, 1], qf[:, 0], oi[idx, 0], oi[idx, 1], qf[:, 2], qf[:, 3]], 1).contiguous()
-    bi, _ = search(gray, valid, back, patch, rng, excl, min_va)
+    bi, _ = backward(back, idx)
     ok = (bi[:, 2] == 0) & ((bi[:, 0] - qf[:, 2]).abs() <= fb_px) & ((bi[:, 1] - qf[:, 3]).abs() <= fb_px)
     lost[idx[~ok]] = 4
     kpts1 = (oi[:, :2].double() + of[:, 2:4]).float()
@@ -284,6 +379,13 @@ def check_settings(settings: dict) -> dict:
             and float(s["fb_px"]) >= 0 and float(s["sigma"]) >= 0 and int(s["erode_px"]) >= 0 and s["offsets"] and min(s["offsets"]) >= 1):
         raise ValueError(f"match: patch in 1..7, range in 0..32, excl >= 0, min_va >= 1, peak_full > 0, fb_px >= 0, sigma >= 0, erode_px "
                          f">= 0 and positive offsets; got {s}")
+    s["warp_max"] = float(s["warp_max"])
+    if s["warp"] not in WARPS:
+        raise ValueError(f"match: warp must be one of {WARPS}, got {s['warp']!r}")
+    if s["warp"] == "affine" and s["guide"] != "mesh":
+        raise ValueError("match: warp 'affine' takes its planes from a mesh: it needs guide 'mesh'")
+    if not 1.0 <= s["warp_max"] <= WARP_MAX_LIMIT:
+        raise ValueError(f"match: warp_max in [1, {WARP_MAX_LIMIT:g}], got {s['warp_max']}")
     return s
 
 
@@ -292,8 +394,10 @@ def match_frames(dataset, verts=None, faces=None, **settings):
     [M,3] in the object frame).  matches: per pair (i, j = i + offset) with at least one kept match {i, j, kpts0 f32 [M,2], kpts1 f32
     [M,2], conf f32 [M]} on the CPU -- what Dataset.set_correspondences and scene.write_correspondences_to_disk take.  stats: the
     resolved settings, per pair the queries (grid pixels with a usable source patch), searched (those the guide kept), kept, the count
-    lost to each gate of LOST, the mean s1 of the kept and, with a mesh, the median distance of the kept kpts1 from the guide; totals;
-    seconds."""
+    lost to each gate of LOST, the mean s1 of the kept, warp_dropped (with warp "affine": the queries the guide kept and mesh_affines
+    did not, which are not searched) and, with a mesh, the median distance of the kept kpts1 from the guide; totals; seconds.
+    warp "affine" (guide "mesh" only): both searches sample their source patch through the affine map the mesh's face plane induces
+    between the two frames (mesh_affines, dh_match_search_warp)."""
     t0 = time.time()
     s = check_settings(settings)
     F, H, W = dataset.label.shape
@@ -306,7 +410,8 @@ def match_frames(dataset, verts=None, faces=None, **settings):
     pairs = frame_pairs(F, s["offsets"])
     rows, pid = pair_queries(pix, pairs, F)
     n_queries = torch.bincount(pid, minlength=len(pairs))
-    guide = None
+    guide = affine_fwd = affine_bwd = None
+    warp_dropped = torch.zeros(len(pairs), dtype=torch.int64, device=dev)
     if s["guide"] == "none":
         queries = guide_none(pix, rows, pid, pairs, dataset.label)
     else:
@@ -318,19 +423,25 @@ def match_frames(dataset, verts=None, faces=None, **settings):
         pr = torch.tensor(pairs, dtype=torch.int64, device=dev).reshape(-1, 2)
         fi, fj, p = pr[pid, 0], pr[pid, 1], pix[rows, 1:3].long()
         g, keep, guide = mesh_guesses(fi, fj, p, zbuf, verts, faces, R, T, K, s["depth_eps"], s["min_cos"])
+        if s["warp"] == "affine":
+            _, affine_fwd, affine_bwd, ok = mesh_affines(fi, fj, p, zbuf, verts, faces, R, T, K, s["warp_max"])
+            warp_dropped = torch.bincount(pid[keep & ~ok], minlength=len(pairs))
+            keep = keep & ok
         del zbuf
         sel = keep.nonzero().reshape(-1)
+        if affine_fwd is not None:
+            affine_fwd, affine_bwd = affine_fwd[sel], affine_bwd[sel]
         queries = torch.cat([fi[:, None], fj[:, None], p, g], 1)[sel].to(torch.int32).contiguous()
         pid, guide = pid[sel], guide[sel]
     res = match_pairs(gray, valid, queries, s["patch"], s["range"], s["excl"], s["min_va"], s["zncc_min"], s["peak_margin"],
-                      s["peak_full"], s["fb_px"])
+                      s["peak_full"], s["fb_px"], affine_fwd, affine_bwd)
     npair = len(pairs)
     keep = res["keep"]
     searched = torch.bincount(pid, minlength=npair)
     kept = torch.bincount(pid[keep], minlength=npair)
     lost = torch.stack([torch.bincount(pid[res["lost"] == k + 1], minlength=npair) for k in range(len(LOST))], 1)
     s1_sum = torch.zeros(npair, dtype=torch.float64, device=dev).index_add_(0, pid[keep], res["s1"][keep])
-    counts = torch.cat([n_queries[:, None], searched[:, None], kept[:, None], lost], 1).cpu()
+    counts = torch.cat([n_queries[:, None], searched[:, None], kept[:, None], lost, warp_dropped[:, None]], 1).cpu()
     s1_sum = s1_sum.cpu()
     kq = queries[keep].cpu()
     k1, cf, kp = res["kpts1"][keep].cpu(), res["conf"][keep].cpu(), pid[keep].cpu()
@@ -341,7 +452,7 @@ def match_frames(dataset, verts=None, faces=None, **settings):
         a, b = bounds[k], bounds[k + 1]
         row = {"i": i, "j": j, "queries": int(counts[k, 0]), "searched": int(counts[k, 1]), "kept": int(counts[k, 2]),
                "lost": {name: int(counts[k, 3 + m]) for m, name in enumerate(LOST)},
-               "mean_s1": float(s1_sum[k]) / (b - a) if b > a else None}
+               "mean_s1": float(s1_sum[k]) / (b - a) if b > a else None, "warp_dropped": int(counts[k, 3 + len(LOST)])}
         if dist is not None:
             row["median_guide_px"] = float(dist[a:b].median()) if b > a else None
         per_pair.append(row)
@@ -352,6 +463,6 @@ def match_frames(dataset, verts=None, faces=None, **settings):
              "pairs": per_pair,
              "totals": {"pairs": npair, "queries": int(tot[0]), "searched": int(tot[1]), "kept": int(tot[2]),
                         "kept_share": float(tot[2]) / max(1, int(tot[1])),
-                        "lost": {name: int(tot[3 + m]) for m, name in enumerate(LOST)}},
+                        "lost": {name: int(tot[3 + m]) for m, name in enumerate(LOST)}, "warp_dropped": int(tot[3 + len(LOST)])},
              "seconds": time.time() - t0}
     return matches, stats

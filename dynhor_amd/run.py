@@ -130,6 +130,10 @@ def build_parser():
     ap.add_argument("--match_offsets", type=str, default=None,
                     help="match_frames: frame i is matched to i + every offset of this comma-separated list (default: the config's "
                          "match.offsets, else 1,2,5)")
+    ap.add_argument("--match_warp", type=str, default=None, choices=["none", "affine"],
+                    help="match_frames: 'affine' = with --match_guide mesh, sample every source patch through the affine map that the "
+                         "plane of the mesh face seen there induces between the two frames (wide baselines, in-plane rotation); 'none' = "
+                         "patches as they lie in the image (default: the config's match.warp, else none)")
     # visual_hull only (defaults: the config's visual_hull: block; with the config's mesh_simplify.mode it also writes hull_simple.ply)
     ap.add_argument("--hull_resolution", type=int, default=None,
                     help="visual_hull: grid points per axis of the fine grid, at most 512 (default: the config's visual_hull.resolution, "
@@ -218,7 +222,7 @@ def main():
             print(json.dumps(res), flush=True)
     elif args.mode == "match_frames":
         res = runner.match_frames(guide=args.match_guide, offsets=args.match_offsets, mesh=args.vis_mesh, normalize=args.vis_normalize,
-                                  resolution=args.mesh_resolution)
+                                  resolution=args.mesh_resolution, warp=args.match_warp)
         runner.close()
         if runner.rank == 0:
             import json

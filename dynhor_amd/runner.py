@@ -1334,13 +1334,14 @@ class Runner:
 
     @torch.no_grad()
     def match_frames(self, guide=None, offsets=None, mesh=None, normalize=None, resolution=None, clean=None, extract=None, simplify=None,
-                     save=True, **overrides):
+                     save=True, warp=None, **overrides):
         """Dense correspondences between the frames by guided block matching (dynhor_amd/match.py), set on the dataset
         (Dataset.set_correspondences), so that a run in the same process can train on them (train.corr_weight).  guide: None (the
         config's match.guide) | "none" (the guess is the displacement of the object's box) | "mesh" (the guess comes from a mesh at the
         dataset's current poses, chosen as refine_poses_silhouette chooses it: _select_mesh with `mesh`, `normalize`, `resolution`
-        (default pose_sil.resolution), `clean`, `extract`, `simplify`).  offsets: a list or "1,2,5"; overrides: any key of the config's
-        match: block.  Rank 0 writes <exp>/correspondences/correspondence_infos/<stem_i>_<stem_j>.npz
+        (default pose_sil.resolution), `clean`, `extract`, `simplify`).  offsets: a list or "1,2,5"; warp: None (the config's
+        match.warp) | "none" | "affine" (with the mesh guide: source patches sampled through the affine map of the face plane, for wide
+        baselines); overrides: any key of the config's match: block.  Rank 0 writes <exp>/correspondences/correspondence_infos/<stem_i>_<stem_j>.npz
         (scene.write_correspondences_to_disk with the dataset's stems; point data_info.correspondence_infos at that folder) and
         <exp>/correspondences/match.json (settings, per pair queries / searched / kept and the count lost to each gate, mean s1, with a
         mesh the median distance of the kept matches from the guide, totals, seconds), and logs match/kept and match/kept_share to
@@ -1358,6 +1359,8 @@ class Runner:
             mc["guide"] = guide
         if offsets is not None:
             mc["offsets"] = offsets
+        if warp is not None:
+            mc["warp"] = warp
         verts = faces = name = None
         if (mc.get("guide") or MATCH_DEFAULTS["guide"]) == "mesh":
             pc = dict(POSE_SIL_DEFAULTS)

@@ -694,10 +694,25 @@ int dh_photo_loss_grad(const float* pts, const float* normals, const float* colo
  * The frame indices are checked on the device before the search and the verdict is read back: the call waits for the stream once
  * (out_i's first word is the scratch).  n == 0: no-op.
  * DH_ERR_BAD_ARG: null pointer, misaligned queries / out_i / out_f, negative count, H or W < 1, P outside 1..7, R outside 0..32,
- * excl < 0, min_va < 1, a frame index outside [0, n_frames).  DH_ERR_UNSUPPORTED: n or n_frames >= 2^31, H or W > 2^24. */
+ * excl < 0, min_va < 1, a frame index outside [0, n_frames).  DH_ERR_UNSUPPORTED: n or n_frames >= 2^31, H or W > 2^24.
+ *
+ * dh_match_search_warp: dh_match_search with queries int32 [n,10] = (fi, fj, px, py, gx, gy, a00, a01, a10, a11); A = a / 65536 (Q16)
+ * maps an offset in the target patch to an offset in the source image, and the source patch is sampled through it.  Only the source
+ * patch differs from dh_match_search; va, the flags, the window, the scores, the selection and the sub-pixel step are the same.  Cell
+ * (c, r), c, r in [-P, P], of the source patch, in int64:
+ *   X = px 65536 + a00 c + a01 r, Y = py 65536 + a10 c + a11 r;  x0 = X >> 16, y0 = Y >> 16 (arithmetic shifts: floors, also below 0);
+ *   fx = (X & 0xFFFF) >> 8, fy = (Y & 0xFFFF) >> 8, each in 0..255; the taps (x0 + i, y0 + j), i, j in {0, 1}, weigh
+ *   (256 - fx, fx)[i] (256 - fy, fy)[j] (sum 65536).  A tap of weight 0 is not needed and not read.  The cell is valid iff every
+ *   needed tap lies in the image and has valid != 0; value = (sum w gray + 32768) >> 16 (below 2^32).
+ * With a = (65536, 0, 0, 65536) every cell needs the one tap (px + c, py + r) with weight 65536: every output equals
+ * dh_match_search's bit for bit.  All of it is integer arithmetic: the outputs stay bitwise independent of launch, order and split.
+ * The argument rules are dh_match_search's; the device check of the frame indices also answers DH_ERR_BAD_ARG for a query with an
+ * |a_kl| > 2^19 (a scale of 8). */
 int dh_match_gray(const float* img, int64_t n_frames, int H, int W, float a_min, uint8_t* gray, uint8_t* valid, void* stream);
 int dh_match_search(const uint8_t* gray, const uint8_t* valid, int64_t n_frames, int H, int W, const int32_t* queries, int64_t n, int P,
                     int R, int excl, int64_t min_va, int32_t* out_i, double* out_f, void* stream);
+int dh_match_search_warp(const uint8_t* gray, const uint8_t* valid, int64_t n_frames, int H, int W, const int32_t* queries, int64_t n,
+                         int P, int R, int excl, int64_t min_va, int32_t* out_i, double* out_f, void* stream);
 
 /* ---- image metrics (dynhor_amd/image_metrics.py: renderings scored against the frames, Runner.evaluate_views) ----
  * Integer window sums, a short fp64 formula, no atomics: map and out are bitwise the same from launch to launch and for every split
