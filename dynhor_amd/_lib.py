@@ -122,6 +122,11 @@ SIGNATURES = {
     "dh_photo_loss_sums": (_i32, []),
     "dh_photo_loss_grad_workspace": (_i64, [_i64, _i64]),
     "dh_photo_loss_grad": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
+    "dh_pose_corr_width": (_i32, []),
+    "dh_pose_corr_sums_workspace": (_i64, [_i64, _i64]),
+    "dh_pose_corr_sums": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _i64, _f32, _f32,
+                                 _vp, _vp, _vp, _vp]),
+    "dh_pose_corr_frames": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "dh_match_gray": (_i32, [_vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp]),
     "dh_match_search": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp]),
     "dh_match_search_warp": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp]),

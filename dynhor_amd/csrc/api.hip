@@ -889,6 +889,41 @@ int dh_photo_loss_grad(const float* pts, const float* normals, const float* colo
                                   out, ws, static_cast<hipStream_t>(stream));
 }
 
+int dh_pose_corr_width(void) { return pose_corr_width(); }
+
+int64_t dh_pose_corr_sums_workspace(int64_t n_pairs, int64_t max_count) {
+    if (n_pairs < 0 || max_count < 0) return DH_ERR_BAD_ARG;
+    if (n_pairs > 65535 || max_count >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;
+    return pose_corr_sums_workspace(n_pairs, max_count);
+}
+
+int dh_pose_corr_sums(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* R, const float* T, const float* K,
+                      int64_t n_frames, const uint64_t* zbuf, int64_t n_z, int H, int W, const float* matches, int64_t n_matches,
+                      const int64_t* pairs, int64_t n_pairs, int64_t max_count, float delta_px, float min_cos, double* out, float* resid,
+                      void* ws, void* stream) {
+    if (nv < 0 || nf < 0 || n_frames < 0 || n_matches < 0 || n_pairs < 0 || max_count < 0) return DH_ERR_BAD_ARG;
+    const int rc = sil_args(n_z, H, W);
+    if (rc != DH_OK) return rc;
+    if (!(delta_px > 0.f) || !(min_cos >= 0.f) || delta_px > 1e6f || min_cos > 1.f) return DH_ERR_BAD_ARG;   // NaN, negative, absurd
+    if (nf >= ((int64_t)1 << 32) || n_pairs > 65535 || max_count >= ((int64_t)1 << 31) || n_matches >= ((int64_t)1 << 40)
+        || n_frames >= ((int64_t)1 << 31))
+        return DH_ERR_UNSUPPORTED;                                                                     // grid (slabs, pairs)
+    if (n_pairs == 0) return DH_OK;
+    if (!pairs || !out || !ws || misaligned16(ws)) return DH_ERR_BAD_ARG;
+    if (max_count > 0 && (!R || !T || !K || !zbuf || !matches || n_z == 0 || (nf > 0 && (!verts || !faces)))) return DH_ERR_BAD_ARG;
+    return launch_pose_corr_sums(verts, nv, faces, nf, R, T, K, n_frames, zbuf, n_z, H, W, matches, n_matches, pairs, n_pairs, max_count,
+                                 delta_px, min_cos, out, resid, ws, static_cast<hipStream_t>(stream));
+}
+
+int dh_pose_corr_frames(const double* rows, const double* scale, int64_t n_pairs, const int64_t* start, const int64_t* entries,
+                        int64_t n_entries, int64_t n_frames, double* gR, double* gT, void* stream) {
+    if (n_pairs < 0 || n_entries < 0 || n_frames < 0) return DH_ERR_BAD_ARG;
+    if (n_frames >= ((int64_t)1 << 31) || n_pairs >= ((int64_t)1 << 31) || n_entries >= ((int64_t)1 << 40)) return DH_ERR_UNSUPPORTED;
+    if (n_frames == 0) return DH_OK;
+    if (!start || !gR || !gT || (n_entries > 0 && (!rows || !scale || !entries))) return DH_ERR_BAD_ARG;
+    return launch_pose_corr_frames(rows, scale, n_pairs, start, entries, n_entries, n_frames, gR, gT, static_cast<hipStream_t>(stream));
+}
+
 int dh_match_gray(const float* img, int64_t n_frames, int H, int W, float a_min, uint8_t* gray, uint8_t* valid, void* stream) {
     const int rc = sil_args(n_frames, H, W);
     if (rc != DH_OK) return rc;

@@ -260,6 +260,18 @@ int launch_photo_loss_grad(const float* pts, const float* normals, const float* 
                            const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
                            float depth_eps, float min_cos, float a_min, float delta, double* out, void* ws, hipStream_t st);
 
+// correspondence pose term (pose_corr.hip): loss / pose-gradient sums per frame pair of matches lifted to the mesh (pose_corr_width()
+// doubles per pair, ws = pose_corr_sums_workspace bytes; max_count = the largest count of the pair table, from the host), and the fold
+// of the pairs' rows into per-frame gradients in the order of the host's list
+int pose_corr_width();
+int64_t pose_corr_sums_workspace(int64_t n_pairs, int64_t max_count);
+int launch_pose_corr_sums(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* R, const float* T, const float* K,
+                          int64_t n_frames, const uint64_t* zbuf, int64_t n_z, int H, int W, const float* matches, int64_t n_matches,
+                          const int64_t* pairs, int64_t n_pairs, int64_t max_count, float delta_px, float min_cos, double* out, float* resid,
+                          void* ws, hipStream_t st);
+int launch_pose_corr_frames(const double* rows, const double* scale, int64_t n_pairs, const int64_t* start, const int64_t* entries,
+                            int64_t n_entries, int64_t n_frames, double* gR, double* gT, hipStream_t st);
+
 // dense frame matching (match.hip): 8-bit grey and validity of blurred frames, guided ZNCC block search per query (patch half-size
 // <= match_max_patch(), search range <= match_max_range()); match_check_frames waits for the stream: 0 = every query's frames lie in
 // [0, n_frames), 1 = one does not.  warp: the queries have 10 words, the last four a 2 x 2 map in Q16 through which the source patch is

@@ -12,6 +12,7 @@
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode visualize_mesh --is_continue --turntable 36   # overlays, IoU
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode refine_poses --is_continue --pose_frames worst:5   # silhouette fit
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode refine_poses --is_continue --pose_photo views   # plus a colour term
+    python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode refine_poses --is_continue --pose_corr match    # plus dense matches
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode export_poses --is_continue    # obj_infos/<stem>.npz of the poses
     python -m dynhor_amd.run --config_path X.yaml --mode init_poses --vis_mesh template.obj --vis_normalize reference   # poses from masks
     python -m dynhor_amd.run --config_path X.yaml --mode init_sdf --vis_mesh template.obj --vis_normalize reference     # SDF warm start
@@ -107,6 +108,10 @@ def build_parser():
                     help="refine_poses: add a photometric term next to the silhouette: 'views' colours the mesh being fitted from the "
                          "frames at the current poses, 'mesh' takes the vertex colours (.ply) or the texture (.obj) of --vis_mesh "
                          "(default: the config's pose_photo.mode, else none)")
+    ap.add_argument("--pose_corr", type=str, default=None, choices=["none", "dataset", "match"],
+                    help="refine_poses: add a correspondence term next to the silhouette: 'dataset' uses the matches the dataset holds "
+                         "(data_info.correspondence_infos), 'match' first runs match_frames guided by the mesh being fitted "
+                         "(default: the config's pose_corr.mode, else none)")
     ap.add_argument("--pose_dir", type=str, default=None, help="export_poses: write the .npz files here (default <exp>/poses/<iter>/obj_infos)")
     # render_views / interpolate_<i>_<j> (defaults: the config's surface_render: block)
     ap.add_argument("--views", type=str, default="frames", help="render_views: frames | interpolate:i:j:n | orbit:n")
@@ -194,7 +199,7 @@ def main():
     elif args.mode == "refine_poses":
         res = runner.refine_poses_silhouette(mesh=args.vis_mesh, normalize=args.vis_normalize, resolution=args.mesh_resolution,
                                              clean=args.mesh_clean, extract=args.mesh_extract, frames=args.pose_frames,
-                                             simplify=args.mesh_simplify, photo=args.pose_photo)
+                                             simplify=args.mesh_simplify, photo=args.pose_photo, corr=args.pose_corr)
         runner.close()
         if runner.rank == 0:
             import json

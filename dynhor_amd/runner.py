@@ -25,6 +25,7 @@ from .fields import ParamStore, RenderingNetwork, SDFNetwork, SingleVarianceNetw
 from .match import DEFAULTS as MATCH_DEFAULTS
 from .mesh_extract import DEFAULT_LIPSCHITZ
 from .pose_init import DEFAULTS as POSE_INIT_DEFAULTS
+from .pose_corr import DEFAULTS as POSE_CORR_DEFAULTS
 from .pose_photo import DEFAULTS as POSE_PHOTO_DEFAULTS
 from .pose_sil import DEFAULTS as POSE_SIL_DEFAULTS
 from .renderer import NeuSRenderer
@@ -64,6 +65,9 @@ DEFAULT_CONF = {
     # the optional photometric term of refine_poses (--pose_photo): dynhor_amd/pose_photo.py says what each number is,
     # DESIGN_NEXT_ROWS.md section 19 where it comes from; mode none | views | mesh
     "pose_photo": dict(POSE_PHOTO_DEFAULTS),
+    # the optional correspondence term of refine_poses (--pose_corr): dynhor_amd/pose_corr.py says what each number is,
+    # DESIGN_NEXT_ROWS.md section 24 where it comes from; mode none | dataset | match
+    "pose_corr": dict(POSE_CORR_DEFAULTS),
     # pose initialisation from a template mesh (--mode init_poses): dynhor_amd/pose_init.py says what each number is,
     # DESIGN_NEXT_ROWS.md section 16 where it comes from; its final joint refinement takes the pose_sil: block
     "pose_init": dict(POSE_INIT_DEFAULTS),
@@ -1180,7 +1184,7 @@ class Runner:
         return make_term(verts, faces, self.dataset, vertex_colors=colors.to(self.device), **kw)
 
     def refine_poses_silhouette(self, mesh=None, normalize=None, resolution=None, clean=None, extract=None, frames=None, save=True,
-                                simplify=None, photo=None, **overrides):
+                                simplify=None, photo=None, corr=None, **overrides):
         """Every frame's pose refined against a mesh by silhouette matching (dynhor_amd/pose_sil.py) and written into Dataset.R /
         Dataset.T.  The mesh is chosen as visualize_mesh chooses it (_select_mesh; `mesh` and `normalize` left at None take the config's
         mesh_vis: block): the .ply / .obj file `mesh` (normalize "none" | "reference"), else the reconstruction extracted at
@@ -1197,7 +1201,14 @@ class Runner:
         photo: None (the config's pose_photo.mode) | "none" | "views" | "mesh": add the photometric term of dynhor_amd/pose_photo.py
         (_photo_term says where the colours come from; the other keys of the pose_photo: block are its settings).  refine.json then
         carries `photo`, the loss_photo curve and the contributing pairs per refined frame (photo_pairs), and pose/loss_photo goes to
-        the board.  With "none" everything is exactly what it is without the term."""
+        the board.  With "none" everything is exactly what it is without the term.
+        corr: None (the config's pose_corr.mode) | "none" | "dataset" | "match": add the correspondence term of dynhor_amd/pose_corr.py
+        over the matches the dataset holds ("dataset": data_info.correspondence_infos, or an earlier match_frames of this process) or
+        over matches made first by match_frames guided by the very mesh being fitted ("match"; they are not refreshed while the poses
+        move).  The other keys of the pose_corr: block are its settings.  refine.json then carries `corr`, settings["corr"], the
+        loss_corr curve, corr_resid_before / corr_resid_after and corr_worst, and pose/loss_corr goes to the board.  With "none"
+        everything is exactly what it is without the term."""
+        from .pose_corr import MODES as CORR_MODES
         from .pose_photo import MODES as PHOTO_MODES
         from .pose_sil import refine_poses
         if self.world > 1:
@@ -1215,8 +1226,16 @@ class Runner:
         if unknown or pmode not in PHOTO_MODES:
             raise ValueError(f"refine_poses_silhouette: pose_photo mode {pmode!r} (one of {PHOTO_MODES}), unknown setting(s) {unknown}; "
                              f"known: {sorted(POSE_PHOTO_DEFAULTS)}")
+        cc = dict(POSE_CORR_DEFAULTS)
+        cc.update(self.conf.get("pose_corr") or {})
+        unknown = sorted(set(cc) - set(POSE_CORR_DEFAULTS))
+        kmode = corr if corr is not None else cc["mode"]
+        if unknown or kmode not in CORR_MODES:
+            raise ValueError(f"refine_poses_silhouette: pose_corr mode {kmode!r} (one of {CORR_MODES}), unknown setting(s) {unknown}; "
+                             f"known: {sorted(POSE_CORR_DEFAULTS)}")
         vc = dict(MESH_VIS_DEFAULTS)
         vc.update(self.conf.get("mesh_vis") or {})
+        mesh_arg, normalize_arg, resolution_arg = mesh, normalize, resolution
         mesh = mesh if mesh is not None else vc["mesh"]
         normalize = normalize if normalize is not None else vc["normalize"]
         resolution = int(resolution if resolution is not None else pc["resolution"])
@@ -1225,15 +1244,30 @@ class Runner:
         if faces.shape[0] == 0:
             raise ValueError(f"refine_poses_silhouette: the mesh {name} has no faces")
         verts, faces = verts.to(torch.float32).contiguous(), faces.to(torch.int64).contiguous()
+        corr_term = None
+        if kmode != "none":
+            from .pose_corr import make_term as make_corr_term
+            if kmode == "match":
+                self.match_frames(guide="mesh", mesh=mesh_arg, normalize=normalize_arg, resolution=resolution_arg, clean=clean,
+                                  extract=extract, simplify=simplify, save=save)
+            if self.dataset.corr is None:
+                raise ValueError("refine_poses_silhouette: pose_corr 'dataset' needs correspondences and the dataset holds none: point "
+                                 "data_info.correspondence_infos at a folder of matches, run --mode match_frames first, or use "
+                                 "--pose_corr match")
+            corr_term = lambda active: make_corr_term(self.dataset, active=active, delta_px=float(cc["delta_px"]),
+                                                      min_cos=float(cc["min_cos"]), min_conf=float(cc["min_conf"]),
+                                                      frame_chunk=int(pc["frame_chunk"]))
         res = refine_poses(verts, faces, self.dataset, iters=pc["iters"], lr=pc["lr"], rot_lr_mult=pc["rot_lr_mult"],
                            sigma_px=pc["sigma_px"], sigma_end_px=pc["sigma_end_px"], cut=pc["cut"], edge_offset_px=pc["edge_offset_px"],
                            lw_sil=pc["lw_sil"], lw_smooth=pc["lw_smooth"], frame_chunk=pc["frame_chunk"], report_freq=pc["report_freq"],
-                           frames=frames, lw_photo=float(pp["lw_photo"]),
+                           frames=frames, lw_photo=float(pp["lw_photo"]), corr=corr_term, lw_corr=float(cc["lw_corr"]),
                            photo=None if pmode == "none" else self._photo_term(pmode, pp, verts, faces, mesh, cmode, smode))
         res.pop("R"); res.pop("T")
         res.update(iter=self.iter_step, mesh=name, clean=cmode, faces=int(faces.shape[0]))
         if pmode != "none":
             res.update(photo=pmode)
+        if kmode != "none":
+            res.update(corr=kmode)
         if smode != "none":
             res.update(simplify=smode)
         if self.pose_refiner is not None:
@@ -1259,6 +1293,8 @@ class Runner:
                     self._board.add_scalar("pose_sil/" + k, float(st[k]), int(st["iter"]))
                 if "loss_photo" in st:
                     self._board.add_scalar("pose/loss_photo", float(st["loss_photo"]), int(st["iter"]))
+                if "loss_corr" in st:
+                    self._board.add_scalar("pose/loss_corr", float(st["loss_corr"]), int(st["iter"]))
             for k in ("iou_mean_before", "iou_mean_after"):
                 if res[k] is not None:
                     self._board.add_scalar("pose_sil/" + k, float(res[k]), self.iter_step)

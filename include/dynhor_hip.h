@@ -668,6 +668,53 @@ int dh_photo_loss_grad(const float* pts, const float* normals, const float* colo
                        const uint64_t* zbuf, const float* R, const float* T, const float* K, int64_t n_frames, int H, int W,
                        float depth_eps, float min_cos, float a_min, float delta, double* out, void* ws, void* stream);
 
+/* ---- correspondence pose term (dynhor_amd/pose_corr.py: dense matches between frames, next to the silhouette) ----
+ * All arithmetic is fp64 from fp32 inputs.  Pixel centres are integers, x is the column, K is upper triangular with K22 = 1.
+ *
+ * dh_pose_corr_sums: out f64 [n_pairs, dh_pose_corr_width() = 28] for the mesh verts f32 [nv,3], faces i64 [nf,3]; the poses R f32
+ * [n_frames,3,3], T f32 [n_frames,3] (object -> camera) of ALL frames and K f32 [3,3]; zbuf u64 [n_z,H,W] = dh_mesh_raster_depth of
+ * that mesh at the current poses of a chunk of source frames (only the face index in the low 32 bits is read); matches f32
+ * [n_matches,5] = (p_x, p_y, q_x, q_y, c): p the integer pixel in frame i, q the sub-pixel position in frame j, c the confidence;
+ * pairs i64 [n_pairs,5] = (z-buffer slot of frame i, i, j, first match, count): a pair's matches are consecutive.  max_count: a bound
+ * on the counts from the host (it sizes the grid and ws; it does not change a result).  Per match:
+ *   d = K^-1 (p_x, p_y, 1): d_y = (p_y - K12) / K11, d_x = (p_x - K02 - K01 d_y) / K00, d_z = 1;
+ *   f = the face of zbuf[slot] at the pixel (floor(p_x + 0.5), floor(p_y + 0.5));  a = v0(f), n = (v1 - v0) x (v2 - v0);
+ *   o = -R_i^T T_i, e = R_i^T d, s = n.(a - o) / (n.e), X = o + s e   (this form is the contract: the derivative below is entrywise
+ *   in R_i and belongs to it; R_i^T stands for the inverse);
+ *   Y = R_j X + T_j, u = (K00 Y_x + K01 Y_y + K02 Y_z) / Y_z, w = (K11 Y_y + K12 Y_z) / Y_z, r = (u, w) - q,
+ *   rho = huber(|r|), huber(x) = x^2 / 2 for x <= delta_px, else delta_px (x - delta_px / 2); the weight c is constant in the gradient.
+ * A match counts when the pixel lies in the image, zbuf is not empty there and f < nf (and the face's vertices < nv), |n|^2 > 0,
+ * |n.e| >= min_cos |n| |e|, s > 1e-3, Y_z > 1e-3, c > 0 and every input (the match, both poses, K, the face's vertices) and |r| is finite.
+ * With g = huber'(|r|) r / |r| (0 at r = 0) and G = c (g_u du/dY + g_w dw/dY), du/dY = (K00, K01, K02 - u) / Y_z, dw/dY = (0, K11,
+ * K12 - w) / Y_z:   frame j: d/dR_j = G X^T, d/dT_j = G;   frame i: om = R_j^T G, om' = om - n (om.e) / (n.e), d/dR_i = (s d - T_i) om'^T,
+ * d/dT_i = -R_i om'.
+ *   [0] sum c rho  [1] sum c  [2..10] d/dR_i row-major  [11..13] d/dT_i  [14..22] d/dR_j  [23..25] d/dT_j  [26] counted matches
+ *   [27] counted matches with |r| <= delta_px
+ * resid f32 [n_matches] or null: |r| of every match of a usable pair, -1 where the match does not count (a match of no pair, or of an
+ * unusable one, is left as it is).  One lane per match, workgroups over slabs of 256 matches of one pair; every workgroup stores its
+ * partial (ws: dh_pose_corr_sums_workspace(n_pairs, max_count) bytes, 16-byte aligned) and a second kernel adds a pair's partials in
+ * slab order: no atomics, a pair's row is bitwise the same from launch to launch, for every order of the pairs and every split of them
+ * into calls.  i == j is allowed.  A pair whose slot lies outside [0, n_z), whose i or j lies outside [0, n_frames), whose matches do
+ * not lie in [0, n_matches) or whose count exceeds max_count gets a row of zeros.  n_pairs == 0: no-op; count == 0: a row of zeros.
+ * DH_ERR_BAD_ARG: null pointer (ws included; resid may be null; with max_count == 0 only pairs, out, ws are read), misaligned ws,
+ * negative count, H or W < 1, delta_px not > 0, min_cos outside [0, 1], NaN.  DH_ERR_UNSUPPORTED: n_pairs > 65535, max_count >= 2^31,
+ * nf >= 2^32, n_matches >= 2^40, H or W > 2^24.
+ *
+ * dh_pose_corr_frames: the rows f64 [n_pairs,28] of every pair of a step folded into gR f64 [n_frames,9], gT f64 [n_frames,3]:
+ * frame f adds, for k = start[f] .. start[f+1] - 1 in this order, scale[pair] * rows[pair, 2..13] where entries[k] = 2 pair + 0
+ * (f is the pair's i) or scale[pair] * rows[pair, 14..25] where entries[k] = 2 pair + 1 (f is its j); start i64 [n_frames + 1],
+ * entries i64 [n_entries], scale f64 [n_pairs].  A frame with no entry gets zeros; an entry that names no pair is skipped.  The order
+ * of the additions is the list's: bitwise the same from launch to launch.  n_frames == 0: no-op.  DH_ERR_BAD_ARG: null pointer (rows,
+ * scale, entries may be null with n_entries == 0), negative count.  DH_ERR_UNSUPPORTED: n_frames or n_pairs >= 2^31, n_entries >= 2^40. */
+int dh_pose_corr_width(void);
+int64_t dh_pose_corr_sums_workspace(int64_t n_pairs, int64_t max_count);
+int dh_pose_corr_sums(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* R, const float* T, const float* K,
+                      int64_t n_frames, const uint64_t* zbuf, int64_t n_z, int H, int W, const float* matches, int64_t n_matches,
+                      const int64_t* pairs, int64_t n_pairs, int64_t max_count, float delta_px, float min_cos, double* out, float* resid,
+                      void* ws, void* stream);
+int dh_pose_corr_frames(const double* rows, const double* scale, int64_t n_pairs, const int64_t* start, const int64_t* entries,
+                        int64_t n_entries, int64_t n_frames, double* gR, double* gT, void* stream);
+
 /* ---- dense frame matching (dynhor_amd/match.py: guided block matching by zero-mean normalised cross-correlation, ZNCC) ----
  * Integer sums, fp64 scores, no atomics in the search: every output is bitwise the same from launch to launch, for every order of the
  * queries and for every split of them into calls.  Pixel centres are integers; x is the column.
