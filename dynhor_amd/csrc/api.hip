@@ -1150,4 +1150,39 @@ int dh_trace_compose(const uint8_t* state, const float* t, const float* d, const
                                 frame_idx, n_frames, N, rgb, depth, normal, hit, static_cast<hipStream_t>(stream));
 }
 
+int dh_mvs_sweep(const uint8_t* gray, const uint8_t* valid, int64_t n_frames, int H, int W, const float* R, const float* T, const float* K,
+                 const float* Kinv, const int32_t* pix, const float* guide, int64_t n, const int32_t* nbr, int n_nbr, int D, float step,
+                 int P, int64_t min_va, float min_vb, int min_views, float min_cos, float* out_f, int32_t* out_i, void* stream) {
+    if (n < 0) return DH_ERR_BAD_ARG;
+    const int rc = sil_args(n_frames, H, W);
+    if (rc != DH_OK) return rc;
+    if (P < 1 || P > mvs_max_patch() || D < 3 || D > mvs_max_depths() || (D & 1) == 0 || n_nbr < 1 || n_nbr > mvs_max_neighbours() ||
+        min_va < 1 || !(min_vb > 0.f) || min_views < 1 || !(step > 0.f) || !std::isfinite(step) || !std::isfinite(min_vb) ||
+        !(min_cos >= -1.f && min_cos <= 1.f))
+        return DH_ERR_BAD_ARG;
+    if (n >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;                                          // at least one pixel per wave
+    if (n == 0) return DH_OK;
+    if (!gray || !valid || !R || !T || !K || !Kinv || !pix || !guide || !nbr || !out_f || !out_i ||
+        ((reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(T) | reinterpret_cast<uintptr_t>(K) |
+          reinterpret_cast<uintptr_t>(Kinv) | reinterpret_cast<uintptr_t>(pix) | reinterpret_cast<uintptr_t>(guide) |
+          reinterpret_cast<uintptr_t>(nbr) | reinterpret_cast<uintptr_t>(out_f) | reinterpret_cast<uintptr_t>(out_i)) & 3u) != 0)
+        return DH_ERR_BAD_ARG;
+    return launch_mvs_sweep(gray, valid, (int)n_frames, H, W, R, T, K, Kinv, pix, guide, n, nbr, n_nbr, D, step, P, min_va, min_vb,
+                            min_views, min_cos, out_f, out_i, static_cast<hipStream_t>(stream));
+}
+
+int dh_mvs_check(const float* depth, int64_t n_frames, int H, int W, const float* R, const float* T, const float* K, const float* Kinv,
+                 const int32_t* nbr, int n_nbr, float depth_rel, uint8_t* count, void* stream) {
+    const int rc = sil_args(n_frames, H, W);
+    if (rc != DH_OK) return rc;
+    if (n_nbr < 1 || n_nbr > mvs_max_neighbours() || !(depth_rel >= 0.f) || !std::isfinite(depth_rel)) return DH_ERR_BAD_ARG;
+    if (n_frames * H * W >= ((int64_t)1 << 38)) return DH_ERR_UNSUPPORTED;                             // one 1-D grid of 256 pixels per workgroup
+    if (n_frames == 0) return DH_OK;
+    if (!depth || !R || !T || !K || !Kinv || !nbr || !count ||
+        ((reinterpret_cast<uintptr_t>(depth) | reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(T) |
+          reinterpret_cast<uintptr_t>(K) | reinterpret_cast<uintptr_t>(Kinv) | reinterpret_cast<uintptr_t>(nbr)) & 3u) != 0)
+        return DH_ERR_BAD_ARG;
+    return launch_mvs_check(depth, (int)n_frames, H, W, R, T, K, Kinv, nbr, n_nbr, depth_rel, count, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

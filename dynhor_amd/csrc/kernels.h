@@ -325,4 +325,16 @@ int launch_simplify_quadrics(const float* verts, int64_t nv, const int64_t* face
 int launch_simplify_faces(const int64_t* faces, int64_t nf, const int32_t* vrank, int64_t nv, int64_t n_runs, int64_t* tri, uint8_t* keep,
                           int64_t* key, hipStream_t st);
 
+// multi-view stereo (mvs.hip): a plane sweep per pixel about a guide depth, scored by fp32 ZNCC over bilinear taps against up to
+// mvs_max_neighbours() frames (patch half-size <= mvs_max_patch(), 3 <= D <= mvs_max_depths(), D odd), and the count of neighbours whose
+// depth map agrees with a pixel's depth
+int mvs_max_patch();
+int mvs_max_depths();
+int mvs_max_neighbours();
+int launch_mvs_sweep(const uint8_t* gray, const uint8_t* valid, int n_frames, int H, int W, const float* R, const float* T, const float* K,
+                     const float* Kinv, const int32_t* pix, const float* guide, int64_t n, const int32_t* nbr, int n_nbr, int D, float step,
+                     int P, int64_t min_va, float min_vb, int min_views, float min_cos, float* out_f, int32_t* out_i, hipStream_t st);
+int launch_mvs_check(const float* depth, int n_frames, int H, int W, const float* R, const float* T, const float* K, const float* Kinv,
+                     const int32_t* nbr, int n_nbr, float depth_rel, uint8_t* count, hipStream_t st);
+
 }  // namespace dh

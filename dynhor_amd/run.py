@@ -22,6 +22,7 @@
     python -m dynhor_amd.run --config_path X.yaml --mode refine_poses --vis_mesh exps/<seq>/<exp>/hull/hull.ply   # poses fitted to the hull
     python -m dynhor_amd.run --config_path X.yaml --mode match_frames --match_offsets 1,2,5   # correspondence_infos from the frames
     python -m dynhor_amd.run --config_path X.yaml --mode match_frames --is_continue --match_guide mesh   # guided by the reconstruction
+    python -m dynhor_amd.run --config_path X.yaml --mode mvs_depth --vis_mesh hull.ply   # depth and normal maps by plane-sweep stereo
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode render_views --is_continue   # every frame sphere-traced: png, normal, depth, PSNR, IoU
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode render_views --is_continue --views orbit:36 --view_level 2
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode evaluate_views --is_continue   # masked SSIM, PSNR, L1 of the held-out frames
@@ -38,7 +39,7 @@ import sys
 
 
 MODES = ("train", "validate_image", "validate_mesh", "evaluate_mesh", "visualize_mesh", "refine_poses", "export_poses", "init_poses",
-         "init_sdf", "render_views", "match_frames", "evaluate_views", "visual_hull")
+         "init_sdf", "render_views", "match_frames", "evaluate_views", "visual_hull", "mvs_depth")
 
 
 def mode_arg(value: str) -> str:
@@ -146,6 +147,17 @@ def build_parser():
     ap.add_argument("--hull_votes", type=int, default=None,
                     help="visual_hull: a point is outside the hull when this many frames say so; K > 1 tolerates K - 1 frames with a "
                          "wrong pose or mask (default: the config's visual_hull.min_carve_votes, else 1)")
+    # mvs_depth only (defaults: the config's optional mvs: block, else mvs.DEFAULTS -- first settings, not tuned; the guide mesh is chosen
+    # by --vis_mesh / --vis_normalize / --mesh_resolution as for match_frames --match_guide mesh, cleaned, extracted and simplified as
+    # the config's mesh_* blocks say)
+    ap.add_argument("--mvs_offsets", type=str, default=None,
+                    help="mvs_depth: the neighbours of frame i are i - o and i + o for every offset o of this comma-separated list, at "
+                         "most four (default: the config's mvs.offsets, else 1,2)")
+    ap.add_argument("--mvs_range", type=float, default=None,
+                    help="mvs_depth: the sweep covers this many object units either side of the guide mesh (default: the config's "
+                         "mvs.range, else 0.04)")
+    ap.add_argument("--mvs_step_px", type=int, default=None,
+                    help="mvs_depth: sweep the pixels of a grid of this step (default: the config's mvs.step_px, else 1)")
     return ap
 
 
@@ -232,6 +244,13 @@ def main():
         if runner.rank == 0:
             import json
             print(json.dumps({k: v for k, v in res.items() if k not in ("pairs", "steps")}), flush=True)
+    elif args.mode == "mvs_depth":
+        res = runner.mvs_depth(mesh=args.vis_mesh, normalize=args.vis_normalize, resolution=args.mesh_resolution,
+                               offsets=args.mvs_offsets, range=args.mvs_range, step_px=args.mvs_step_px)
+        runner.close()
+        if runner.rank == 0:
+            import json
+            print(json.dumps({k: v for k, v in res.items() if k != "per_frame"}), flush=True)
     elif args.mode == "render_views" or args.mode.startswith("interpolate_"):
         if args.mode == "render_views":
             views, level, method = args.views, args.view_level, args.view_method

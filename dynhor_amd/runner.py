@@ -24,6 +24,7 @@ from .dataset import Dataset
 from .fields import ParamStore, RenderingNetwork, SDFNetwork, SingleVarianceNetwork
 from .match import DEFAULTS as MATCH_DEFAULTS
 from .mesh_extract import DEFAULT_LIPSCHITZ
+from .mvs import DEFAULTS as MVS_DEFAULTS
 from .pose_init import DEFAULTS as POSE_INIT_DEFAULTS
 from .pose_corr import DEFAULTS as POSE_CORR_DEFAULTS
 from .pose_photo import DEFAULTS as POSE_PHOTO_DEFAULTS
@@ -1430,6 +1431,81 @@ class Runner:
                 self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
             self._board.add_scalar("match/kept", float(res["totals"]["kept"]), self.iter_step)
             self._board.add_scalar("match/kept_share", float(res["totals"]["kept_share"]), self.iter_step)
+            self._board.flush()
+        return res
+
+    @torch.no_grad()
+    def mvs_depth(self, mesh=None, normalize=None, resolution=None, clean=None, extract=None, simplify=None, frames=None, save=True,
+                  **overrides):
+        """Per-frame depth and normal maps and a fused point cloud from the frames' texture, by a plane sweep about a guide mesh at the
+        dataset's current poses (dynhor_amd/mvs.py).  The guide is chosen as match_frames with guide "mesh" chooses it: _select_mesh
+        with `mesh`, `normalize`, `resolution` (default pose_sil.resolution), `clean`, `extract`, `simplify` -- the reconstruction, the
+        template, the hull or a scan.  frames: None (all) or a list of frame indices; overrides: any key of the config's optional mvs:
+        block (mvs.DEFAULTS: first settings, not tuned); an unknown key raises.  Rank 0 writes under <exp>/mvs/<iter:08d>/:
+        depth/<stem>.npy (camera z, f32, inf where not kept: render_views' _depth.npy convention), monocular_normal/<stem>.png (the
+        loader's encoding round((n 0.5 + 0.5) 255) in the camera frame, 128 where there is no normal), cloud.ply (points, normals,
+        colours; thinned to one point per mvs.voxel cell when the override `voxel` is given) and mvs.json (settings, per frame the pixels
+        swept, the count lost to each gate, the kept share, the mean c_best, the median and 95th percentile of |z - z_guide|; totals,
+        seconds per phase, the five frames with the lowest kept share), and logs mvs/kept_share and mvs/guide_dev_median to
+        <exp>/board.  Pointing data_info's monocular_normal/ at that folder is the user's step.  Returns the dict of mvs.json plus dir
+        (single process: run it on one rank)."""
+        from . import mvs
+        if self.world > 1:
+            raise ValueError("mvs_depth runs on one rank")
+        voxel = overrides.pop("voxel", None)
+        block = dict(self.conf.get("mvs") or {})
+        block_voxel = block.pop("voxel", None)
+        voxel = block_voxel if voxel is None else voxel
+        for where, keys in (("", overrides), (" in the config", block)):
+            unknown = sorted(set(keys) - set(MVS_DEFAULTS))
+            if unknown:
+                raise ValueError(f"mvs_depth: unknown mvs setting(s) {unknown}{where}; known: {sorted(MVS_DEFAULTS) + ['voxel']}")
+        mc = dict(block)
+        mc.update({k: v for k, v in overrides.items() if v is not None})
+        mvs.check_settings(mc)
+        pc = dict(POSE_SIL_DEFAULTS)
+        pc.update(self.conf.get("pose_sil") or {})
+        vc = dict(MESH_VIS_DEFAULTS)
+        vc.update(self.conf.get("mesh_vis") or {})
+        mesh = mesh if mesh is not None else vc["mesh"]
+        normalize = normalize if normalize is not None else vc["normalize"]
+        resolution = int(resolution if resolution is not None else pc["resolution"])
+        verts, faces, name, _ = self._select_mesh("mvs_depth", mesh, normalize, resolution, clean, extract, simplify)
+        if faces.shape[0] == 0:
+            raise ValueError(f"mvs_depth: the mesh {name} has no faces")
+        verts, faces = verts.to(torch.float32).contiguous(), faces.to(torch.int64).contiguous()
+        ds = self.dataset
+        out = mvs.depth_maps(ds, verts, faces, frames=frames, **mc)
+        res = out["stats"]
+        res.update(iter=self.iter_step, mesh=name, voxel=voxel)
+        if save and self.rank == 0:
+            import time
+            from PIL import Image
+            t0 = time.time()
+            d = os.path.join(self.base_exp_dir, "mvs", f"{self.iter_step:08d}")
+            os.makedirs(os.path.join(d, "depth"), exist_ok=True)
+            os.makedirs(os.path.join(d, "monocular_normal"), exist_ok=True)
+            stems = ds.stems if ds.stems is not None else ["%04d" % f for f in range(ds.n_images)]
+            todo = [r["frame"] for r in res["per_frame"]]
+            for f in todo:
+                z = torch.where(out["kept"][f], out["depth"][f], torch.full_like(out["depth"][f], float("inf")))
+                np.save(os.path.join(d, "depth", stems[f] + ".npy"), z.cpu().numpy())
+                enc = mvs.encode_normals(out["normal"][f], out["normal_ok"][f])
+                Image.fromarray(enc.cpu().numpy()).save(os.path.join(d, "monocular_normal", stems[f] + ".png"))
+            pts, nrm, col, _ = mvs.fuse(out["depth"], out["kept"], out["normal"], out["normal_ok"], ds.rgb, ds.R, ds.T, ds.K, voxel)
+            mvs.write_cloud_ply(os.path.join(d, "cloud.ply"), pts, nrm, col)
+            res["cloud_points"] = int(pts.shape[0])
+            res["seconds"]["write"] = time.time() - t0
+            with open(os.path.join(d, "mvs.json"), "w") as f:
+                json.dump(res, f, indent=1)
+            res["dir"] = d
+            self.last_mvs_dir = d
+            if self._board is None:
+                from .tb_events import make_writer
+                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+            self._board.add_scalar("mvs/kept_share", float(res["totals"]["kept_share"]), self.iter_step)
+            if res["totals"]["guide_dev_median"] is not None:
+                self._board.add_scalar("mvs/guide_dev_median", float(res["totals"]["guide_dev_median"]), self.iter_step)
             self._board.flush()
         return res
 

@@ -929,6 +929,52 @@ int dh_trace_compose(const uint8_t* state, const float* t, const float* d, const
                      const uint8_t* frame_rgb, const int32_t* frame_idx, int n_frames, uint8_t* rgb, float* depth, uint8_t* normal,
                      uint8_t* hit, void* stream);
 
+/* ---- multi-view stereo (dynhor_amd/mvs.py: a mesh-guided plane sweep and a consistency count between depth maps) ----
+ * fp32 throughout, every operation an IEEE operation as written (no contraction), every sum in a fixed order, no atomics: a pixel's
+ * outputs depend on that pixel's inputs alone and are bitwise the same for every order of the pixels and every split into calls.
+ * Pixel centres are integers; x is the column.  dot(a, b) below is (a0 b0 + a1 b1) + a2 b2; a 3 x 3 product uses it per entry.
+ *
+ * dh_mvs_sweep: gray, valid u8 [n_frames,H,W] (dh_match_gray); R f32 [n_frames,9], T f32 [n_frames,3]; K, Kinv f32 [9] in DEVICE memory
+ * (Kinv inverted on the host in fp64); pix int32 [n,3] = (fi, px, py); guide f32 [n,4] = (z0, nx, ny, nz): the guide's camera z at the
+ * pixel and the unit plane normal in frame fi's camera frame; nbr int32 [n_frames,n_nbr]: the neighbour frames of every frame, an entry
+ * outside [0, n_frames) (-1) means none; 1 <= n_nbr <= 8; D odd in 3..63; step > 0; P in 1..7 (N = (2P+1)^2); min_va >= 1; min_vb > 0;
+ * min_views >= 1; min_cos in [-1, 1].  Per pixel, with p = (px, py, 1) as floats:
+ *   source: the patch a about (px, py) of frame fi; flag 1 when a pixel of it lies outside the image or is invalid, fi lies outside
+ *     [0, n_frames), or va = N sum a^2 - (sum a)^2 < min_va (exact integers, as dh_match_search).
+ *   guide: e = Kinv p, e_r = (Kinv[r][0] px + Kinv[r][1] py) + Kinv[r][2]; flag 8 unless z0 is finite, z0 > 1e-3 and
+ *     -dot(n, e) / sqrt(dot(e, e)) >= min_cos (a NaN fails).  With flag 1 or 8 nothing is swept.
+ *   hypothesis k in [0, D): z_k = z0 + float(k - (D-1)/2) * step, X_k = z_k e; invalid unless z_k > 1e-3.  d = dot(n, X_k), s = n / d.
+ *   neighbour j = nbr[fi][.]: R_ij[r][c] = dot(R_j row r, R_i row c), t_ij[r] = T_j[r] - dot(R_ij row r, T_i),
+ *     M[r][c] = R_ij[r][c] + t_ij[r] s[c], G = K M, Hm = G Kinv (entry [r][c] = dot(row r, column c)), h = Hm p with
+ *     h_r = (Hm[r][0] px + Hm[r][1] py) + Hm[r][2]; invalid for j unless h_2 > 1e-3.  q = (h_0 / h_2, h_1 / h_2),
+ *     A = [[(Hm00 - q_x Hm20) / h_2, (Hm01 - q_x Hm21) / h_2], [(Hm10 - q_y Hm20) / h_2, (Hm11 - q_y Hm21) / h_2]].
+ *   tap (c, r), c, r in [-P, P], row-major: (tx, ty) = (q_x + (A00 c + A01 r), q_y + (A10 c + A11 r)); it needs the four pixels
+ *     (floor tx + {0, 1}, floor ty + {0, 1}) whatever the fractions: j is invalid for this hypothesis unless 0 <= tx < W - 1,
+ *     0 <= ty < H - 1 (a NaN fails) and all four are valid.  wx = tx - floor tx, wy = ty - floor ty, top = g00 + wx (g01 - g00),
+ *     bot = g10 + wx (g11 - g10), b = top + wy (bot - top); sb += b, sb2 += b b, sab += a b in this order from 0.
+ *   score: vb = N sb2 - sb sb; j is invalid unless vb >= min_vb; score = (N sab - float(sum a) sb) / sqrt(float(va) vb).
+ *     c_k = (the scores of the valid neighbours added in nbr's order) / their number when that is >= min_views, else NONE = -2.
+ *   result: k* = the largest c_k, the lowest k on a tie; c_second = the largest c_k with |k - k*| > 1, else -2; flag 2: no valid
+ *     hypothesis; flag 4: k* is 0 or D - 1; sub = min(max((0.5 (c_{k*-1} - c_{k*+1})) / den, -0.5), 0.5) with
+ *     den = (c_{k*-1} - 2 c_{k*}) + c_{k*+1} when den < 0, neither neighbour is NONE and flag 4 is not set, else 0;
+ *     z = z0 + (float(k* - (D-1)/2) + sub) * step.
+ * out_f f32 [n,4] = (z, c_best, c_second, sub); out_i int32 [n,4] = (k*, valid neighbours at k*, flags, valid hypotheses).  With flag
+ * 1, 2 or 8: (0, -2, -2, 0) and (0, 0, flags, 0).  Runs on `stream` and does not wait for it.  n == 0: no-op.
+ * DH_ERR_BAD_ARG: null or misaligned pointer, negative count, H or W < 1, a setting outside the ranges above, NaN.
+ * DH_ERR_UNSUPPORTED: n or n_frames >= 2^31, H or W > 2^24.
+ *
+ * dh_mvs_check: depth f32 [n_frames,H,W] (NaN or inf: none) -> count u8 [n_frames,H,W].  A pixel (px, py) of frame i with depth z:
+ * c = z (Kinv p) - T_i per component, X = R_i^T c, and for every neighbour j of nbr (as above): y = R_j X + T_j; j is skipped unless
+ * y_2 > 1e-3; (u, w) = (floor(dot(K row 0, y) / y_2 + 0.5), floor(dot(K row 1, y) / y_2 + 0.5)); skipped unless 0 <= u < W,
+ * 0 <= w < H and z_j = depth[j][w][u] is finite; j agrees when |y_2 - z_j| <= depth_rel z_j.  count = the number of agreeing
+ * neighbours (0 without a depth).  depth_rel >= 0.  n_frames == 0: no-op.  DH_ERR_BAD_ARG: null or misaligned pointer, negative
+ * n_frames, H or W < 1, n_nbr outside 1..8, depth_rel negative or not finite.  DH_ERR_UNSUPPORTED: H or W > 2^24, n_frames H W >= 2^38. */
+int dh_mvs_sweep(const uint8_t* gray, const uint8_t* valid, int64_t n_frames, int H, int W, const float* R, const float* T, const float* K,
+                 const float* Kinv, const int32_t* pix, const float* guide, int64_t n, const int32_t* nbr, int n_nbr, int D, float step,
+                 int P, int64_t min_va, float min_vb, int min_views, float min_cos, float* out_f, int32_t* out_i, void* stream);
+int dh_mvs_check(const float* depth, int64_t n_frames, int H, int W, const float* R, const float* T, const float* K, const float* Kinv,
+                 const int32_t* nbr, int n_nbr, float depth_rel, uint8_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
