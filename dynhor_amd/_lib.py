@@ -132,6 +132,7 @@ SIGNATURES = {
     "dh_match_search_warp": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp]),
     "dh_mvs_sweep": (_i32, [_vp, _vp, _i64, _i32, _i32] + [_vp] * 6 + [_i64, _vp, _i32, _i32, _f32, _i32, _i64, _f32, _i32, _f32, _vp, _vp, _vp]),
     "dh_mvs_check": (_i32, [_vp, _i64, _i32, _i32] + [_vp] * 5 + [_i32, _f32, _vp, _vp]),
+    "dh_tsdf_integrate": (_i32, [_vp, _i64] + [_vp] * 5 + [_i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "dh_ssim_sums": (_i32, []),
     "dh_ssim_workspace": (_i64, [_i64, _i32, _i32]),
     "dh_ssim": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, ctypes.POINTER(_i32), _i32, ctypes.c_uint64, _vp, _vp, _vp, _vp]),

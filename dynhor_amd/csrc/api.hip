@@ -1185,4 +1185,15 @@ int dh_mvs_check(const float* depth, int64_t n_frames, int H, int W, const float
     return launch_mvs_check(depth, (int)n_frames, H, W, R, T, K, Kinv, nbr, n_nbr, depth_rel, count, static_cast<hipStream_t>(stream));
 }
 
+int dh_tsdf_integrate(const float* pts, int64_t n, const float* depth, const uint8_t* weight, const float* R, const float* T, const float* K,
+                      int64_t n_frames, int H, int W, float trunc, int64_t* num, int32_t* den, int32_t* obs, void* stream) {
+    if (n < 0 || n_frames < 0 || H < 1 || W < 1 || !(trunc > 0.f) || !std::isfinite(trunc)) return DH_ERR_BAD_ARG;
+    if (H > (1 << 24) || W > (1 << 24) || n >= ((int64_t)1 << 31) * 256) return DH_ERR_UNSUPPORTED;
+    if (n_frames > ((int64_t)1 << 31) - 1 || n_frames > (((int64_t)1 << 58) / H) / W) return DH_ERR_UNSUPPORTED;
+    if (n == 0 || n_frames == 0) return DH_OK;
+    if (!pts || !depth || !weight || !R || !T || !K || !num || !den || !obs) return DH_ERR_BAD_ARG;
+    return launch_tsdf_integrate(pts, n, depth, weight, R, T, K, (int)n_frames, H, W, trunc, num, den, obs,
+                                 static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -337,4 +337,9 @@ int launch_mvs_sweep(const uint8_t* gray, const uint8_t* valid, int n_frames, in
 int launch_mvs_check(const float* depth, int n_frames, int H, int W, const float* R, const float* T, const float* K, const float* Kinv,
                      const int32_t* nbr, int n_nbr, float depth_rel, uint8_t* count, hipStream_t st);
 
+// depth fusion (tsdf.hip): the weighted truncated signed distance of every point to the depth maps of a chunk of frames, in integer sums
+int launch_tsdf_integrate(const float* pts, int64_t n, const float* depth, const uint8_t* weight, const float* R, const float* T,
+                          const float* K, int n_frames, int H, int W, float trunc, int64_t* num, int32_t* den, int32_t* obs,
+                          hipStream_t st);
+
 }  // namespace dh

@@ -23,6 +23,9 @@
     python -m dynhor_amd.run --config_path X.yaml --mode match_frames --match_offsets 1,2,5   # correspondence_infos from the frames
     python -m dynhor_amd.run --config_path X.yaml --mode match_frames --is_continue --match_guide mesh   # guided by the reconstruction
     python -m dynhor_amd.run --config_path X.yaml --mode mvs_depth --vis_mesh hull.ply   # depth and normal maps by plane-sweep stereo
+    python -m dynhor_amd.run --config_path X.yaml --mode fuse_depth   # <exp>/fuse/<iter>/fused.ply: the newest mvs_depth maps fused on the hull's grid
+    python -m dynhor_amd.run --config_path X.yaml --mode fuse_depth --mvs_dir exps/<seq>/<exp>/mvs/00000000 --fuse_resolution 256 --fuse_trunc_cells 3
+    python -m dynhor_amd.run --config_path X.yaml --mode mvs_depth --vis_mesh exps/<seq>/<exp>/fuse/00000000/fused.ply   # the fused mesh as the next guide
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode render_views --is_continue   # every frame sphere-traced: png, normal, depth, PSNR, IoU
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode render_views --is_continue --views orbit:36 --view_level 2
     python -m dynhor_amd.run --config_path configs/synthetic.yaml --mode evaluate_views --is_continue   # masked SSIM, PSNR, L1 of the held-out frames
@@ -39,7 +42,7 @@ import sys
 
 
 MODES = ("train", "validate_image", "validate_mesh", "evaluate_mesh", "visualize_mesh", "refine_poses", "export_poses", "init_poses",
-         "init_sdf", "render_views", "match_frames", "evaluate_views", "visual_hull", "mvs_depth")
+         "init_sdf", "render_views", "match_frames", "evaluate_views", "visual_hull", "mvs_depth", "fuse_depth")
 
 
 def mode_arg(value: str) -> str:
@@ -158,6 +161,14 @@ def build_parser():
                          "mvs.range, else 0.04)")
     ap.add_argument("--mvs_step_px", type=int, default=None,
                     help="mvs_depth: sweep the pixels of a grid of this step (default: the config's mvs.step_px, else 1)")
+    # fuse_depth only (defaults: the config's optional depth_fuse: block, else depth_fuse.DEPTH_FUSE_DEFAULTS -- first settings, not tuned;
+    # the hull pass takes the config's visual_hull: block)
+    ap.add_argument("--mvs_dir", type=str, default=None,
+                    help="fuse_depth: the folder mvs_depth wrote (default: the newest <exp>/mvs/*/)")
+    ap.add_argument("--fuse_resolution", type=int, default=None,
+                    help="fuse_depth: grid points per axis, at most 512 (default: the config's depth_fuse.resolution, else 128)")
+    ap.add_argument("--fuse_trunc_cells", type=float, default=None,
+                    help="fuse_depth: the truncation distance in cells of the grid (default: the config's depth_fuse.trunc_cells, else 4)")
     return ap
 
 
@@ -251,6 +262,14 @@ def main():
         if runner.rank == 0:
             import json
             print(json.dumps({k: v for k, v in res.items() if k != "per_frame"}), flush=True)
+    elif args.mode == "fuse_depth":
+        res = runner.fuse_depth(mvs_dir=args.mvs_dir, resolution=args.fuse_resolution, trunc_cells=args.fuse_trunc_cells)
+        runner.close()
+        if runner.rank == 0:
+            import json
+            res["silhouette"] = {k: v for k, v in res["silhouette"].items() if k != "frames"}
+            res["stats"] = {k: v for k, v in res["stats"].items() if k != "pixels"}
+            print(json.dumps({k: v for k, v in res.items() if k not in ("residual_median", "residual_count")}), flush=True)
     elif args.mode == "render_views" or args.mode.startswith("interpolate_"):
         if args.mode == "render_views":
             views, level, method = args.views, args.view_level, args.view_method

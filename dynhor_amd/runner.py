@@ -232,6 +232,8 @@ class Runner:
         self.last_match_dir = None       # match_frames: the correspondences directory it wrote
         self.last_eval_dir = None        # evaluate_views: the image_eval/<iter> directory it wrote
         self.last_hull = None            # visual_hull: (verts, faces) of the hull it meshed
+        self.last_mvs_dir = None         # mvs_depth: the mvs/<iter> directory it wrote
+        self.last_fuse_dir = None        # fuse_depth: the fuse/<iter> directory it wrote
         if is_continue:
             ck_dir = os.path.join(self.base_exp_dir, "checkpoints")
             ck = sorted(f for f in os.listdir(ck_dir) if f.endswith(".pth")) if os.path.isdir(ck_dir) else []
@@ -1657,6 +1659,87 @@ class Runner:
                 self._board.add_scalar("hull/iou_mean", float(sil["iou_mean"]), self.iter_step)
             self._board.add_scalar("hull/volume", float(stats["volume"]), self.iter_step)
             self._board.add_scalar("hull/sole_carved_max", float(stats["sole_carved"]["share_max"]), self.iter_step)
+            self._board.flush()
+        return res
+
+    @torch.no_grad()
+    def fuse_depth(self, mvs_dir=None, save=True, **overrides):
+        """The depth maps of mvs_depth fused into a mesh (dynhor_amd/depth_fuse.py): a truncated signed distance field on the visual
+        hull's grid with the hull as a weak prior, at the dataset's current poses -- no checkpoint, no template.  mvs_dir: the folder
+        mvs_depth wrote (None: the one this runner wrote last, else the newest <exp>/mvs/*/; none: an error that names --mode
+        mvs_depth).  It reads depth/<stem>.npy (inf: no depth; a frame without a file contributes nothing; a map of another shape than
+        the frames' raises), monocular_normal/<stem>.png (128 in all three channels: no normal) and settings.step_px of mvs.json.  It
+        uses the frames that have depth files: train.holdout does not apply (as for the hull).  overrides: any key of the config's
+        optional depth_fuse: block (depth_fuse.DEPTH_FUSE_DEFAULTS: first settings, not tuned); the hull pass takes the config's
+        visual_hull: block.  Rank 0 writes <exp>/fuse/<iter:08d>/fused.ply and fuse.json (settings, stats, mvs_dir, step_px, silhouette:
+        mesh_vis.silhouette_summary of the mesh drawn over the frames, residual_median per frame and residual_worst: the frames that
+        disagree most with the fusion of all, seconds per phase) and logs fuse/volume, fuse/carved_cells and fuse/residual_median to
+        <exp>/board.  Returns the dict of fuse.json plus dir (single process: run it on one rank)."""
+        import time
+        from . import depth_fuse
+        from .mesh_vis import overlay_frames, silhouette_summary
+        if self.world > 1:
+            raise ValueError("fuse_depth runs on one rank")
+        fz = depth_fuse.merge_settings(self.conf.get("depth_fuse"), **overrides)
+        hc = self._visual_hull_conf()
+        if mvs_dir is None:
+            mvs_dir = self.last_mvs_dir
+        if mvs_dir is None:
+            root = os.path.join(self.base_exp_dir, "mvs")
+            runs = sorted(d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d, "depth"))) if os.path.isdir(root) else []
+            if not runs:
+                raise ValueError(f"fuse_depth: no depth maps under {root}: run --mode mvs_depth first, or give --mvs_dir")
+            mvs_dir = os.path.join(root, runs[-1])
+        if not os.path.isdir(os.path.join(str(mvs_dir), "depth")):
+            raise ValueError(f"fuse_depth: {mvs_dir} holds no depth/ folder: run --mode mvs_depth first, or give its folder as --mvs_dir")
+        mvs_dir = str(mvs_dir)
+        ds = self.dataset
+        seconds = {}
+        t0 = time.perf_counter()
+        names = schedules.frame_names(ds.n_images, ds.stems)
+        stems = ds.stems if ds.stems is not None else ["%04d" % f for f in range(ds.n_images)]
+        step_px = 1
+        if os.path.exists(os.path.join(mvs_dir, "mvs.json")):
+            with open(os.path.join(mvs_dir, "mvs.json")) as f:
+                step_px = int((json.load(f).get("settings") or {}).get("step_px", 1))
+        depth, normal, present = depth_fuse.read_maps(mvs_dir, stems, ds.H, ds.W)
+        if not any(present):
+            raise ValueError(f"fuse_depth: {mvs_dir}/depth holds no map of this sequence's frames: run --mode mvs_depth first")
+        depth = depth.to(self.device)
+        weight = depth_fuse.map_weights(depth, normal.to(self.device), ds.Kinv, fz["weight"], fz["floor_weight"])
+        del normal
+        seconds["read"] = time.perf_counter() - t0
+        kept = {}
+        verts, faces, stats = depth_fuse.fused_mesh(ds, depth, weight, step_px=step_px, hull=hc, timer=seconds, keep=kept, **fz)
+        t0 = time.perf_counter()
+        d_s, w_s, K_s = depth_fuse._step_maps(depth, weight, ds.K, step_px)
+        rs = depth_fuse.frame_residuals(kept["field"], kept["lo"], kept["hi"], kept["trunc"], d_s, w_s, ds.R, ds.T, K_s, names)
+        torch.cuda.synchronize(self.device)
+        seconds["residuals"] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        sil = silhouette_summary(overlay_frames(verts, faces, ds, frame_chunk=fz["frame_chunk"]).cpu(), names)
+        seconds["silhouette"] = time.perf_counter() - t0
+        have = [m for m in rs["median"] if m is not None]
+        res = {"iter": self.iter_step, "settings": fz, "hull_settings": hc, "stats": stats, "mvs_dir": mvs_dir, "step_px": step_px,
+               "frames_with_depth": int(sum(present)), "silhouette": sil, "residual_median": rs["median"], "residual_count": rs["count"],
+               "residual_worst": rs["worst"], "residual_median_all": float(np.median(have)) if have else None, "seconds": seconds}
+        if save and self.rank == 0:
+            from .mesh import write_ply
+            d = os.path.join(self.base_exp_dir, "fuse", f"{self.iter_step:08d}")
+            os.makedirs(d, exist_ok=True)
+            res["mesh"] = os.path.join(d, "fused.ply")
+            write_ply(res["mesh"], verts, faces)
+            with open(os.path.join(d, "fuse.json"), "w") as f:
+                json.dump(res, f, indent=1)
+            res["dir"] = d
+            self.last_fuse_dir = d
+            if self._board is None:
+                from .tb_events import make_writer
+                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+            self._board.add_scalar("fuse/volume", float(stats["volume"]), self.iter_step)
+            self._board.add_scalar("fuse/carved_cells", float(stats["carved_cells"]), self.iter_step)
+            if res["residual_median_all"] is not None:
+                self._board.add_scalar("fuse/residual_median", float(res["residual_median_all"]), self.iter_step)
             self._board.flush()
         return res
 

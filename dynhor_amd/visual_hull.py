@@ -219,30 +219,60 @@ def grid_points(lo, hi, N: int, device):
 BRICK = 4
 
 
-def grid_field(dataset, lo, hi, N: int, timer=None, **field_settings):
-    """hull_field on the N^3 grid of grid_points(lo, hi, N), returned in grid order: (h [N,N,N], topk [N^3,m], arg [N^3], seen [N^3]).
-    The points go to the kernel in bricks of BRICK^3 (a wave's 64 lanes hold one 4 x 4 x 4 brick, whose projections cover a compact
-    patch of pixels; in plain grid order a wave holds a line of 64 points along z): 3.5x faster at 128^3 and 7.6x at 256^3 on an
-    MI355X (scripts/bench_visual_hull.py).  A grid whose N is no multiple of BRICK is padded by repeating its last plane; the padding
-    is cut off again.  Every point's result is its own, so the order changes no value."""
-    dev = dataset.label.device
-    ax = [torch.linspace(float(lo[a]), float(hi[a]), N, device=dev) for a in range(3)]
+def brick_points(lo, hi, N: int, device):
+    """(points f32 [Np^3,3], grid_order): the points of grid_points(lo, hi, N) in bricks of BRICK^3 -- 64 consecutive points are one
+    4 x 4 x 4 brick --, and the function that puts a per-point result [Np^3, ...] back into grid order [N^3, ...].  A grid whose N is no
+    multiple of BRICK is padded to Np by repeating its last plane; grid_order cuts the padding off again."""
+    ax = [torch.linspace(float(lo[a]), float(hi[a]), N, device=device) for a in range(3)]
     nb = (N + BRICK - 1) // BRICK
     Np = nb * BRICK
     if Np != N:
         ax = [torch.cat([x, x[-1:].expand(Np - N)]) for x in ax]
     pts = torch.stack(torch.meshgrid(ax[0], ax[1], ax[2], indexing="ij"), dim=-1)
     pts = pts.view(nb, BRICK, nb, BRICK, nb, BRICK, 3).permute(0, 2, 4, 1, 3, 5, 6).reshape(-1, 3).contiguous()
-    out = hull_field(pts, dataset, timer=timer, **field_settings)
-    del pts
 
     def grid_order(t):
         tail = tuple(t.shape[1:])
         t = t.view(nb, nb, nb, BRICK, BRICK, BRICK, *tail).permute(0, 3, 1, 4, 2, 5, *range(6, 6 + len(tail)))
         return t.reshape(Np, Np, Np, *tail)[:N, :N, :N].reshape(N * N * N, *tail).contiguous()
 
+    return pts, grid_order
+
+
+def grid_field(dataset, lo, hi, N: int, timer=None, **field_settings):
+    """hull_field on the N^3 grid of grid_points(lo, hi, N), returned in grid order: (h [N,N,N], topk [N^3,m], arg [N^3], seen [N^3]).
+    The points go to the kernel in bricks of BRICK^3 (``brick_points``: a wave's 64 lanes hold one 4 x 4 x 4 brick, whose projections
+    cover a compact patch of pixels; in plain grid order a wave holds a line of 64 points along z): 3.5x faster at 128^3 and 7.6x at
+    256^3 on an MI355X (scripts/bench_visual_hull.py).  Every point's result is its own, so the order changes no value."""
+    pts, grid_order = brick_points(lo, hi, N, dataset.label.device)
+    out = hull_field(pts, dataset, timer=timer, **field_settings)
+    del pts
     h, topk, arg, seen = (grid_order(t) for t in out)
     return h.view(N, N, N), topk, arg, seen
+
+
+def _touches(inside):
+    """Whether an inside cell lies on the outer layer of the grid."""
+    return bool(inside[0].any() | inside[-1].any() | inside[:, 0].any() | inside[:, -1].any() | inside[:, :, 0].any()
+                | inside[:, :, -1].any())
+
+
+def hull_box(dataset, Nc: int, **field_settings):
+    """(lo, hi, touches): the cube the fine grid covers, from a coarse pass at Nc^3 over [-1,1]^3: the coarse hull's box padded by two
+    coarse cells, made a cube, moved and cut to lie inside [-1,1]^3; touches: an inside cell on the outer layer of the coarse grid.
+    An empty coarse hull raises ValueError."""
+    inside = grid_field(dataset, [-1.0] * 3, [1.0] * 3, Nc, **field_settings)[0] <= 0
+    if not bool(inside.any()):
+        raise ValueError("visual_hull: the coarse hull over [-1,1]^3 is empty: no grid point lies inside the masks of enough frames "
+                         f"at these poses ({_pose_note(dataset)}); check the poses, their scale and min_seen / min_carve_votes")
+    touches = _touches(inside)
+    hc = 2.0 / (Nc - 1)
+    idx = inside.nonzero()
+    lo = -1.0 + (idx.min(dim=0).values.double() - 2) * hc
+    hi = -1.0 + (idx.max(dim=0).values.double() + 2) * hc
+    side = min(float((hi - lo).max()), 2.0)
+    centre = ((lo + hi) * 0.5).clamp(-1.0 + side / 2, 1.0 - side / 2)
+    return (centre - side / 2).tolist(), (centre + side / 2).tolist(), touches
 
 
 def sole_carved(topk, arg, seen, n_frames: int, min_seen: float, names=None) -> dict:
@@ -288,21 +318,7 @@ def visual_hull(dataset, timer=None, **settings):
     fc["signed_maps"] = {} if keep else None
     t_start = time.perf_counter()
     if c["bound"] == "auto":
-        Nc = c["coarse_resolution"]
-        inside = grid_field(dataset, [-1.0] * 3, [1.0] * 3, Nc, **fc)[0] <= 0
-        if not bool(inside.any()):
-            raise ValueError("visual_hull: the coarse hull over [-1,1]^3 is empty: no grid point lies inside the masks of enough frames "
-                             f"at these poses ({_pose_note(dataset)}); check the poses, their scale and min_seen / min_carve_votes")
-        touches = bool(inside[0].any() | inside[-1].any() | inside[:, 0].any() | inside[:, -1].any() | inside[:, :, 0].any()
-                       | inside[:, :, -1].any())
-        hc = 2.0 / (Nc - 1)
-        idx = inside.nonzero()
-        lo = -1.0 + (idx.min(dim=0).values.double() - 2) * hc
-        hi = -1.0 + (idx.max(dim=0).values.double() + 2) * hc
-        side = min(float((hi - lo).max()), 2.0)
-        centre = ((lo + hi) * 0.5).clamp(-1.0 + side / 2, 1.0 - side / 2)
-        lo, hi = (centre - side / 2).tolist(), (centre + side / 2).tolist()
-        del inside
+        lo, hi, touches = hull_box(dataset, c["coarse_resolution"], **fc)
         if timer is not None:
             torch.cuda.synchronize(dev)
             timer["coarse"] = time.perf_counter() - t_start
@@ -317,8 +333,7 @@ def visual_hull(dataset, timer=None, **settings):
     if n_inside == 0:
         raise ValueError(f"visual_hull: the hull is empty on the {N}^3 grid over {lo} .. {hi} ({_pose_note(dataset)})")
     if c["bound"] != "auto":
-        touches = bool(inside[0].any() | inside[-1].any() | inside[:, 0].any() | inside[:, -1].any() | inside[:, :, 0].any()
-                       | inside[:, :, -1].any())
+        touches = _touches(inside)
     sc = sole_carved(topk, arg, seen, F, c["min_seen"], frame_names(F, dataset.stems))
     del topk, arg, seen
     fc["signed_maps"] = None

@@ -975,6 +975,26 @@ int dh_mvs_sweep(const uint8_t* gray, const uint8_t* valid, int64_t n_frames, in
 int dh_mvs_check(const float* depth, int64_t n_frames, int H, int W, const float* R, const float* T, const float* K, const float* Kinv,
                  const int32_t* nbr, int n_nbr, float depth_rel, uint8_t* count, void* stream);
 
+/* ---- depth fusion (dynhor_amd/depth_fuse.py: the depth maps of all frames integrated into a truncated signed distance field; csrc/tsdf.hip) ----
+ * dh_tsdf_integrate: pts f32 [n,3]; depth f32 [n_frames,H,W], camera z; weight u8 [n_frames,H,W]; R [n_frames,9] row-major,
+ * T [n_frames,3], K [9] = the K of the depth image, as for dh_mesh_mask_votes; trunc > 0 in object units.  State per point, updated in
+ * place and carried from call to call (the caller starts all three at 0): num int64 [n], den int32 [n], obs int32 [n].
+ * Per point p and frame f, in fp32:
+ *   1. c = R_f p + T_f and (u, w) in dh_mesh_mask_votes' fma order (mk_project); skipped unless c_2 > 1e-3.
+ *   2. The nearest pixel, as dh_mvs_check: xf = floor(u + 0.5), yf = floor(w + 0.5); skipped unless 0 <= xf <= W - 1 and
+ *      0 <= yf <= H - 1, compared as floats before any conversion (a NaN or a huge value skips).
+ *   3. zd = depth[f, yf, xf], wt = weight[f, yf, xf]; skipped when wt == 0, when zd is not finite, or when zd <= 1e-3.
+ *   4. d = zd - c_2; skipped when d < -trunc (the point is hidden behind the surface).
+ *   5. t = min(d / trunc, 1) with one division; q = rint(t * 65536) (round to nearest even) as int32, in [-65536, 65536].
+ *   6. num += (int64) wt * q; den += wt; obs += 1.
+ * The sums are integers, so the state after any set of frames is the same bits for every order of the frames and every split of them
+ * into calls.  |num| <= 255 * 2^16 * frames; den <= 255 * frames fits in int32 up to 8.4e6 frames (the caller's bound: it is not
+ * checked).  No atomics; the library allocates nothing and keeps no state.  Runs on `stream` and does not wait for it.
+ * n == 0 or n_frames == 0: no-op.  DH_ERR_BAD_ARG: negative count, H or W < 1, trunc not finite and positive, a null pointer with
+ * n > 0 and n_frames > 0.  DH_ERR_UNSUPPORTED: H or W > 2^24, n >= 2^31 * 256, n_frames >= 2^31, n_frames H W > 2^58. */
+int dh_tsdf_integrate(const float* pts, int64_t n, const float* depth, const uint8_t* weight, const float* R, const float* T, const float* K,
+                      int64_t n_frames, int H, int W, float trunc, int64_t* num, int32_t* den, int32_t* obs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
