@@ -31,8 +31,8 @@ import torch
 
 from . import _lib
 from . import visual_hull as vh
-from .mesh_clean import _device_tensor
-from .mesh_color import _cams
+from ._args import check_cams, device_tensor, lap
+from .settings import int_in, is_int, is_num, merge
 
 # First settings, not tuned (as mvs.DEFAULTS).  resolution: grid points per axis (at most visual_hull.MAX_RESOLUTION); trunc_cells: the
 # truncation distance in cells of the grid; prior_weight: the weight of the hull's field, 255 = one frame at full weight (> 0:
@@ -47,38 +47,34 @@ N_WORST = 5
 
 def check_settings(c: dict):
     """ValueError unless c is a full, sensible dict over DEPTH_FUSE_DEFAULTS; the message names the unknown, missing or bad key."""
-    unknown = sorted(set(c) - set(DEPTH_FUSE_DEFAULTS))
-    if unknown:
-        raise ValueError(f"depth_fuse: unknown setting(s) {unknown}; known: {sorted(DEPTH_FUSE_DEFAULTS)}")
+    merge("depth_fuse", DEPTH_FUSE_DEFAULTS, None, c, check_overrides=True)
     missing = sorted(set(DEPTH_FUSE_DEFAULTS) - set(c))
     if missing:
         raise ValueError(f"depth_fuse: missing setting(s) {missing}")
-    if not vh._is_int(c["resolution"]) or not 2 <= c["resolution"] <= vh.MAX_RESOLUTION:
-        raise ValueError(f"depth_fuse resolution must be an integer in [2, {vh.MAX_RESOLUTION}], got {c['resolution']!r}")
-    if not vh._is_num(c["trunc_cells"]) or not 0 < c["trunc_cells"] <= 64:
+    int_in("depth_fuse", "resolution", c["resolution"], 2, vh.MAX_RESOLUTION)
+    if not is_num(c["trunc_cells"]) or not 0 < c["trunc_cells"] <= 64:
         raise ValueError(f"depth_fuse trunc_cells must be a number in (0, 64], got {c['trunc_cells']!r}")
-    if not vh._is_num(c["prior_weight"]) or not 0 < c["prior_weight"] <= 1e9:
+    if not is_num(c["prior_weight"]) or not 0 < c["prior_weight"] <= 1e9:
         raise ValueError("depth_fuse prior_weight must be a number in (0, 1e9] (without the hull as a prior the field grows a back face "
                          f"at -trunc), got {c['prior_weight']!r}")
     if c["weight"] not in ("cos", "uniform"):
         raise ValueError(f"depth_fuse weight must be 'cos' or 'uniform', got {c['weight']!r}")
-    if not vh._is_int(c["floor_weight"]) or not 1 <= c["floor_weight"] <= 255:
-        raise ValueError(f"depth_fuse floor_weight must be an integer in [1, 255], got {c['floor_weight']!r}")
+    int_in("depth_fuse", "floor_weight", c["floor_weight"], 1, 255)
     for k in ("frame_chunk", "point_chunk"):
-        if not vh._is_int(c[k]) or c[k] < 1:
+        if not is_int(c[k]) or c[k] < 1:
             raise ValueError(f"depth_fuse {k} must be a positive integer, got {c[k]!r}")
 
 
-def merge_settings(block=None, **overrides) -> dict:
-    """DEPTH_FUSE_DEFAULTS, then the YAML's optional depth_fuse: block, then the overrides that are not None; checked."""
-    c = dict(DEPTH_FUSE_DEFAULTS)
-    for src, where in ((block or {}, " in the config"), ({k: v for k, v in overrides.items() if v is not None}, "")):
-        unknown = sorted(set(src) - set(DEPTH_FUSE_DEFAULTS))
-        if unknown:
-            raise ValueError(f"depth_fuse: unknown setting(s) {unknown}{where}; known: {sorted(DEPTH_FUSE_DEFAULTS)}")
-        c.update(src)
+def fuse_settings(block=None, **overrides) -> dict:
+    """DEPTH_FUSE_DEFAULTS, then the YAML's optional depth_fuse: block, then the overrides that are not None; checked (in the order
+    of visual_hull.hull_settings)."""
+    c = merge("depth_fuse", DEPTH_FUSE_DEFAULTS, block, check_block=True)
+    c = merge("depth_fuse", DEPTH_FUSE_DEFAULTS, c, {k: v for k, v in overrides.items() if v is not None}, check_overrides=True)
     check_settings(c)
     return c
+
+
+merge_settings = fuse_settings           # the name the config tests and earlier callers know
 
 
 def integrate(points, depth, weight, R, T, K, trunc, num, den, obs):
@@ -89,19 +85,19 @@ def integrate(points, depth, weight, R, T, K, trunc, num, den, obs):
     for name, t in (("num", num), ("den", den), ("obs", obs)):
         if torch.is_tensor(t) and not t.is_contiguous():
             raise ValueError(f"{fn}: {name} is updated in place and must be contiguous")
-    points = _device_tensor(fn, "points", points, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[n,3]")
+    points = device_tensor(fn, "points", points, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[n,3]")
     n = points.shape[0]
-    depth = _device_tensor(fn, "depth", depth, torch.float32, lambda s: len(s) == 3, "[F,H,W]")
+    depth = device_tensor(fn, "depth", depth, torch.float32, lambda s: len(s) == 3, "[F,H,W]")
     F, H, W = depth.shape
-    weight = _device_tensor(fn, "weight", weight, torch.uint8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
-    R, T, K = _cams(fn, F, R, T, K, points.device)
+    weight = device_tensor(fn, "weight", weight, torch.uint8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
+    R, T, K = check_cams(fn, F, R, T, K, points.device)
     for name, t, dtype in (("num", num, torch.int64), ("den", den, torch.int32), ("obs", obs, torch.int32)):
-        _device_tensor(fn, name, t, dtype, lambda s: s == (n,), f"[{n}]")
+        device_tensor(fn, name, t, dtype, lambda s: s == (n,), f"[{n}]")
     if len({t.device for t in (points, depth, weight, num, den, obs)}) != 1:
         raise ValueError(f"{fn}: every tensor must be on {points.device}")
     if H < 1 or W < 1:
         raise ValueError(f"{fn}: images of at least 1 x 1 pixels, got {H}x{W}")
-    if not vh._is_num(trunc) or not trunc > 0:
+    if not is_num(trunc) or not trunc > 0:
         raise ValueError(f"{fn}: trunc must be a positive number, got {trunc!r}")
     with torch.cuda.device(points.device):
         _lib.check(_lib.lib().dh_tsdf_integrate(_lib.ptr(points), n, _lib.ptr(depth), _lib.ptr(weight), _lib.ptr(R), _lib.ptr(T), _lib.ptr(K),
@@ -227,33 +223,27 @@ def fused_field(dataset, depth, weight, /, step_px=1, hull=None, timer=None, **s
     """What fused_mesh meshes: {"field" f32 [N,N,N], "h" (the hull's field), "num", "den", "obs" [N^3], "lo", "hi", "cell", "trunc",
     "settings"}.  hull: the settings of the hull pass (visual_hull.VISUAL_HULL_DEFAULTS' keys; its resolution is not used)."""
     import time
-    c = merge_settings(None, **settings)
-    hc = vh.merge_settings(hull)
+    c = fuse_settings(None, **settings)
+    hc = vh.hull_settings(hull)
     dev = dataset.label.device
     N = c["resolution"]
     fc = {k: hc[k] for k in ("min_carve_votes", "min_seen", "outside_value", "band_px", "frame_chunk", "point_chunk")}
     fc["signed_maps"] = {} if hc["bound"] == "auto" and 4 * dataset.label.numel() <= vh.SIGNED_MAP_CACHE_BYTES else None
-
-    def lap(key, t0):
-        if timer is not None:
-            torch.cuda.synchronize(dev)
-            timer[key] = time.perf_counter() - t0
-        return time.perf_counter()
 
     t0 = time.perf_counter()
     if hc["bound"] == "auto":
         lo, hi, _ = vh.hull_box(dataset, hc["coarse_resolution"], **fc)
     else:
         lo, hi = [-float(hc["bound"])] * 3, [float(hc["bound"])] * 3
-    t0 = lap("box", t0)
+    t0 = lap(timer, "box", t0, dev)
     h = vh.grid_field(dataset, lo, hi, N, **fc)[0]
     fc["signed_maps"] = None
-    t0 = lap("hull", t0)
+    t0 = lap(timer, "hull", t0, dev)
     cell = (hi[0] - lo[0]) / (N - 1)
     trunc = c["trunc_cells"] * cell
     num, den, obs = fuse_field(dataset, depth, weight, lo, hi, N, step_px=step_px, trunc=trunc, frame_chunk=c["frame_chunk"],
                                point_chunk=c["point_chunk"])
-    lap("integrate", t0)
+    lap(timer, "integrate", t0, dev)
     return {"field": field_from_state(num, den, h, trunc, c["prior_weight"]), "h": h, "num": num, "den": den, "obs": obs,
             "lo": [float(v) for v in lo], "hi": [float(v) for v in hi], "cell": float(cell), "trunc": float(trunc), "settings": c}
 

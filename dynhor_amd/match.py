@@ -39,8 +39,9 @@ import time
 import torch
 
 from . import _lib
-from .mesh_clean import _device_tensor, _faces
-from .mesh_color import _cams, _verts, raster_depth, usable_map
+from ._args import check_cams, check_faces, check_verts, device_tensor
+from .mesh_color import raster_depth, usable_map
+from .settings import merge
 from .pose_photo import blur_frames
 
 GUIDES = ("none", "mesh")
@@ -64,8 +65,8 @@ def default_min_va(patch: int) -> int:
 
 def match_gray(img, a_min: float):
     """(gray, valid) u8 [F,H,W] of img f32 [F,H,W,4] = blur_frames' output (dh_match_gray)."""
-    img = _device_tensor("match_gray", "img", img, torch.float32, lambda s: len(s) == 4 and s[3] == 4 and s[1] > 0 and s[2] > 0,
-                         "[F,H,W,4]")
+    img = device_tensor("match_gray", "img", img, torch.float32, lambda s: len(s) == 4 and s[3] == 4 and s[1] > 0 and s[2] > 0,
+                        "[F,H,W,4]")
     F, H, W = img.shape[:3]
     gray = torch.empty(F, H, W, dtype=torch.uint8, device=img.device)
     valid = torch.empty_like(gray)
@@ -96,10 +97,10 @@ def search(gray, valid, queries, patch: int = DEFAULTS["patch"], rng: int = 16, 
 
 def _search(fn, words, gray, valid, queries, patch, rng, excl, min_va):
     """search (words 6, dh_match_search) and search_warp (words 10, dh_match_search_warp)."""
-    gray = _device_tensor(fn, "gray", gray, torch.uint8, lambda s: len(s) == 3 and s[1] > 0 and s[2] > 0, "[F,H,W]")
+    gray = device_tensor(fn, "gray", gray, torch.uint8, lambda s: len(s) == 3 and s[1] > 0 and s[2] > 0, "[F,H,W]")
     F, H, W = gray.shape
-    valid = _device_tensor(fn, "valid", valid, torch.uint8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
-    queries = _device_tensor(fn, "queries", queries, torch.int32, lambda s: len(s) == 2 and s[1] == words, f"[n,{words}]")
+    valid = device_tensor(fn, "valid", valid, torch.uint8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
+    queries = device_tensor(fn, "queries", queries, torch.int32, lambda s: len(s) == 2 and s[1] == words, f"[n,{words}]")
     if valid.device != gray.device or queries.device != gray.device:
         raise ValueError(f"{fn}: every tensor must be on {gray.device}")
     min_va = default_min_va(patch) if min_va is None else int(min_va)
@@ -362,11 +363,7 @@ def _match_pairs(forward, backward, queries, zncc_min, peak_margin, peak_full, f
 
 def check_settings(settings: dict) -> dict:
     """DEFAULTS overlaid with `settings`; an unknown key or a value out of range raises ValueError.  range and min_va are resolved."""
-    unknown = sorted(set(settings) - set(DEFAULTS))
-    if unknown:
-        raise ValueError(f"match: unknown setting(s) {unknown}; known: {sorted(DEFAULTS)}")
-    s = dict(DEFAULTS)
-    s.update({k: v for k, v in settings.items() if v is not None})
+    s = merge("match", DEFAULTS, None, settings, check_overrides=True)
     if s["guide"] not in GUIDES:
         raise ValueError(f"match: guide must be one of {GUIDES}, got {s['guide']!r}")
     if isinstance(s["offsets"], str):
@@ -417,8 +414,8 @@ def match_frames(dataset, verts=None, faces=None, **settings):
     else:
         if verts is None or faces is None:
             raise ValueError("match_frames: guide 'mesh' needs a mesh (verts, faces)")
-        verts, faces = _verts("match_frames", verts), _faces("match_frames", faces)
-        R, T, K = _cams("match_frames", F, dataset.R, dataset.T, dataset.K, dev)
+        verts, faces = check_verts("match_frames", verts), check_faces("match_frames", faces)
+        R, T, K = check_cams("match_frames", F, dataset.R, dataset.T, dataset.K, dev)
         zbuf = raster_depth(verts, faces, R, T, K, H, W)
         pr = torch.tensor(pairs, dtype=torch.int64, device=dev).reshape(-1, 2)
         fi, fj, p = pr[pid, 0], pr[pid, 1], pix[rows, 1:3].long()

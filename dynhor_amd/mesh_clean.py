@@ -19,22 +19,15 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._args import check_faces, check_poses, device_tensor
 
 MODES = ("none", "mask", "largest", "mask+largest")
-
-
-def _device_tensor(fn, name, t, dtype, shape_ok, shape_txt):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise _lib.DynhorHipError(f"{fn}: {name} must be a device tensor (the HIP kernel has no CPU fallback)")
-    if t.dtype != dtype or not shape_ok(tuple(t.shape)):
-        raise ValueError(f"{fn}: {name} must be {dtype} {shape_txt}, got {t.dtype} {tuple(t.shape)}")
-    return t.contiguous()
 
 
 def dilate_labels(label: torch.Tensor, radius: int) -> torch.Tensor:
     """keep u8 [F,H,W] from a label map i8 [F,H,W] (1 object / 0 background / -1 hand): 1 where the square window of half-width
     `radius` (clipped to the image) holds a label != 0.  radius 0 = (label != 0)."""
-    label = _device_tensor("dilate_labels", "label", label, torch.int8, lambda s: len(s) == 3, "[F,H,W]")
+    label = device_tensor("dilate_labels", "label", label, torch.int8, lambda s: len(s) == 3, "[F,H,W]")
     if int(radius) < 0:
         raise ValueError(f"dilate_labels: radius must be >= 0, got {radius}")
     F, H, W = label.shape
@@ -47,23 +40,12 @@ def dilate_labels(label: torch.Tensor, radius: int) -> torch.Tensor:
     return keep
 
 
-def _poses(fn, keep, R, T, K):
-    keep = _device_tensor(fn, "keep", keep, torch.uint8, lambda s: len(s) == 3, "[F,H,W]")
-    F = keep.shape[0]
-    R = _device_tensor(fn, "R", R, torch.float32, lambda s: s in ((F, 3, 3), (F, 9)), f"[{F},3,3]")
-    T = _device_tensor(fn, "T", T, torch.float32, lambda s: s in ((F, 3), (F, 1, 3)), f"[{F},3]")
-    K = _device_tensor(fn, "K", K, torch.float32, lambda s: s == (3, 3), "[3,3]")
-    if len({t.device for t in (keep, R, T, K)}) != 1:
-        raise ValueError(f"{fn}: keep, R, T and K must be on one device")
-    return keep, R, T, K
-
-
 def mask_votes(verts: torch.Tensor, keep: torch.Tensor, R: torch.Tensor, T: torch.Tensor, K: torch.Tensor):
     """(bg_votes, seen), int32 [V]: for every vertex, the frames in which it projects inside the image in front of the camera (x_cam =
     R_f v + T_f, pixel round(K x_cam / z)), and of those the frames whose keep map is 0 at its pixel.  keep u8 [F,H,W]
     (dilate_labels), R [F,3,3], T [F,3], K [3,3] float32 (Dataset.R / T / K)."""
-    verts = _device_tensor("mask_votes", "verts", verts, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[V,3]")
-    keep, R, T, K = _poses("mask_votes", keep, R, T, K)
+    verts = device_tensor("mask_votes", "verts", verts, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[V,3]")
+    keep, R, T, K = check_poses("mask_votes", keep, R, T, K)
     if verts.device != keep.device:
         raise ValueError(f"mask_votes: verts on {verts.device}, keep on {keep.device}")
     F, H, W = keep.shape
@@ -78,14 +60,10 @@ def mask_votes(verts: torch.Tensor, keep: torch.Tensor, R: torch.Tensor, T: torc
     return bg, seen
 
 
-def _faces(fn, faces):
-    return _device_tensor(fn, "faces", faces, torch.int64, lambda s: len(s) == 2 and s[1] == 3, "[M,3]")
-
-
 def vertex_components(n_verts: int, faces: torch.Tensor) -> torch.Tensor:
     """labels int32 [n_verts]: the smallest vertex index of each vertex's connected component (edges: the three edges of every face;
     a vertex in no face is its own component).  Bitwise reproducible."""
-    faces = _faces("vertex_components", faces)
+    faces = check_faces("vertex_components", faces)
     n_verts = int(n_verts)
     if n_verts < 0:
         raise ValueError(f"vertex_components: n_verts must be >= 0, got {n_verts}")
@@ -106,7 +84,7 @@ def _compact(verts, faces, face_keep):
 
 def cull_by_masks(verts, faces, keep, R, T, K, min_bg_votes: int = 1):
     """Removes every vertex with at least `min_bg_votes` background votes (mask_votes) and every face that touches one, then compacts."""
-    faces = _faces("cull_by_masks", faces)
+    faces = check_faces("cull_by_masks", faces)
     if int(min_bg_votes) < 1:
         raise ValueError(f"cull_by_masks: min_bg_votes must be >= 1, got {min_bg_votes}")
     bg, _ = mask_votes(verts, keep, R, T, K)
@@ -137,8 +115,8 @@ def _count_components(n_verts, faces, labels):
 def keep_components(verts, faces, min_area_frac=None):
     """Keeps the connected component of largest total face area (ties: the smaller label), or, with min_area_frac = f, every
     component whose area is at least f x the largest; then compacts."""
-    verts = _device_tensor("keep_components", "verts", verts, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[V,3]")
-    faces = _faces("keep_components", faces)
+    verts = device_tensor("keep_components", "verts", verts, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[V,3]")
+    faces = check_faces("keep_components", faces)
     if faces.shape[0] == 0:
         return _compact(verts, faces, torch.zeros(0, dtype=torch.bool, device=faces.device))
     labels = vertex_components(verts.shape[0], faces)
@@ -168,8 +146,8 @@ def clean_mesh(verts, faces, dataset, mode: str = "mask+largest", dilate_px: int
     faces each stage removed and the number of connected components of the mesh the component stage sees."""
     if mode not in MODES:
         raise ValueError(f"clean_mesh: mode must be one of {MODES}, got {mode!r}")
-    verts = _device_tensor("clean_mesh", "verts", verts, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[V,3]")
-    faces = _faces("clean_mesh", faces)
+    verts = device_tensor("clean_mesh", "verts", verts, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[V,3]")
+    faces = check_faces("clean_mesh", faces)
     stats = {"mode": mode, "verts_in": int(verts.shape[0]), "faces_in": int(faces.shape[0])}
     v, f = verts, faces
     if mode == "none":

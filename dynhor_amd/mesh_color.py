@@ -19,53 +19,37 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
-from .mesh_clean import _device_tensor, _faces, dilate_labels
+from ._args import check_cams, check_faces, check_verts, device_tensor, same_device
+from .mesh_clean import dilate_labels
 
 MODES = ("none", "views", "network", "views+network")
 NET_CHUNK = 1 << 20
 
 
-def _verts(fn, verts):
-    return _device_tensor(fn, "verts", verts, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[V,3]")
-
-
-def _same_device(fn, device, *tensors):
-    if any(t is not None and t.device != device for t in tensors):
-        raise ValueError(f"{fn}: every tensor must be on {device}")
-
-
-def _cams(fn, F, R, T, K, device):
-    R = _device_tensor(fn, "R", R, torch.float32, lambda s: s in ((F, 3, 3), (F, 9)), f"[{F},3,3]")
-    T = _device_tensor(fn, "T", T, torch.float32, lambda s: s in ((F, 3), (F, 1, 3)), f"[{F},3]")
-    K = _device_tensor(fn, "K", K, torch.float32, lambda s: s == (3, 3), "[3,3]")
-    _same_device(fn, device, R, T, K)
-    return R, T, K
-
-
 def _normals(fn, verts, faces, normals):
     if normals is None:
         normals = vertex_normals(verts, faces)
-    return _device_tensor(fn, "normals", normals, torch.float32, lambda s: s == tuple(verts.shape), "[V,3]")
+    return device_tensor(fn, "normals", normals, torch.float32, lambda s: s == tuple(verts.shape), "[V,3]")
 
 
 def _draw_args(fn, verts, faces, zbuf, R, T, K, alpha, normals, rgb):
     """What mesh_vis.shade and mesh_texture.render_textured check alike, under the caller's name `fn`: (verts, faces, zbuf int64
     [F,H,W] with H, W > 0, R, T, K for its F frames, alpha as a float in [0, 1], normals (default vertex_normals), rgb u8 [F,H,W,3] or
     None), all on zbuf's device."""
-    verts = _verts(fn, verts)
-    faces = _faces(fn, faces)
-    zbuf = _device_tensor(fn, "zbuf", zbuf, torch.int64, lambda s: len(s) == 3, "[F,H,W]")
+    verts = check_verts(fn, verts)
+    faces = check_faces(fn, faces)
+    zbuf = device_tensor(fn, "zbuf", zbuf, torch.int64, lambda s: len(s) == 3, "[F,H,W]")
     F, H, W = zbuf.shape
     if H == 0 or W == 0:
         raise ValueError(f"{fn}: empty images {H}x{W}")
-    R, T, K = _cams(fn, F, R, T, K, zbuf.device)
+    R, T, K = check_cams(fn, F, R, T, K, zbuf.device)
     alpha = float(alpha)
     if not 0.0 <= alpha <= 1.0:
         raise ValueError(f"{fn}: alpha must lie in [0, 1], got {alpha}")
     normals = _normals(fn, verts, faces, normals)
     if rgb is not None:
-        rgb = _device_tensor(fn, "rgb", rgb, torch.uint8, lambda s: s == (F, H, W, 3), f"[{F},{H},{W},3]")
-    _same_device(fn, zbuf.device, verts, faces, normals, rgb)
+        rgb = device_tensor(fn, "rgb", rgb, torch.uint8, lambda s: s == (F, H, W, 3), f"[{F},{H},{W},3]")
+    same_device(fn, zbuf.device, verts, faces, normals, rgb)
     return verts, faces, zbuf, R, T, K, alpha, normals, rgb
 
 
@@ -82,15 +66,15 @@ def raster_depth(verts, faces, R, T, K, H: int, W: int) -> torch.Tensor:
     """zbuf int64 [F,H,W]: the uint64 keys (float_bits(camera depth) << 32) | face of the nearest face whose screen triangle covers
     each pixel centre (integer coordinates; both windings), -1 where none does.  R [F,3,3], T [F,3], K [3,3] (Dataset.R / T / K).
     zbuf >> 32 (as int32 bits) is the depth as float32; zbuf & 0xffffffff the face."""
-    verts = _verts("raster_depth", verts)
-    faces = _faces("raster_depth", faces)
+    verts = check_verts("raster_depth", verts)
+    faces = check_faces("raster_depth", faces)
     if verts.device != faces.device:
         raise ValueError(f"raster_depth: verts on {verts.device}, faces on {faces.device}")
     H, W = int(H), int(W)
     if H <= 0 or W <= 0:
         raise ValueError(f"raster_depth: empty images {H}x{W}")
     F = R.shape[0] if torch.is_tensor(R) and R.dim() >= 1 else -1
-    R, T, K = _cams("raster_depth", F, R, T, K, verts.device)
+    R, T, K = check_cams("raster_depth", F, R, T, K, verts.device)
     zbuf = torch.full((F, H, W), -1, dtype=torch.int64, device=verts.device)
     with torch.cuda.device(verts.device):
         _lib.check(_lib.lib().dh_mesh_raster_depth(_lib.ptr(verts), verts.shape[0], _lib.ptr(faces), faces.shape[0], _lib.ptr(R),
@@ -154,14 +138,14 @@ def bake_vertex_colors(verts, faces, dataset, erode_px: int = 1, min_cos: float 
     in order whatever the chunking, so the result is bitwise the same for every chunk size.
     normals: unit vertex normals (default: vertex_normals(verts, faces))."""
     fn = "bake_vertex_colors"
-    verts = _verts(fn, verts)
-    faces = _faces(fn, faces)
+    verts = check_verts(fn, verts)
+    faces = check_faces(fn, faces)
     _check_bake_args(fn, erode_px, min_cos, depth_eps, frame_chunk)
     normals = _normals(fn, verts, faces, normals)
     ds = dataset
     F, H, W = ds.n_images, ds.H, ds.W
-    R, T, K = _cams(fn, F, ds.R, ds.T, ds.K, verts.device)
-    rgb = _device_tensor(fn, "dataset.rgb", ds.rgb, torch.uint8, lambda s: s == (F, H, W, 3), f"[{F},{H},{W},3]")
+    R, T, K = check_cams(fn, F, ds.R, ds.T, ds.K, verts.device)
+    rgb = device_tensor(fn, "dataset.rgb", ds.rgb, torch.uint8, lambda s: s == (F, H, W, 3), f"[{F},{H},{W},3]")
     nv = verts.shape[0]
     acc = torch.zeros(nv, 4, dtype=torch.float32, device=verts.device)
     n_views = torch.zeros(nv, dtype=torch.int32, device=verts.device)
@@ -183,9 +167,9 @@ def network_vertex_colors(renderer, verts, normals=None):
     vertex.  Runs the renderer's family hooks (_net_forward, one sample per "ray", forward-only workspace) in chunks of at most 2^20
     points: a first pass for the gradient, a second for the colour with the direction.  Non-finite output (split_f16 range exceeded,
     or a diverged network) raises DynhorHipError."""
-    verts = _verts("network_vertex_colors", verts)
+    verts = check_verts("network_vertex_colors", verts)
     if normals is not None:
-        normals = _device_tensor("network_vertex_colors", "normals", normals, torch.float32, lambda s: s == tuple(verts.shape), "[V,3]")
+        normals = device_tensor("network_vertex_colors", "normals", normals, torch.float32, lambda s: s == tuple(verts.shape), "[V,3]")
     dev = verts.device
     packed = renderer.store.ensure_packed(renderer._arith())
     out = torch.empty(verts.shape[0], 3, dtype=torch.float32, device=dev)
@@ -216,8 +200,8 @@ def color_mesh(verts, faces, mode: str, dataset=None, renderer=None, erode_px: i
     contributing view), mean_views (mean n_views over the seen vertices; 0.0 when none is seen)."""
     if mode not in MODES:
         raise ValueError(f"color_mesh: mode must be one of {MODES}, got {mode!r}")
-    verts = _verts("color_mesh", verts)
-    faces = _faces("color_mesh", faces)
+    verts = check_verts("color_mesh", verts)
+    faces = check_faces("color_mesh", faces)
     stats = {"mode": mode, "verts_in": int(verts.shape[0])}
     if mode == "none":
         return None, stats

@@ -34,7 +34,7 @@ import math
 import torch
 
 from . import _lib
-from .mesh_clean import _device_tensor, _faces
+from ._args import check_faces, check_verts
 
 PLACEMENTS = ("mean", "quadric")
 MAX_CELLS = 1 << 20
@@ -89,12 +89,8 @@ class _Grid:
 def cell_keys(verts: torch.Tensor, cells: int):
     """(keys int64 [V], cell_size float, dims (dx, dy, dz)): the cell key i_x + dx (i_y + dy i_z) of every vertex on the grid that cuts
     the bounding box's longest axis into `cells` cells (dh_simplify_grid, dh_simplify_cells).  ValueError: a non-finite vertex."""
-    keys, g = _cell_keys("cell_keys", _verts("cell_keys", verts), int(cells))
+    keys, g = _cell_keys("cell_keys", check_verts("cell_keys", verts), int(cells))
     return keys, g.h, tuple(g.dims)
-
-
-def _verts(fn, verts):
-    return _device_tensor(fn, "verts", verts, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[V,3]")
 
 
 def _cell_keys(fn, verts, cells):
@@ -200,7 +196,7 @@ def simplify_mesh(verts, faces, cells=None, target_faces=None, regularization=1e
     not on the launch.  ValueError: non-finite vertices, face indices outside [0, V), bad options.  CPU tensors: DynhorHipError."""
     fn = "simplify_mesh"
     _check_options(fn, cells, target_faces, regularization, placement, cells_max)
-    verts, faces = _verts(fn, verts), _faces(fn, faces)
+    verts, faces = check_verts(fn, verts), check_faces(fn, faces)
     if verts.device != faces.device:
         raise ValueError(f"{fn}: verts on {verts.device}, faces on {faces.device}")
     if faces.shape[0] and (int(faces.min()) < 0 or int(faces.max()) >= verts.shape[0]):

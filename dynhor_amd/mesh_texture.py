@@ -40,9 +40,8 @@ import os
 import torch
 
 from . import _lib
-from .mesh_clean import _device_tensor, _faces
-from .mesh_color import (_cams, _check_bake_args, _draw_args, _normals, _same_device, _verts, frame_chunks, network_vertex_colors,
-                         usable_map, vertex_normals)
+from ._args import check_cams, check_faces, check_verts, device_tensor, same_device
+from .mesh_color import _check_bake_args, _draw_args, _normals, frame_chunks, network_vertex_colors, usable_map, vertex_normals
 
 MODES = ("none", "views", "views+network")
 MIN_CELL = 8
@@ -92,8 +91,8 @@ def face_atlas(n_faces: int, size: int, device=None):
 
 
 def _uv(fn, uv, nf, device):
-    uv = _device_tensor(fn, "uv", uv, torch.float32, lambda s: s == (nf, 3, 2), f"[{nf},3,2]")
-    _same_device(fn, device, uv)
+    uv = device_tensor(fn, "uv", uv, torch.float32, lambda s: s == (nf, 3, 2), f"[{nf},3,2]")
+    same_device(fn, device, uv)
     return uv
 
 
@@ -103,18 +102,18 @@ def bake_texture_sums(verts, faces, dataset, uv, owner, erode_px: int = 1, min_c
     colour, sum of weight) over the contributing frames, in frame order whatever the chunking (bitwise the same for every
     frame_chunk).  Texels no face owns keep 0."""
     fn = "bake_texture_sums"
-    verts = _verts(fn, verts)
-    faces = _faces(fn, faces)
+    verts = check_verts(fn, verts)
+    faces = check_faces(fn, faces)
     _check_bake_args(fn, erode_px, min_cos, depth_eps, frame_chunk, sharpen)
     nf, nv, dev = faces.shape[0], verts.shape[0], verts.device
     uv = _uv(fn, uv, nf, dev)
-    owner = _device_tensor(fn, "owner", owner, torch.int32, lambda s: len(s) == 2 and s[0] == s[1], "[S,S]")
+    owner = device_tensor(fn, "owner", owner, torch.int32, lambda s: len(s) == 2 and s[0] == s[1], "[S,S]")
     normals = _normals(fn, verts, faces, normals)
     ds = dataset
     F, H, W = ds.n_images, ds.H, ds.W
-    R, T, K = _cams(fn, F, ds.R, ds.T, ds.K, dev)
-    rgb = _device_tensor(fn, "dataset.rgb", ds.rgb, torch.uint8, lambda s: s == (F, H, W, 3), f"[{F},{H},{W},3]")
-    _same_device(fn, dev, faces, owner, normals, rgb)
+    R, T, K = check_cams(fn, F, ds.R, ds.T, ds.K, dev)
+    rgb = device_tensor(fn, "dataset.rgb", ds.rgb, torch.uint8, lambda s: s == (F, H, W, 3), f"[{F},{H},{W},3]")
+    same_device(fn, dev, faces, owner, normals, rgb)
     S = owner.shape[0]
     acc = torch.zeros(S, S, 4, dtype=torch.float32, device=dev)
     n_views = torch.zeros(S, S, dtype=torch.int32, device=dev)
@@ -161,8 +160,8 @@ def bake_texture(verts, faces, dataset, size: int = 1024, mode: str = "views", r
     stats = {"mode": mode}
     if mode == "none":
         return None, None, None, stats
-    verts = _verts("bake_texture", verts)
-    faces = _faces("bake_texture", faces)
+    verts = check_verts("bake_texture", verts)
+    faces = check_faces("bake_texture", faces)
     if dataset is None:
         raise ValueError(f"bake_texture: mode {mode!r} needs the dataset")
     if "network" in mode and renderer is None:
@@ -201,12 +200,12 @@ def render_textured(verts, faces, zbuf, R, T, K, uv, tex, normals=None, rgb=None
     F, H, W = zbuf.shape
     dev = zbuf.device
     uv = _uv(fn, uv, faces.shape[0], dev)
-    tex = _device_tensor(fn, "tex", tex, torch.uint8, lambda s: len(s) == 3 and s[2] == 3 and s[0] > 0 and s[1] > 0, "[Sh,Sw,3]")
+    tex = device_tensor(fn, "tex", tex, torch.uint8, lambda s: len(s) == 3 and s[2] == 3 and s[0] > 0 and s[1] > 0, "[Sh,Sw,3]")
     if usable is not None:
         if rgb is None:
             raise ValueError(f"{fn}: usable needs rgb (the error sums are taken against it)")
-        usable = _device_tensor(fn, "usable", usable, torch.uint8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
-    _same_device(fn, dev, tex, usable)
+        usable = device_tensor(fn, "usable", usable, torch.uint8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
+    same_device(fn, dev, tex, usable)
     out = torch.empty(F, H, W, 3, dtype=torch.uint8, device=dev)
     sums = torch.zeros(F, 2, dtype=torch.int64, device=dev) if usable is not None else None
     opt = lambda t: _lib.ptr(t) if t is not None else ctypes.c_void_p(0)
@@ -230,13 +229,13 @@ def texture_psnr(verts, faces, dataset, uv, tex, erode_px: int = 1, frame_chunk:
     """Re-render PSNR of the textured mesh, unlit, against the dataset's frames at its current poses, over the pixels the mesh covers
     whose label is usable (object, eroded by erode_px): {"frames": [psnr or None per frame], "pooled", "sse", "count"}."""
     fn = "texture_psnr"
-    verts = _verts(fn, verts)
-    faces = _faces(fn, faces)
+    verts = check_verts(fn, verts)
+    faces = check_faces(fn, faces)
     if int(erode_px) < 0:
         raise ValueError(f"{fn}: erode_px must be >= 0, got {erode_px}")
     ds = dataset
     F, H, W = ds.n_images, ds.H, ds.W
-    R, T, K = _cams(fn, F, ds.R, ds.T, ds.K, verts.device)
+    R, T, K = check_cams(fn, F, ds.R, ds.T, ds.K, verts.device)
     normals = vertex_normals(verts, faces)
     sums = torch.zeros(F, 2, dtype=torch.int64, device=verts.device)
     for f0, f1, Rc, Tc, zbuf in frame_chunks(fn, verts, faces, R, T, K, H, W, frame_chunk):

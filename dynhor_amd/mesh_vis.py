@@ -22,8 +22,8 @@ import math
 import torch
 
 from . import _lib
-from .mesh_clean import _device_tensor, _faces
-from .mesh_color import _cams, _draw_args, _same_device, _verts, frame_chunks, vertex_normals
+from ._args import check_cams, check_faces, check_verts, device_tensor, same_device
+from .mesh_color import _draw_args, frame_chunks, vertex_normals
 
 BASE_COLOR = (0.8, 0.46, 0.51)      # the constant base colour of a mesh without vertex colours
 N_WORST = 5
@@ -37,10 +37,10 @@ def shade(verts, faces, zbuf, R, T, K, normals=None, colors=None, rgb=None, labe
     verts, faces, zbuf, R, T, K, alpha, normals, rgb = _draw_args(fn, verts, faces, zbuf, R, T, K, alpha, normals, rgb)
     F, H, W = zbuf.shape
     if colors is not None:
-        colors = _device_tensor(fn, "colors", colors, torch.uint8, lambda s: s == tuple(verts.shape), "[V,3]")
+        colors = device_tensor(fn, "colors", colors, torch.uint8, lambda s: s == tuple(verts.shape), "[V,3]")
     if label is not None:
-        label = _device_tensor(fn, "label", label, torch.int8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
-    _same_device(fn, zbuf.device, colors, label)
+        label = device_tensor(fn, "label", label, torch.int8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
+    same_device(fn, zbuf.device, colors, label)
     out = torch.empty(F, H, W, 3, dtype=torch.uint8, device=zbuf.device)
     counts = torch.zeros(F, 3, dtype=torch.int64, device=zbuf.device) if label is not None else None
     opt = lambda t: _lib.ptr(t) if t is not None else ctypes.c_void_p(0)
@@ -69,11 +69,11 @@ def overlay_frames(verts, faces, dataset, colors=None, alpha: float = 0.6, frame
     same counts (shade's, from the same z-buffer), the images drawn lit through mesh_texture.render_textured.  Images and counts are
     bitwise the same for every chunk size."""
     fn = "overlay_frames"
-    verts = _verts(fn, verts)
-    faces = _faces(fn, faces)
+    verts = check_verts(fn, verts)
+    faces = check_faces(fn, faces)
     ds = dataset
     F, H, W = ds.n_images, ds.H, ds.W
-    R, T, K = _cams(fn, F, ds.R, ds.T, ds.K, verts.device)
+    R, T, K = check_cams(fn, F, ds.R, ds.T, ds.K, verts.device)
     normals = vertex_normals(verts, faces)
     counts = torch.zeros(F, 3, dtype=torch.int64, device=verts.device)
     for f0, f1, Rc, Tc, zbuf in frame_chunks(fn, verts, faces, R, T, K, H, W, frame_chunk):
@@ -144,10 +144,10 @@ def orbit_cameras(R, T, n: int):
 def turntable(verts, faces, K, H: int, W: int, R, T, colors=None, frame_chunk: int = 16, texture=None):
     """u8 [n,H,W,3]: the mesh from the cameras R [n,3,3], T [n,3] (e.g. orbit_cameras) with intrinsics K, on white, alpha 1; with
     texture = (uv, tex) drawn with its texture, lit."""
-    verts = _verts("turntable", verts)
-    faces = _faces("turntable", faces)
+    verts = check_verts("turntable", verts)
+    faces = check_faces("turntable", faces)
     n = R.shape[0]
-    R, T, K = _cams("turntable", n, R, T, K, verts.device)
+    R, T, K = check_cams("turntable", n, R, T, K, verts.device)
     normals = vertex_normals(verts, faces)
     out = torch.empty(n, int(H), int(W), 3, dtype=torch.uint8, device=verts.device)
     for f0, f1, Rc, Tc, zbuf in frame_chunks("turntable", verts, faces, R, T, K, H, W, frame_chunk):

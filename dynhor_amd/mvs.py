@@ -29,8 +29,9 @@ import torch
 
 from . import _lib
 from .match import default_min_va, gray_frames, usable_sources
-from .mesh_clean import _device_tensor, _faces
-from .mesh_color import _cams, _verts, raster_depth, usable_map
+from ._args import check_cams, check_faces, check_verts, device_tensor, lap
+from .mesh_color import raster_depth, usable_map
+from .settings import merge
 
 # defaults of the YAML's mvs: block -- first settings, none of them tuned.  min_va None: match's 4 N^2; min_vb None: float(min_va)
 DEFAULTS = {"offsets": (1, 2), "sigma": 1.0, "a_min": 0.5, "erode_px": 1, "patch": 4, "range": 0.04, "depths": 33, "fine_depths": 9,
@@ -48,8 +49,8 @@ def _kinv(K):
 
 
 def _nbr(fn, nbr, F, device):
-    nbr = _device_tensor(fn, "nbr", nbr, torch.int32, lambda s: len(s) == 2 and s[0] == F and 1 <= s[1] <= MAX_NEIGHBOURS,
-                         f"[{F},1..{MAX_NEIGHBOURS}]")
+    nbr = device_tensor(fn, "nbr", nbr, torch.int32, lambda s: len(s) == 2 and s[0] == F and 1 <= s[1] <= MAX_NEIGHBOURS,
+                        f"[{F},1..{MAX_NEIGHBOURS}]")
     if nbr.device != device:
         raise ValueError(f"{fn}: every tensor must be on {device}")
     return nbr
@@ -61,14 +62,14 @@ def sweep(gray, valid, R, T, K, pix, guide, nbr, depths: int, step: float, patch
     pixels pix int32 [n,3] = (fi, px, py) with guide f32 [n,4] = (z0, nx, ny, nz) on gray, valid u8 [F,H,W]; R [F,3,3], T [F,3], K [3,3]
     float32; nbr int32 [F,Nn] (dh_mvs_sweep, in calls of at most PIXEL_CHUNK pixels)."""
     fn = "sweep"
-    gray = _device_tensor(fn, "gray", gray, torch.uint8, lambda s: len(s) == 3 and s[1] > 0 and s[2] > 0, "[F,H,W]")
+    gray = device_tensor(fn, "gray", gray, torch.uint8, lambda s: len(s) == 3 and s[1] > 0 and s[2] > 0, "[F,H,W]")
     F, H, W = gray.shape
     dev = gray.device
-    valid = _device_tensor(fn, "valid", valid, torch.uint8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
-    R, T, K = _cams(fn, F, R, T, K, dev)
-    pix = _device_tensor(fn, "pix", pix, torch.int32, lambda s: len(s) == 2 and s[1] == 3, "[n,3]")
+    valid = device_tensor(fn, "valid", valid, torch.uint8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
+    R, T, K = check_cams(fn, F, R, T, K, dev)
+    pix = device_tensor(fn, "pix", pix, torch.int32, lambda s: len(s) == 2 and s[1] == 3, "[n,3]")
     n = pix.shape[0]
-    guide = _device_tensor(fn, "guide", guide, torch.float32, lambda s: s == (n, 4), f"[{n},4]")
+    guide = device_tensor(fn, "guide", guide, torch.float32, lambda s: s == (n, 4), f"[{n},4]")
     nbr = _nbr(fn, nbr, F, dev)
     if valid.device != dev or pix.device != dev or guide.device != dev:
         raise ValueError(f"{fn}: every tensor must be on {dev}")
@@ -95,10 +96,10 @@ def check(depth, R, T, K, nbr, depth_rel: float = DEFAULTS["depth_rel"]):
     """count u8 [F,H,W]: per pixel of depth f32 [F,H,W] (NaN or inf: none), the neighbour frames of nbr int32 [F,Nn] whose depth z_j at
     the nearest pixel to the point's projection has |z_pred - z_j| <= depth_rel z_j (dh_mvs_check)."""
     fn = "check"
-    depth = _device_tensor(fn, "depth", depth, torch.float32, lambda s: len(s) == 3 and s[1] > 0 and s[2] > 0, "[F,H,W]")
+    depth = device_tensor(fn, "depth", depth, torch.float32, lambda s: len(s) == 3 and s[1] > 0 and s[2] > 0, "[F,H,W]")
     F, H, W = depth.shape
     dev = depth.device
-    R, T, K = _cams(fn, F, R, T, K, dev)
+    R, T, K = check_cams(fn, F, R, T, K, dev)
     nbr = _nbr(fn, nbr, F, dev)
     if not float(depth_rel) >= 0:
         raise ValueError(f"{fn}: depth_rel >= 0, got {depth_rel}")
@@ -133,9 +134,9 @@ def guide_from_mesh(verts, faces, R, T, K, H: int, W: int, pix=None):
     unit normal in the frame's camera frame, turned to face the camera (n . x_cam <= 0); NaN where no face covers the pixel.  The normal
     is formed in fp64 and rounded once.  pix (int64 [n,3] = (frame, x, y), frame an index into R): f32 [n,4], the same values at those
     pixels only -- the fp64 work is done for n pixels, not for F H W."""
-    verts, faces = _verts("guide_from_mesh", verts), _faces("guide_from_mesh", faces)
+    verts, faces = check_verts("guide_from_mesh", verts), check_faces("guide_from_mesh", faces)
     F, H, W = R.shape[0], int(H), int(W)
-    R, T, K = _cams("guide_from_mesh", F, R, T, K, verts.device)
+    R, T, K = check_cams("guide_from_mesh", F, R, T, K, verts.device)
     zbuf = raster_depth(verts, faces, R, T, K, H, W)
     if pix is None:
         fyx = torch.ones(F, H, W, dtype=torch.bool, device=zbuf.device).nonzero()
@@ -252,11 +253,7 @@ def write_cloud_ply(path: str, points, normals, colors):
 
 def check_settings(settings: dict) -> dict:
     """DEFAULTS overlaid with `settings`; an unknown key or a value out of range raises ValueError.  min_va and min_vb are resolved."""
-    unknown = sorted(set(settings) - set(DEFAULTS))
-    if unknown:
-        raise ValueError(f"mvs: unknown setting(s) {unknown}; known: {sorted(DEFAULTS)}")
-    s = dict(DEFAULTS)
-    s.update({k: v for k, v in settings.items() if v is not None})
+    s = merge("mvs", DEFAULTS, None, settings, check_overrides=True)
     if isinstance(s["offsets"], str):
         s["offsets"] = tuple(int(o) for o in s["offsets"].split(",") if o.strip())
     s["offsets"] = tuple(int(o) for o in s["offsets"])
@@ -289,23 +286,19 @@ def depth_maps(dataset, verts, faces, frames=None, **settings):
     s = check_settings(settings)
     F, H, W = dataset.label.shape
     dev = dataset.label.device
-    verts, faces = _verts("depth_maps", verts), _faces("depth_maps", faces)
-    R, T, K = _cams("depth_maps", F, dataset.R, dataset.T, dataset.K, dev)
+    verts, faces = check_verts("depth_maps", verts), check_faces("depth_maps", faces)
+    R, T, K = check_cams("depth_maps", F, dataset.R, dataset.T, dataset.K, dev)
     todo = list(range(F)) if frames is None else sorted({int(f) for f in frames})
     if any(f < 0 or f >= F for f in todo):
         raise ValueError(f"depth_maps: frames must lie in [0, {F}), got {frames}")
     sec = {}
 
-    def lap(name, t0):
-        torch.cuda.synchronize(dev)
-        sec[name] = sec.get(name, 0.0) + time.time() - t0
-
-    t0 = time.time()
+    t0 = time.perf_counter()
     usable = usable_map(dataset.label, s["erode_px"])
     gray, valid = gray_frames(dataset.rgb, usable, s["sigma"], s["a_min"], s["frame_chunk"])
     src_ok = usable_sources(gray, valid, s["patch"], s["min_va"], s["frame_chunk"])
     nbr = neighbours(F, s["offsets"]).to(dev)
-    lap("gray", t0)
+    lap(sec, "gray", t0, dev)
     D1, D2 = s["depths"], s["fine_depths"]
     step1 = 2.0 * s["range"] / (D1 - 1)
     step2 = 0.25 * step1
@@ -319,15 +312,13 @@ def depth_maps(dataset, verts, faces, frames=None, **settings):
     grid[::s["step_px"], ::s["step_px"]] = True
     for c0 in range(0, len(todo), s["frame_chunk"]):
         fr = torch.tensor(todo[c0:c0 + s["frame_chunk"]], dtype=torch.int64, device=dev)
-        t0 = time.time()
+        t0 = time.perf_counter()
         fyx = (src_ok[fr] & grid[None]).nonzero()
         pix = torch.stack([fr[fyx[:, 0]], fyx[:, 2], fyx[:, 1]], 1).to(torch.int32).contiguous()
         gd = guide_from_mesh(verts, faces, R[fr].contiguous(), T[fr].contiguous(), K, H, W, pix=fyx[:, [0, 2, 1]])
-        lap("guide", t0)
-        t0 = time.time()
+        t0 = lap(sec, "guide", t0, dev)
         f1, i1 = sweep(gray, valid, R, T, K, pix, gd, nbr, D1, step1, s["patch"], s["min_va"], s["min_vb"], s["min_views"], s["min_cos"])
-        lap("sweep", t0)
-        t0 = time.time()
+        t0 = lap(sec, "sweep", t0, dev)
         why = torch.zeros(pix.shape[0], dtype=torch.uint8, device=dev)
         why[i1[:, 2] != 0] = 1
         why[(why == 0) & ~(f1[:, 1] >= s["score_min"])] = 2
@@ -335,12 +326,10 @@ def depth_maps(dataset, verts, faces, frames=None, **settings):
         sel = (why == 0).nonzero().reshape(-1)
         gd2 = gd[sel].clone()
         gd2[:, 0] = f1[sel, 0]
-        lap("gates", t0)
-        t0 = time.time()
+        t0 = lap(sec, "gates", t0, dev)
         f2, i2 = sweep(gray, valid, R, T, K, pix[sel].contiguous(), gd2, nbr, D2, step2, s["patch"], s["min_va"], s["min_vb"],
                        s["min_views"], s["min_cos"])
-        lap("sweep", t0)
-        t0 = time.time()
+        t0 = lap(sec, "sweep", t0, dev)
         bad2 = i2[:, 2] != 0
         why[sel[bad2]] = 4
         pf, py, px = pix[:, 0].long(), pix[:, 2].long(), pix[:, 1].long()
@@ -350,8 +339,8 @@ def depth_maps(dataset, verts, faces, frames=None, **settings):
         good = sel[~bad2]
         depth[pf[good], py[good], px[good]] = f2[~bad2, 0]
         score[pf[good], py[good], px[good]] = f2[~bad2, 1]
-        lap("gates", t0)
-    t0 = time.time()
+        lap(sec, "gates", t0, dev)
+    t0 = time.perf_counter()
     if s["min_consistent"] > 0:
         # on the grid's own image: pixel (x, y) of the grid is pixel (x / step_px, y / step_px) of the camera diag(1/s, 1/s, 1) K, so the
         # nearest pixel in a neighbour is the nearest grid pixel there
@@ -363,10 +352,9 @@ def depth_maps(dataset, verts, faces, frames=None, **settings):
         lost[drop] = 5
         depth[drop] = nan
     kept = torch.isfinite(depth)
-    lap("check", t0)
-    t0 = time.time()
+    t0 = lap(sec, "check", t0, dev)
     normal, normal_ok = normals_from_depth(depth, kept, _kinv(K).reshape(3, 3), s["depth_rel"], s["step_px"])
-    lap("normals", t0)
+    lap(sec, "normals", t0, dev)
     per, tot = [], {"swept": 0, "kept": 0, "lost": {name: 0 for name in LOST}}
     dev_all = []
     for f in todo:

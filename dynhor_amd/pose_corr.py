@@ -26,8 +26,8 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .mesh_clean import _device_tensor, _faces
-from .mesh_color import _cams, _verts, raster_depth
+from ._args import check_cams, check_faces, check_verts, device_tensor
+from .mesh_color import raster_depth
 
 # defaults of the YAML's pose_corr: block; DESIGN_NEXT_ROWS.md section 24 says where each comes from
 DEFAULTS = {"mode": "none", "lw_corr": 1e-3, "delta_px": 2.0, "min_cos": 0.1, "min_conf": 0.0}
@@ -43,19 +43,19 @@ def corr_sums(verts, faces, R, T, K, zbuf, matches, pairs, max_count: int, delta
     int64 [n_pairs,5] = (slot, i, j, first, count); max_count: a host-side bound on the counts.  resid f32 [M] (optional) receives |r|
     per match of these pairs, -1 where it does not count.  Nothing is read back."""
     fn = "corr_sums"
-    verts = _verts(fn, verts)
-    faces = _faces(fn, faces)
-    zbuf = _device_tensor(fn, "zbuf", zbuf, torch.int64, lambda s: len(s) == 3, "[n_z,H,W]")
+    verts = check_verts(fn, verts)
+    faces = check_faces(fn, faces)
+    zbuf = device_tensor(fn, "zbuf", zbuf, torch.int64, lambda s: len(s) == 3, "[n_z,H,W]")
     n_z, H, W = zbuf.shape
     if H == 0 or W == 0:
         raise ValueError(f"{fn}: empty images {H}x{W}")
     F = R.shape[0] if torch.is_tensor(R) and R.dim() >= 1 else -1
-    R, T, K = _cams(fn, F, R, T, K, zbuf.device)
-    matches = _device_tensor(fn, "matches", matches, torch.float32, lambda s: len(s) == 2 and s[1] == 5, "[M,5]")
-    pairs = _device_tensor(fn, "pairs", pairs, torch.int64, lambda s: len(s) == 2 and s[1] == 5, "[n_pairs,5]")
+    R, T, K = check_cams(fn, F, R, T, K, zbuf.device)
+    matches = device_tensor(fn, "matches", matches, torch.float32, lambda s: len(s) == 2 and s[1] == 5, "[M,5]")
+    pairs = device_tensor(fn, "pairs", pairs, torch.int64, lambda s: len(s) == 2 and s[1] == 5, "[n_pairs,5]")
     M, n_pairs = matches.shape[0], pairs.shape[0]
     if resid is not None:
-        resid = _device_tensor(fn, "resid", resid, torch.float32, lambda s: s == (M,), f"[{M}]")
+        resid = device_tensor(fn, "resid", resid, torch.float32, lambda s: s == (M,), f"[{M}]")
         if not resid.is_contiguous():
             raise ValueError(f"{fn}: resid must be contiguous")
     if any(t.device != zbuf.device for t in (verts, faces, matches, pairs) + (() if resid is None else (resid,))):
@@ -83,11 +83,11 @@ def frame_grads(rows, scale, start, entries):
     fn = "frame_grads"
     L = _lib.lib()
     width = int(L.dh_pose_corr_width())
-    rows = _device_tensor(fn, "rows", rows, torch.float64, lambda s: len(s) == 2 and s[1] == width, f"[n_pairs,{width}]")
+    rows = device_tensor(fn, "rows", rows, torch.float64, lambda s: len(s) == 2 and s[1] == width, f"[n_pairs,{width}]")
     n_pairs = rows.shape[0]
-    scale = _device_tensor(fn, "scale", scale, torch.float64, lambda s: s == (n_pairs,), f"[{n_pairs}]")
-    start = _device_tensor(fn, "start", start, torch.int64, lambda s: len(s) == 1 and s[0] >= 1, "[F+1]")
-    entries = _device_tensor(fn, "entries", entries, torch.int64, lambda s: len(s) == 1, "[E]")
+    scale = device_tensor(fn, "scale", scale, torch.float64, lambda s: s == (n_pairs,), f"[{n_pairs}]")
+    start = device_tensor(fn, "start", start, torch.int64, lambda s: len(s) == 1 and s[0] >= 1, "[F+1]")
+    entries = device_tensor(fn, "entries", entries, torch.int64, lambda s: len(s) == 1, "[E]")
     if any(t.device != rows.device for t in (scale, start, entries)):
         raise ValueError(f"{fn}: every tensor must be on {rows.device}")
     F = start.shape[0] - 1
@@ -124,7 +124,7 @@ class CorrespondenceTerm:
     def __init__(self, matches, pair_i, pair_j, pair_first, pair_count, n_frames: int, H: int, W: int, active=None,
                  delta_px=DEFAULTS["delta_px"], min_cos=DEFAULTS["min_cos"], frame_chunk: int = 16):
         fn = "CorrespondenceTerm"
-        self.matches = _device_tensor(fn, "matches", matches, torch.float32, lambda s: len(s) == 2 and s[1] == 5, "[M,5]")
+        self.matches = device_tensor(fn, "matches", matches, torch.float32, lambda s: len(s) == 2 and s[1] == 5, "[M,5]")
         dev = self.device = self.matches.device
         M = self.matches.shape[0]
         self.F, self.H, self.W, self.frame_chunk = int(n_frames), int(H), int(W), int(frame_chunk)

@@ -42,9 +42,10 @@ import math
 import torch
 
 from . import _lib
-from .mesh_clean import _device_tensor, _faces
-from .mesh_color import _verts, raster_depth
+from ._args import check_faces, check_verts, device_tensor
+from .mesh_color import raster_depth
 from .pose_sil import DEFAULTS as POSE_SIL_DEFAULTS
+from .settings import merge
 
 BOX_EXPANSION = 1.3
 # defaults of the YAML's pose_init: block (runner.POSE_INIT_DEFAULTS); DESIGN_NEXT_ROWS.md section 16 says where each comes from
@@ -138,7 +139,7 @@ def viterbi(node_cost: torch.Tensor, edge_cost) -> list:
 # ------------------------------------------------------------------------------------------------ kernels
 def label_boxes(label) -> torch.Tensor:
     """boxes int32 [n,4] = (xmin, ymin, xmax, ymax) over label == 1 of label i8 [n,H,W]; (W, H, -1, -1) without an object pixel."""
-    label = _device_tensor("label_boxes", "label", label, torch.int8, lambda s: len(s) == 3 and s[1] > 0 and s[2] > 0, "[n,H,W]")
+    label = device_tensor("label_boxes", "label", label, torch.int8, lambda s: len(s) == 3 and s[1] > 0 and s[2] > 0, "[n,H,W]")
     n, H, W = label.shape
     boxes = torch.empty(n, 4, dtype=torch.int32, device=label.device)
     if n:
@@ -151,9 +152,9 @@ def sil_crop_pack(label, sq, S: int):
     """(obj, keep) int64 [n, S^2 / 64] (the bits of the kernel's uint64 words): label i8 [n,H,W] resampled on the squares sq f32 [n,3]
     (crop_squares) and packed, sample r S + c at bit (s & 63) of word (s >> 6)."""
     fn = "sil_crop_pack"
-    label = _device_tensor(fn, "label", label, torch.int8, lambda s: len(s) == 3 and s[1] > 0 and s[2] > 0, "[n,H,W]")
+    label = device_tensor(fn, "label", label, torch.int8, lambda s: len(s) == 3 and s[1] > 0 and s[2] > 0, "[n,H,W]")
     n, H, W = label.shape
-    sq = _device_tensor(fn, "sq", sq, torch.float32, lambda s: s == (n, 3), f"[{n},3]")
+    sq = device_tensor(fn, "sq", sq, torch.float32, lambda s: s == (n, 3), f"[{n},3]")
     S = int(S)
     if S < 8 or S > 128 or S % 8:
         raise ValueError(f"{fn}: S must be a multiple of 8 in [8, 128], got {S}")
@@ -171,10 +172,10 @@ def sil_bank_score(frame_obj, frame_keep, bank_obj, view_chunk: int = 0) -> torc
     """int32 [F,V,2] = (intersection, union) of every frame (obj / keep planes int64 [F,Wd]) against every bank view (int64 [V,Wd]),
     the views in launches of `view_chunk` (0: one launch); the same tensor for every chunking."""
     fn = "sil_bank_score"
-    frame_obj = _device_tensor(fn, "frame_obj", frame_obj, torch.int64, lambda s: len(s) == 2 and s[1] > 0, "[F,Wd]")
+    frame_obj = device_tensor(fn, "frame_obj", frame_obj, torch.int64, lambda s: len(s) == 2 and s[1] > 0, "[F,Wd]")
     F, Wd = frame_obj.shape
-    frame_keep = _device_tensor(fn, "frame_keep", frame_keep, torch.int64, lambda s: s == (F, Wd), f"[{F},{Wd}]")
-    bank_obj = _device_tensor(fn, "bank_obj", bank_obj, torch.int64, lambda s: len(s) == 2 and s[1] == Wd, f"[V,{Wd}]")
+    frame_keep = device_tensor(fn, "frame_keep", frame_keep, torch.int64, lambda s: s == (F, Wd), f"[{F},{Wd}]")
+    bank_obj = device_tensor(fn, "bank_obj", bank_obj, torch.int64, lambda s: len(s) == 2 and s[1] == Wd, f"[V,{Wd}]")
     if frame_keep.device != frame_obj.device or bank_obj.device != frame_obj.device:
         raise ValueError(f"{fn}: every tensor must be on {frame_obj.device}")
     V = bank_obj.shape[0]
@@ -228,8 +229,8 @@ def build_view_bank(verts, faces, n_views=DEFAULTS["n_views"], seed=DEFAULTS["se
     bank camera, "settings"}.  The views are rendered by mesh_color.raster_depth in chunks of view_chunk at render_size^2; (zbuf != -1)
     is the label the box, crop and pack kernels take."""
     fn = "build_view_bank"
-    verts = _verts(fn, verts)
-    faces = _faces(fn, faces)
+    verts = check_verts(fn, verts)
+    faces = check_faces(fn, faces)
     n_views, rs, S, view_chunk = int(n_views), int(render_size), int(crop_size), int(view_chunk)
     if n_views < 1 or rs < 8 or view_chunk < 1 or not float(distance_scale) > 1.0:
         raise ValueError(f"{fn}: n_views >= 1, render_size >= 8, view_chunk >= 1, distance_scale > 1; got {n_views}, {render_size}, "
@@ -321,13 +322,9 @@ def init_poses(verts, faces, dataset, bank: dict | None = None, pose_sil: dict |
     angle_prev_deg, filled_from}], "iou_fit_mean", "iou_final_mean", "settings", "bank": its settings, "refine": the refine_poses result
     without its tensors (None without final_refine), "R", "T" (float32 device tensors)}."""
     fn = "init_poses"
-    unknown = sorted(set(settings) - set(DEFAULTS))
-    if unknown:
-        raise ValueError(f"{fn}: unknown setting(s) {unknown}; known: {sorted(DEFAULTS)}")
-    st = dict(DEFAULTS)
-    st.update({k: v for k, v in settings.items() if v is not None})
-    verts = _verts(fn, verts)
-    faces = _faces(fn, faces)
+    st = merge(fn, DEFAULTS, None, settings, check_overrides=True)
+    verts = check_verts(fn, verts)
+    faces = check_faces(fn, faces)
     ds = dataset
     F, dev = ds.n_images, verts.device
     if int(st["candidates"]) < 1 or int(st["hyp_iters"]) < 1 or int(st["hyp_chunk"]) < 1 or not float(st["lw_track"]) >= 0.0 or \

@@ -29,8 +29,8 @@ import math
 import torch
 
 from . import _lib
-from .mesh_clean import _device_tensor, _faces
-from .mesh_color import _cams, _check_bake_args, _verts, raster_depth, usable_map, vertex_normals
+from ._args import check_cams, check_faces, check_verts, device_tensor
+from .mesh_color import _check_bake_args, raster_depth, usable_map, vertex_normals
 
 # defaults of the YAML's pose_photo: block; DESIGN_NEXT_ROWS.md section 19 says where each comes from
 DEFAULTS = {"mode": "none", "points": 20000, "levels": (2.0, 1.0, 0.0), "lw_photo": 0.25, "delta": 0.1, "a_min": 0.5, "min_cos": 0.2,
@@ -58,9 +58,9 @@ def blur_frames(rgb, usable, sigma: float) -> torch.Tensor:
     ceil(3 sigma)) over the pixels with usable u8 [F,H,W] set, normalised by a = the kernel's usable share; all 0 where a == 0.
     sigma 0: (usable ? rgb / 255 : 0, usable)."""
     fn = "blur_frames"
-    rgb = _device_tensor(fn, "rgb", rgb, torch.uint8, lambda s: len(s) == 4 and s[3] == 3, "[F,H,W,3]")
+    rgb = device_tensor(fn, "rgb", rgb, torch.uint8, lambda s: len(s) == 4 and s[3] == 3, "[F,H,W,3]")
     F, H, W = rgb.shape[:3]
-    usable = _device_tensor(fn, "usable", usable, torch.uint8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
+    usable = device_tensor(fn, "usable", usable, torch.uint8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
     if usable.device != rgb.device:
         raise ValueError(f"{fn}: rgb on {rgb.device}, usable on {usable.device}")
     if H == 0 or W == 0:
@@ -83,16 +83,16 @@ def photo_sums(pts, normals, colors, img, zbuf, R, T, K, depth_eps: float = DEFA
     [11..13] d[0] / dT, [14] contributing pairs, [15] pairs with every channel inside delta.  img: blur_frames of the F frames; zbuf:
     mesh_color.raster_depth of the mesh the points lie on, at R, T, K.  Nothing is read back."""
     fn = "photo_sums"
-    pts = _device_tensor(fn, "pts", pts, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[N,3]")
+    pts = device_tensor(fn, "pts", pts, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[N,3]")
     n = pts.shape[0]
-    normals = _device_tensor(fn, "normals", normals, torch.float32, lambda s: s == (n, 3), f"[{n},3]")
-    colors = _device_tensor(fn, "colors", colors, torch.float32, lambda s: s == (n, 3), f"[{n},3]")
-    zbuf = _device_tensor(fn, "zbuf", zbuf, torch.int64, lambda s: len(s) == 3, "[F,H,W]")
+    normals = device_tensor(fn, "normals", normals, torch.float32, lambda s: s == (n, 3), f"[{n},3]")
+    colors = device_tensor(fn, "colors", colors, torch.float32, lambda s: s == (n, 3), f"[{n},3]")
+    zbuf = device_tensor(fn, "zbuf", zbuf, torch.int64, lambda s: len(s) == 3, "[F,H,W]")
     F, H, W = zbuf.shape
     if H == 0 or W == 0:
         raise ValueError(f"{fn}: empty images {H}x{W}")
-    img = _device_tensor(fn, "img", img, torch.float32, lambda s: s == (F, H, W, 4), f"[{F},{H},{W},4]")
-    R, T, K = _cams(fn, F, R, T, K, zbuf.device)
+    img = device_tensor(fn, "img", img, torch.float32, lambda s: s == (F, H, W, 4), f"[{F},{H},{W},4]")
+    R, T, K = check_cams(fn, F, R, T, K, zbuf.device)
     if any(t.device != zbuf.device for t in (pts, normals, colors, img)):
         raise ValueError(f"{fn}: every tensor must be on {zbuf.device}")
     depth_eps, min_cos, a_min, delta = float(depth_eps), float(min_cos), float(a_min), float(delta)
@@ -167,13 +167,13 @@ class PhotometricTerm:
     def __init__(self, pts, normals, colors, rgb, usable, levels=DEFAULTS["levels"], delta=DEFAULTS["delta"], a_min=DEFAULTS["a_min"],
                  min_cos=DEFAULTS["min_cos"], depth_eps=DEFAULTS["depth_eps"], max_bytes=MAX_BYTES):
         fn = "PhotometricTerm"
-        self.pts = _device_tensor(fn, "pts", pts, torch.float32, lambda s: len(s) == 2 and s[1] == 3 and s[0] > 0, "[N,3], N > 0")
+        self.pts = device_tensor(fn, "pts", pts, torch.float32, lambda s: len(s) == 2 and s[1] == 3 and s[0] > 0, "[N,3], N > 0")
         n = self.pts.shape[0]
-        self.normals = _device_tensor(fn, "normals", normals, torch.float32, lambda s: s == (n, 3), f"[{n},3]")
-        self.colors = _device_tensor(fn, "colors", colors, torch.float32, lambda s: s == (n, 3), f"[{n},3]")
-        self.rgb = _device_tensor(fn, "rgb", rgb, torch.uint8, lambda s: len(s) == 4 and s[3] == 3, "[F,H,W,3]")
+        self.normals = device_tensor(fn, "normals", normals, torch.float32, lambda s: s == (n, 3), f"[{n},3]")
+        self.colors = device_tensor(fn, "colors", colors, torch.float32, lambda s: s == (n, 3), f"[{n},3]")
+        self.rgb = device_tensor(fn, "rgb", rgb, torch.uint8, lambda s: len(s) == 4 and s[3] == 3, "[F,H,W,3]")
         F, H, W = self.rgb.shape[:3]
-        self.usable = _device_tensor(fn, "usable", usable, torch.uint8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
+        self.usable = device_tensor(fn, "usable", usable, torch.uint8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
         self.levels = tuple(float(s) for s in levels)
         if not self.levels or any(not 0.0 <= s <= 21.0 for s in self.levels):
             raise ValueError(f"{fn}: levels must be a non-empty list of blur sigmas in [0, 21] pixels, got {levels}")
@@ -220,8 +220,8 @@ def make_term(verts, faces, dataset, n_points=DEFAULTS["points"], seed=DEFAULTS[
               erode_px=DEFAULTS["erode_px"], **settings) -> PhotometricTerm:
     """A PhotometricTerm of `n_points` samples of the mesh, coloured from vertex_colors or (uv, texture), over the dataset's frames
     with their usable maps (object pixels eroded by erode_px)."""
-    verts = _verts("make_term", verts)
-    faces = _faces("make_term", faces)
+    verts = check_verts("make_term", verts)
+    faces = check_faces("make_term", faces)
     pts, nrm, col = surface_points(verts, faces, n_points, seed, vertex_colors=vertex_colors, uv=uv, texture=texture)
     usable = usable_map(dataset.label, int(erode_px))
     return PhotometricTerm(pts, nrm, col, dataset.rgb, usable, **settings)

@@ -40,8 +40,7 @@ import math
 import torch
 
 from . import _lib
-from .mesh_clean import _device_tensor, _faces
-from .mesh_color import _cams, _verts
+from ._args import check_cams, check_faces, check_verts, device_tensor
 from .pose import rot6d_to_matrix
 from .pose_corr import DEFAULTS as CORR_DEFAULTS
 from .pose_photo import DEFAULTS as PHOTO_DEFAULTS, level_at
@@ -55,7 +54,7 @@ def label_edt(label, value: int, rmax: int) -> torch.Tensor:
     """float32 [F,H,W]: the squared Euclidean distance in pixels to the nearest pixel with label == value, searched over |dx|, |dy| <=
     rmax; +inf where the window holds none.  Results <= rmax^2 are the exact distance transform; larger ones only say "farther"."""
     fn = "label_edt"
-    label = _device_tensor(fn, "label", label, torch.int8, lambda s: len(s) == 3, "[F,H,W]")
+    label = device_tensor(fn, "label", label, torch.int8, lambda s: len(s) == 3, "[F,H,W]")
     value, rmax = int(value), int(rmax)
     if not -128 <= value <= 127:
         raise ValueError(f"{fn}: value must lie in [-128, 127], got {value}")
@@ -75,8 +74,8 @@ def nearest_faces(verts, faces, R, T, K, H: int, W: int, rmax_px: float) -> torc
     """near int64 [F,H,W]: the uint64 keys (float_bits(d2) << 32) | face of the face nearest to each pixel centre, d2 = 0 exactly where
     raster_depth is covered, -1 where no face lies within rmax_px pixels.  near >> 32 (as int32 bits) is d2 as float32."""
     fn = "nearest_faces"
-    verts = _verts(fn, verts)
-    faces = _faces(fn, faces)
+    verts = check_verts(fn, verts)
+    faces = check_faces(fn, faces)
     if verts.device != faces.device:
         raise ValueError(f"{fn}: verts on {verts.device}, faces on {faces.device}")
     H, W, rmax_px = int(H), int(W), float(rmax_px)
@@ -85,7 +84,7 @@ def nearest_faces(verts, faces, R, T, K, H: int, W: int, rmax_px: float) -> torc
     if not 0.0 <= rmax_px <= 4096.0:
         raise ValueError(f"{fn}: rmax_px must lie in [0, 4096], got {rmax_px}")
     F = R.shape[0] if torch.is_tensor(R) and R.dim() >= 1 else -1
-    R, T, K = _cams(fn, F, R, T, K, verts.device)
+    R, T, K = check_cams(fn, F, R, T, K, verts.device)
     near = torch.full((F, H, W), -1, dtype=torch.int64, device=verts.device)
     if F == 0 or faces.shape[0] == 0:
         return near
@@ -102,16 +101,16 @@ def silhouette_sums(verts, faces, near, R, T, K, d2_obj, d2_hand, label, sigma: 
     """float64 [F,17] on the device, the layout of dh_sil_loss_grad: [0] sum w (S - M)^2, [1] sum w, [2..10] d[0] / dR row-major,
     [11..13] d[0] / dT, [14..16] tp, fp, fn.  Nothing is read back."""
     fn = "silhouette_loss_grad"
-    verts = _verts(fn, verts)
-    faces = _faces(fn, faces)
-    near = _device_tensor(fn, "near", near, torch.int64, lambda s: len(s) == 3, "[F,H,W]")
+    verts = check_verts(fn, verts)
+    faces = check_faces(fn, faces)
+    near = device_tensor(fn, "near", near, torch.int64, lambda s: len(s) == 3, "[F,H,W]")
     F, H, W = near.shape
     if H == 0 or W == 0:
         raise ValueError(f"{fn}: empty images {H}x{W}")
-    R, T, K = _cams(fn, F, R, T, K, near.device)
-    d2_obj = _device_tensor(fn, "d2_obj", d2_obj, torch.float32, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
-    d2_hand = _device_tensor(fn, "d2_hand", d2_hand, torch.float32, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
-    label = _device_tensor(fn, "label", label, torch.int8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
+    R, T, K = check_cams(fn, F, R, T, K, near.device)
+    d2_obj = device_tensor(fn, "d2_obj", d2_obj, torch.float32, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
+    d2_hand = device_tensor(fn, "d2_hand", d2_hand, torch.float32, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
+    label = device_tensor(fn, "label", label, torch.int8, lambda s: s == (F, H, W), f"[{F},{H},{W}]")
     if any(t.device != near.device for t in (verts, faces, d2_obj, d2_hand, label)):
         raise ValueError(f"{fn}: every tensor must be on {near.device}")
     sigma, cut, edge_offset_px = float(sigma), float(cut), float(edge_offset_px)
@@ -161,12 +160,12 @@ class SilhouettePoseOptimizer:
                  lw_sil=DEFAULTS["lw_sil"], lw_smooth=DEFAULTS["lw_smooth"], frame_chunk=DEFAULTS["frame_chunk"], active=None,
                  photo=None, lw_photo=0.0, corr=None, lw_corr=0.0):
         fn = "SilhouettePoseOptimizer"
-        self.verts = _verts(fn, verts)
-        self.faces = _faces(fn, faces)
-        label = _device_tensor(fn, "label", label, torch.int8, lambda s: len(s) == 3, "[F,H,W]")
+        self.verts = check_verts(fn, verts)
+        self.faces = check_faces(fn, faces)
+        label = device_tensor(fn, "label", label, torch.int8, lambda s: len(s) == 3, "[F,H,W]")
         self.F, self.H, self.W = label.shape
         dev = self.device = label.device
-        R0, T0, self.K = _cams(fn, self.F, R0, T0, K, dev)
+        R0, T0, self.K = check_cams(fn, self.F, R0, T0, K, dev)
         if self.verts.device != dev or self.faces.device != dev:
             raise ValueError(f"{fn}: every tensor must be on {dev}")
         if int(frame_chunk) < 1:
@@ -392,8 +391,8 @@ def refine_poses(verts, faces, dataset, iters=DEFAULTS["iters"], lr=DEFAULTS["lr
         raise ValueError(f"refine_poses: iters must be >= 1, got {iters}")
     if not 0.0 < float(sigma_end_px) <= float(sigma_px):
         raise ValueError(f"refine_poses: 0 < sigma_end_px <= sigma_px, got {sigma_end_px}, {sigma_px}")
-    verts = _verts("refine_poses", verts)
-    faces = _faces("refine_poses", faces)
+    verts = check_verts("refine_poses", verts)
+    faces = check_faces("refine_poses", faces)
     ds = dataset
     stems = list(ds.stems) if ds.stems is not None else ["{:04d}".format(i) for i in range(ds.n_images)]
     before = _iou(overlay_frames(verts, faces, ds, frame_chunk=frame_chunk))

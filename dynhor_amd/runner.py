@@ -31,6 +31,7 @@ from .pose_photo import DEFAULTS as POSE_PHOTO_DEFAULTS
 from .pose_sil import DEFAULTS as POSE_SIL_DEFAULTS
 from .renderer import NeuSRenderer
 from .sdf_init import SDF_INIT_DEFAULTS
+from .settings import int_in, is_int, merge, one_of
 
 DEFAULT_CONF = {
     "seq_name": "synthetic", "exp_name": "neus",
@@ -119,6 +120,9 @@ MESH_SIMPLIFY_DEFAULTS = {"mode": "none", "regularization": 1e-3, "cells_max": 1
 # the optional mesh_vis: block of the YAML (visualize_mesh; dynhor_amd/mesh_vis.py): mesh None = the reconstruction at `resolution`;
 # normalize "none" | "reference" for a mesh file; turntable = frames of the orbit GIF (0: none)
 MESH_VIS_DEFAULTS = {"mesh": None, "normalize": "none", "resolution": 512, "alpha": 0.6, "turntable": 0}
+# the optional eval: block of the YAML (evaluate_mesh; dynhor_amd/metrics.py); a key at null counts as not set
+EVAL_DEFAULTS = {"gt_mesh": None, "gt_normalize": "none", "resolution": 512, "gt_resolution": 512, "n_samples": 1_000_000,
+                 "taus": (0.005, 0.01, 0.02), "gt_align": "none", "gt_align_init": "identity", "align_opts": None}
 VIS_WRITERS = 8                  # JPEG writer threads of visualize_mesh (a fixed pool: JPEG encoding is host work)
 
 
@@ -462,6 +466,64 @@ class Runner:
                 self.ray_gen.manual_seed((self.conf["train"]["ray_seed"] * 1000003 + self.rank) ^ (self.iter_step * 2654435761 % (1 << 31)))
         self.store.bump()
 
+    # ------------------------------------------------------------------ what the opt-in modes share: settings, mesh, compute, write
+    def _board_writer(self):
+        """The scalar writer under <exp>/board, made at first use."""
+        if self._board is None:
+            from .tb_events import make_writer
+            self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+        return self._board
+
+    def _write_json(self, d, name, res):
+        os.makedirs(d, exist_ok=True)
+        with open(os.path.join(d, name), "w") as f:
+            json.dump(res, f, indent=1)
+
+    def _reseed_pose_refiner(self):
+        """With train.refine_poses on: a new PoseRefiner from the dataset's current poses (its Adam state starts afresh).  Returns
+        whether there is one."""
+        if self.pose_refiner is not None:
+            from .pose import PoseRefiner
+            tr = self.conf["train"]
+            self.pose_refiner = PoseRefiner(self.dataset.R, self.dataset.T, lr=tr["pose_lr"], rot_lr_mult=tr["pose_rot_lr_mult"]).to(self.device)
+        return self.pose_refiner is not None
+
+    def _guide_mesh(self, fn, mesh, normalize, resolution, clean, extract, simplify):
+        """(verts f32, faces int64, name, clean mode, simplify mode) of the mesh refine_poses_silhouette fits and match_frames /
+        mvs_depth take as their guide: _select_mesh with `mesh` / `normalize` left at None taken from the config's mesh_vis: block and
+        `resolution` from its pose_sil: block.  A mesh without faces raises."""
+        vc = merge("mesh_vis", MESH_VIS_DEFAULTS, self.conf.get("mesh_vis"), {"mesh": mesh, "normalize": normalize})
+        resolution = int(resolution if resolution is not None else
+                         merge("pose_sil", POSE_SIL_DEFAULTS, self.conf.get("pose_sil"))["resolution"])
+        verts, faces, name, cmode = self._select_mesh(fn, vc["mesh"], vc["normalize"], resolution, clean, extract, simplify)
+        if faces.shape[0] == 0:
+            raise ValueError(f"{fn}: the mesh {name} has no faces")
+        return verts.to(torch.float32).contiguous(), faces.to(torch.int64).contiguous(), name, cmode, self._simplify_conf(simplify)["mode"]
+
+    def _template_mesh(self, fn, mesh, normalize):
+        """(verts f32, faces int64, mesh, normalize) of the template init_poses and init_sdf start from: the .ply / .obj file `mesh` with
+        normalize "none" | "reference"; left at None it is the config's data_info.obj_path, normalised as the reference normalises
+        its prior when data_info.normalize_mesh is true."""
+        from . import metrics
+        di = self.conf["data_info"]
+        if mesh is None:
+            mesh = di.get("obj_path")
+            if normalize is None:
+                normalize = "reference" if di.get("normalize_mesh") else "none"
+        normalize = normalize if normalize is not None else "none"
+        if mesh is None:
+            raise ValueError(f"{fn}: no template mesh: give --vis_mesh (with --vis_normalize) or data_info.obj_path (with "
+                             "normalize_mesh) in the config")
+        if normalize not in ("none", "reference"):
+            raise ValueError(f"{fn}: normalize must be 'none' or 'reference', got {normalize!r}")
+        verts, faces = metrics.load_mesh(str(mesh))
+        if normalize == "reference":
+            verts = metrics.normalize_like_reference(verts)[0]
+        verts, faces = verts.to(self.device, torch.float32).contiguous(), faces.to(self.device, torch.int64).contiguous()
+        if faces.shape[0] == 0:
+            raise ValueError(f"{fn}: the template {mesh} has no faces")
+        return verts, faces, mesh, normalize
+
     # ------------------------------------------------------------------ validation
     @torch.no_grad()
     def render_image(self, idx, resolution_level=4, chunk=4096):
@@ -572,51 +634,32 @@ class Runner:
                 os.makedirs(d, exist_ok=True)
                 write_textured_obj(os.path.join(d, "{:0>8d}_textured.obj".format(self.iter_step)), verts, faces, uv, tex,
                                    image=tc["image"])
-                with open(os.path.join(d, "{:0>8d}_texture.json".format(self.iter_step)), "w") as f:
-                    json.dump(st, f, indent=1)
+                self._write_json(d, "{:0>8d}_texture.json".format(self.iter_step), st)
         return verts, faces
 
     def _texture_conf(self, mode=None, size=None):
         """The YAML's optional mesh_texture: block over MESH_TEXTURE_DEFAULTS; `mode` / `size` (when not None) override its mode / size."""
         from .mesh_texture import IMAGES, MODES
-        c = dict(MESH_TEXTURE_DEFAULTS)
-        c.update(self.conf.get("mesh_texture") or {})
-        if mode is not None:
-            c["mode"] = mode
-        if size is not None:
-            c["size"] = size
-        if c["mode"] not in MODES:
-            raise ValueError(f"mesh_texture mode must be one of {MODES}, got {c['mode']!r}")
-        if isinstance(c["size"], bool) or not isinstance(c["size"], int) or not 8 <= c["size"] <= 32768:
-            raise ValueError(f"mesh_texture size must be an integer in [8, 32768], got {c['size']!r}")
-        if isinstance(c["sharpen"], bool) or not isinstance(c["sharpen"], int) or not 0 <= c["sharpen"] <= 4:
-            raise ValueError(f"mesh_texture sharpen must be an integer in [0, 4], got {c['sharpen']!r}")
-        if c["image"] not in IMAGES:
-            raise ValueError(f"mesh_texture image must be one of {IMAGES}, got {c['image']!r}")
+        c = merge("mesh_texture", MESH_TEXTURE_DEFAULTS, self.conf.get("mesh_texture"), {"mode": mode, "size": size})
+        one_of("mesh_texture", "mode", c["mode"], MODES)
+        int_in("mesh_texture", "size", c["size"], 8, 32768)
+        int_in("mesh_texture", "sharpen", c["sharpen"], 0, 4)
+        one_of("mesh_texture", "image", c["image"], IMAGES)
         return c
 
     def _color_conf(self, mode=None):
         """The YAML's optional mesh_color: block over MESH_COLOR_DEFAULTS; `mode` (when not None) overrides its mode."""
         from .mesh_color import MODES
-        c = dict(MESH_COLOR_DEFAULTS)
-        c.update(self.conf.get("mesh_color") or {})
-        if mode is not None:
-            c["mode"] = mode
-        if c["mode"] not in MODES:
-            raise ValueError(f"mesh_color mode must be one of {MODES}, got {c['mode']!r}")
+        c = merge("mesh_color", MESH_COLOR_DEFAULTS, self.conf.get("mesh_color"), {"mode": mode})
+        one_of("mesh_color", "mode", c["mode"], MODES)
         return c
 
     def _extract_conf(self, mode=None):
         """The YAML's optional mesh_extract: block over MESH_EXTRACT_DEFAULTS; `mode` (when not None) overrides its mode."""
         from .mesh_extract import MAX_BLOCK, MODES
-        c = dict(MESH_EXTRACT_DEFAULTS)
-        c.update(self.conf.get("mesh_extract") or {})
-        if mode is not None:
-            c["mode"] = mode
-        if c["mode"] not in MODES:
-            raise ValueError(f"mesh_extract mode must be one of {MODES}, got {c['mode']!r}")
-        if isinstance(c["block"], bool) or not isinstance(c["block"], int) or not 1 <= c["block"] <= MAX_BLOCK:
-            raise ValueError(f"mesh_extract block must be an integer in [1, {MAX_BLOCK}], got {c['block']!r}")
+        c = merge("mesh_extract", MESH_EXTRACT_DEFAULTS, self.conf.get("mesh_extract"), {"mode": mode})
+        one_of("mesh_extract", "mode", c["mode"], MODES)
+        int_in("mesh_extract", "block", c["block"], 1, MAX_BLOCK)
         if isinstance(c["lipschitz"], bool) or not isinstance(c["lipschitz"], (int, float)) or not c["lipschitz"] > 0:
             raise ValueError(f"mesh_extract lipschitz must be a number > 0, got {c['lipschitz']!r}")
         return c
@@ -624,16 +667,12 @@ class Runner:
     def _simplify_conf(self, mode=None):
         """The YAML's optional mesh_simplify: block over MESH_SIMPLIFY_DEFAULTS; `mode` (when not None) overrides its mode."""
         from .mesh_simplify import MAX_CELLS, parse_mode
-        c = dict(MESH_SIMPLIFY_DEFAULTS)
-        c.update(self.conf.get("mesh_simplify") or {})
-        if mode is not None:
-            c["mode"] = mode
+        c = merge("mesh_simplify", MESH_SIMPLIFY_DEFAULTS, self.conf.get("mesh_simplify"), {"mode": mode})
         c["mode"] = "none" if c["mode"] is None else c["mode"]
         parse_mode(c["mode"])
         if isinstance(c["regularization"], bool) or not isinstance(c["regularization"], (int, float)) or not 0 < c["regularization"] <= 1e6:
             raise ValueError(f"mesh_simplify regularization must be a number in (0, 1e6], got {c['regularization']!r}")
-        if isinstance(c["cells_max"], bool) or not isinstance(c["cells_max"], int) or not 1 <= c["cells_max"] <= MAX_CELLS:
-            raise ValueError(f"mesh_simplify cells_max must be an integer in [1, {MAX_CELLS}], got {c['cells_max']!r}")
+        int_in("mesh_simplify", "cells_max", c["cells_max"], 1, MAX_CELLS)
         return c
 
     def _simplify_mesh(self, verts, faces, mode=None):
@@ -649,12 +688,8 @@ class Runner:
     def _clean_conf(self, mode=None):
         """The YAML's optional mesh_clean: block over MESH_CLEAN_DEFAULTS; `mode` (when not None) overrides its mode."""
         from .mesh_clean import MODES
-        c = dict(MESH_CLEAN_DEFAULTS)
-        c.update(self.conf.get("mesh_clean") or {})
-        if mode is not None:
-            c["mode"] = mode
-        if c["mode"] not in MODES:
-            raise ValueError(f"mesh_clean mode must be one of {MODES}, got {c['mode']!r}")
+        c = merge("mesh_clean", MESH_CLEAN_DEFAULTS, self.conf.get("mesh_clean"), {"mode": mode})
+        one_of("mesh_clean", "mode", c["mode"], MODES)
         return c
 
     def _clean_mesh(self, verts, faces, mode=None):
@@ -693,17 +728,13 @@ class Runner:
         (cleaned) mesh is simplified before it is scored and the dict gains `simplify`: the mode and mesh_simplify.simplify_mesh's stats.
         Rank 0 writes meshes/<iter:08d>_eval.json and logs every number as eval/<key> to <exp>/board.  Returns the dict."""
         from . import metrics
-        ev = self.conf.get("eval") or {}
-        pick = lambda v, key, default: v if v is not None else (ev.get(key) if ev.get(key) is not None else default)
-        gt_mesh = pick(gt_mesh, "gt_mesh", None)
-        gt_normalize = pick(gt_normalize, "gt_normalize", "none")
-        resolution = int(pick(resolution, "resolution", 512))
-        gt_resolution = int(pick(gt_resolution, "gt_resolution", 512))
-        n_samples = int(pick(n_samples, "n_samples", 1_000_000))
-        taus = tuple(float(t) for t in pick(taus, "taus", (0.005, 0.01, 0.02)))
-        gt_align = pick(gt_align, "gt_align", "none")
-        gt_align_init = pick(gt_align_init, "gt_align_init", "identity")
-        align_opts = pick(align_opts, "align_opts", None)
+        ec = merge("eval", EVAL_DEFAULTS, {k: v for k, v in (self.conf.get("eval") or {}).items() if v is not None},
+                   dict(gt_mesh=gt_mesh, gt_normalize=gt_normalize, resolution=resolution, gt_resolution=gt_resolution, n_samples=n_samples,
+                        taus=taus, gt_align=gt_align, gt_align_init=gt_align_init, align_opts=align_opts))
+        gt_mesh, gt_normalize, gt_align, gt_align_init, align_opts = (ec[k] for k in ("gt_mesh", "gt_normalize", "gt_align", "gt_align_init",
+                                                                                      "align_opts"))
+        resolution, gt_resolution, n_samples = int(ec["resolution"]), int(ec["gt_resolution"]), int(ec["n_samples"])
+        taus = tuple(float(t) for t in ec["taus"])
         metrics.check_align_args("evaluate_mesh", gt_align, gt_align_init)
         if gt_mesh is not None:
             gt_v, gt_f = metrics.load_mesh(gt_mesh)
@@ -739,20 +770,16 @@ class Runner:
                        extract_dense_samples=es["dense_samples"])
         if save and self.rank == 0:
             d = os.path.join(self.base_exp_dir, "meshes")
-            os.makedirs(d, exist_ok=True)
-            with open(os.path.join(d, "{:0>8d}_eval.json".format(self.iter_step)), "w") as f:
-                json.dump(res, f, indent=1)
+            self._write_json(d, "{:0>8d}_eval.json".format(self.iter_step), res)
             if gt_align != "none":
                 from .mesh import write_ply
                 write_ply(os.path.join(d, "{:0>8d}_gt_aligned.ply".format(self.iter_step)),
                           metrics.aligned_ground_truth(gt_v, res, gt_normalize), gt_f)
-            if self._board is None:
-                from .tb_events import make_writer
-                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+            board = self._board_writer()
             for k, v in res.items():
                 if k != "iter" and isinstance(v, (int, float)):
-                    self._board.add_scalar("eval/" + k, float(v), self.iter_step)
-            self._board.flush()
+                    board.add_scalar("eval/" + k, float(v), self.iter_step)
+            board.flush()
         return res
 
     @torch.no_grad()
@@ -800,11 +827,10 @@ class Runner:
         from .mesh_vis import orbit_cameras, overlay_frames, silhouette_summary, turntable as render_turntable
         if self.rank != 0:
             return None
-        vc = dict(MESH_VIS_DEFAULTS)
-        vc.update(self.conf.get("mesh_vis") or {})
-        pick = lambda v, key: v if v is not None else vc[key]
-        mesh, normalize = pick(mesh, "mesh"), pick(normalize, "normalize")
-        resolution, alpha, n_turn = int(pick(resolution, "resolution")), float(pick(alpha, "alpha")), int(pick(turntable, "turntable"))
+        vc = merge("mesh_vis", MESH_VIS_DEFAULTS, self.conf.get("mesh_vis"),
+                   {"mesh": mesh, "normalize": normalize, "resolution": resolution, "alpha": alpha, "turntable": turntable})
+        mesh, normalize = vc["mesh"], vc["normalize"]
+        resolution, alpha, n_turn = int(vc["resolution"]), float(vc["alpha"]), int(vc["turntable"])
         verts, faces, name, cmode = self._select_mesh("visualize_mesh", mesh, normalize, resolution, clean, extract, simplify)
         smode = self._simplify_conf(simplify)["mode"]
         cc = self._color_conf(color)
@@ -855,35 +881,28 @@ class Runner:
             if pool is not None:
                 pool.shutdown()
         if save:
-            with open(os.path.join(d, "silhouette.json"), "w") as f:
-                json.dump(res, f, indent=1)
+            self._write_json(d, "silhouette.json", res)
             self.last_vis_dir = d
-            if self._board is None:
-                from .tb_events import make_writer
-                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+            board = self._board_writer()
             for k in ("iou_mean", "iou_median", "iou_min"):
                 if res[k] is not None:
-                    self._board.add_scalar("vis/" + k, float(res[k]), self.iter_step)
-            self._board.flush()
+                    board.add_scalar("vis/" + k, float(res[k]), self.iter_step)
+            board.flush()
         return res
 
     # ------------------------------------------------------------------ novel views, depth and normal maps (surface_render.py)
     def _surface_conf(self, method=None, level=None, background=None):
         """The YAML's optional surface_render: block over SURFACE_RENDER_DEFAULTS; arguments that are not None override it."""
         from .surface_render import BACKGROUNDS
-        c = dict(SURFACE_RENDER_DEFAULTS)
-        c.update(self.conf.get("surface_render") or {})
-        for k, v in (("method", method), ("level", level), ("background", background)):
-            if v is not None:
-                c[k] = v
+        c = merge("surface_render", SURFACE_RENDER_DEFAULTS, self.conf.get("surface_render"),
+                  {"method": method, "level": level, "background": background})
         unknown = set(c) - set(SURFACE_RENDER_DEFAULTS)
         if unknown:
             raise ValueError(f"surface_render: unknown keys {sorted(unknown)}")
         if c["method"] not in ("surface", "volume"):
             raise ValueError(f"surface_render method must be 'surface' or 'volume', got {c['method']!r}")
-        if c["background"] not in BACKGROUNDS:
-            raise ValueError(f"surface_render background must be one of {BACKGROUNDS}, got {c['background']!r}")
-        if isinstance(c["level"], bool) or not isinstance(c["level"], int) or c["level"] < 1:
+        one_of("surface_render", "background", c["background"], BACKGROUNDS)
+        if not is_int(c["level"]) or c["level"] < 1:
             raise ValueError(f"surface_render level must be an integer >= 1, got {c['level']!r}")
         if c["method"] == "volume" and c["background"] == "frame":
             raise ValueError("surface_render: method 'volume' has no hit mask to lay over a frame; use background 'white' or 'black'")
@@ -1005,33 +1024,22 @@ class Runner:
         if save:
             frames = [Image.fromarray(im) for im in host["rgb"].numpy()]
             frames[0].save(os.path.join(d, "views.gif"), save_all=True, append_images=frames[1:], duration=100, loop=0)
-            with open(os.path.join(d, "views.json"), "w") as f:
-                json.dump(res, f, indent=1)
+            self._write_json(d, "views.json", res)
             if score:
-                if self._board is None:
-                    from .tb_events import make_writer
-                    self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+                board = self._board_writer()
                 for k in ("psnr", "iou"):
                     if res.get(k + "_mean") is not None:
-                        self._board.add_scalar("view/" + k, float(res[k + "_mean"]), self.iter_step)
-                self._board.flush()
+                        board.add_scalar("view/" + k, float(res[k + "_mean"]), self.iter_step)
+                board.flush()
         self.last_view_dir = d if save else None
         return dict(res, dir=self.last_view_dir, **host)
 
     # ------------------------------------------------------------------ renderings scored against the frames (image_metrics.py)
     def _image_eval_conf(self, frames=None, maps=None):
         """The YAML's optional image_eval: block over IMAGE_EVAL_DEFAULTS; arguments that are not None override it."""
-        block = self.conf.get("image_eval") or {}
-        unknown = sorted(set(block) - set(IMAGE_EVAL_DEFAULTS))
-        if unknown:
-            raise ValueError(f"image_eval: unknown keys {unknown}; known: {sorted(IMAGE_EVAL_DEFAULTS)}")
-        c = dict(IMAGE_EVAL_DEFAULTS)
-        c.update(block)
-        if frames is not None:
-            c["frames"] = frames
-        if maps is not None:
-            c["maps"] = bool(maps)
-        if isinstance(c["erode_px"], bool) or not isinstance(c["erode_px"], int) or c["erode_px"] < 0:
+        c = merge("image_eval", IMAGE_EVAL_DEFAULTS, self.conf.get("image_eval"),
+                  {"frames": frames, "maps": None if maps is None else bool(maps)}, check_block="keys")
+        if not is_int(c["erode_px"]) or c["erode_px"] < 0:
             raise ValueError(f"image_eval erode_px must be an integer >= 0, got {c['erode_px']!r}")
         return c
 
@@ -1119,16 +1127,13 @@ class Runner:
         scored = sorted((x for x in rows if x["ssim"] is not None), key=lambda x: x["ssim"])
         res["worst_ssim"] = [{"frame": x["frame"], "ssim": x["ssim"], "psnr": x["psnr"]} for x in scored[:5]]
         if save:
-            with open(os.path.join(d, "eval.json"), "w") as f:
-                json.dump(res, f, indent=1)
-            if self._board is None:
-                from .tb_events import make_writer
-                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+            self._write_json(d, "eval.json", res)
+            board = self._board_writer()
             for key in ("psnr", "ssim"):
                 for split in ("train", "holdout"):
                     if res[f"{key}_{split}"] is not None:
-                        self._board.add_scalar(f"eval_img/{key}_{split}", res[f"{key}_{split}"], self.iter_step)
-            self._board.flush()
+                        board.add_scalar(f"eval_img/{key}_{split}", res[f"{key}_{split}"], self.iter_step)
+            board.flush()
         self.last_eval_dir = d if save else None
         res = dict(res, dir=self.last_eval_dir)
         if ec["maps"]:
@@ -1216,43 +1221,27 @@ class Runner:
         from .pose_sil import refine_poses
         if self.world > 1:
             raise ValueError("refine_poses_silhouette runs on one rank (the poses of all frames are optimised jointly)")
-        pc = dict(POSE_SIL_DEFAULTS)
-        pc.update(self.conf.get("pose_sil") or {})
-        unknown = sorted(set(overrides) - set(POSE_SIL_DEFAULTS))
-        if unknown:
-            raise ValueError(f"refine_poses_silhouette: unknown pose_sil setting(s) {unknown}; known: {sorted(POSE_SIL_DEFAULTS)}")
-        pc.update({k: v for k, v in overrides.items() if v is not None})
-        pp = dict(POSE_PHOTO_DEFAULTS)
-        pp.update(self.conf.get("pose_photo") or {})
-        unknown = sorted(set(pp) - set(POSE_PHOTO_DEFAULTS))
-        pmode = photo if photo is not None else pp["mode"]
-        if unknown or pmode not in PHOTO_MODES:
-            raise ValueError(f"refine_poses_silhouette: pose_photo mode {pmode!r} (one of {PHOTO_MODES}), unknown setting(s) {unknown}; "
-                             f"known: {sorted(POSE_PHOTO_DEFAULTS)}")
-        cc = dict(POSE_CORR_DEFAULTS)
-        cc.update(self.conf.get("pose_corr") or {})
-        unknown = sorted(set(cc) - set(POSE_CORR_DEFAULTS))
-        kmode = corr if corr is not None else cc["mode"]
-        if unknown or kmode not in CORR_MODES:
-            raise ValueError(f"refine_poses_silhouette: pose_corr mode {kmode!r} (one of {CORR_MODES}), unknown setting(s) {unknown}; "
-                             f"known: {sorted(POSE_CORR_DEFAULTS)}")
-        vc = dict(MESH_VIS_DEFAULTS)
-        vc.update(self.conf.get("mesh_vis") or {})
-        mesh_arg, normalize_arg, resolution_arg = mesh, normalize, resolution
-        mesh = mesh if mesh is not None else vc["mesh"]
-        normalize = normalize if normalize is not None else vc["normalize"]
-        resolution = int(resolution if resolution is not None else pc["resolution"])
-        verts, faces, name, cmode = self._select_mesh("refine_poses_silhouette", mesh, normalize, resolution, clean, extract, simplify)
-        smode = self._simplify_conf(simplify)["mode"]
-        if faces.shape[0] == 0:
-            raise ValueError(f"refine_poses_silhouette: the mesh {name} has no faces")
-        verts, faces = verts.to(torch.float32).contiguous(), faces.to(torch.int64).contiguous()
+        fn = "refine_poses_silhouette"
+        pc = merge("pose_sil", POSE_SIL_DEFAULTS, self.conf.get("pose_sil"), overrides, who=fn, check_overrides=True)
+
+        def term(name, defaults, mode, known):                      # an optional term's block with its mode; both are checked
+            c = merge(name, defaults, self.conf.get(name), {"mode": mode})
+            unknown = sorted(set(c) - set(defaults))
+            if unknown or c["mode"] not in known:
+                raise ValueError(f"{fn}: {name} mode {c['mode']!r} (one of {known}), unknown setting(s) {unknown}; known: {sorted(defaults)}")
+            return c
+
+        pp = term("pose_photo", POSE_PHOTO_DEFAULTS, photo, PHOTO_MODES)
+        cc = term("pose_corr", POSE_CORR_DEFAULTS, corr, CORR_MODES)
+        pmode, kmode = pp["mode"], cc["mode"]
+        verts, faces, name, cmode, smode = self._guide_mesh(fn, mesh, normalize, resolution, clean, extract, simplify)
+        mesh_file = merge("mesh_vis", MESH_VIS_DEFAULTS, self.conf.get("mesh_vis"), {"mesh": mesh})["mesh"]     # None: the reconstruction
         corr_term = None
         if kmode != "none":
             from .pose_corr import make_term as make_corr_term
             if kmode == "match":
-                self.match_frames(guide="mesh", mesh=mesh_arg, normalize=normalize_arg, resolution=resolution_arg, clean=clean,
-                                  extract=extract, simplify=simplify, save=save)
+                self.match_frames(guide="mesh", mesh=mesh, normalize=normalize, resolution=resolution, clean=clean, extract=extract,
+                                  simplify=simplify, save=save)
             if self.dataset.corr is None:
                 raise ValueError("refine_poses_silhouette: pose_corr 'dataset' needs correspondences and the dataset holds none: point "
                                  "data_info.correspondence_infos at a folder of matches, run --mode match_frames first, or use "
@@ -1264,7 +1253,7 @@ class Runner:
                            sigma_px=pc["sigma_px"], sigma_end_px=pc["sigma_end_px"], cut=pc["cut"], edge_offset_px=pc["edge_offset_px"],
                            lw_sil=pc["lw_sil"], lw_smooth=pc["lw_smooth"], frame_chunk=pc["frame_chunk"], report_freq=pc["report_freq"],
                            frames=frames, lw_photo=float(pp["lw_photo"]), corr=corr_term, lw_corr=float(cc["lw_corr"]),
-                           photo=None if pmode == "none" else self._photo_term(pmode, pp, verts, faces, mesh, cmode, smode))
+                           photo=None if pmode == "none" else self._photo_term(pmode, pp, verts, faces, mesh_file, cmode, smode))
         res.pop("R"); res.pop("T")
         res.update(iter=self.iter_step, mesh=name, clean=cmode, faces=int(faces.shape[0]))
         if pmode != "none":
@@ -1273,35 +1262,28 @@ class Runner:
             res.update(corr=kmode)
         if smode != "none":
             res.update(simplify=smode)
-        if self.pose_refiner is not None:
-            from .pose import PoseRefiner
-            tr = self.conf["train"]
-            self.pose_refiner = PoseRefiner(self.dataset.R, self.dataset.T, lr=tr["pose_lr"], rot_lr_mult=tr["pose_rot_lr_mult"]).to(self.device)
-            if save:
-                # load_checkpoint copies the checkpoint's PoseRefiner poses over Dataset.R / T: without a checkpoint of the re-seeded
-                # refiner a later --is_continue run would bring the old poses back
-                res["checkpoint"] = self.save_checkpoint()
+        if self._reseed_pose_refiner() and save:
+            # load_checkpoint copies the checkpoint's PoseRefiner poses over Dataset.R / T: without a checkpoint of the re-seeded
+            # refiner a later --is_continue run would bring the old poses back
+            res["checkpoint"] = self.save_checkpoint()
         if save:
             d = os.path.join(self.base_exp_dir, "poses", "{:0>8d}".format(self.iter_step))
             self.export_poses(os.path.join(d, "obj_infos"))
-            with open(os.path.join(d, "refine.json"), "w") as f:
-                json.dump(res, f, indent=1)
+            self._write_json(d, "refine.json", res)
             res["dir"] = d
             self.last_pose_dir = d
-            if self._board is None:
-                from .tb_events import make_writer
-                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+            board = self._board_writer()
             for st in res["curve"]:
                 for k in ("loss", "loss_sil", "loss_smooth", "iou_mean", "iou_min", "sigma"):
-                    self._board.add_scalar("pose_sil/" + k, float(st[k]), int(st["iter"]))
+                    board.add_scalar("pose_sil/" + k, float(st[k]), int(st["iter"]))
                 if "loss_photo" in st:
-                    self._board.add_scalar("pose/loss_photo", float(st["loss_photo"]), int(st["iter"]))
+                    board.add_scalar("pose/loss_photo", float(st["loss_photo"]), int(st["iter"]))
                 if "loss_corr" in st:
-                    self._board.add_scalar("pose/loss_corr", float(st["loss_corr"]), int(st["iter"]))
+                    board.add_scalar("pose/loss_corr", float(st["loss_corr"]), int(st["iter"]))
             for k in ("iou_mean_before", "iou_mean_after"):
                 if res[k] is not None:
-                    self._board.add_scalar("pose_sil/" + k, float(res[k]), self.iter_step)
-            self._board.flush()
+                    board.add_scalar("pose_sil/" + k, float(res[k]), self.iter_step)
+            board.flush()
         return res
 
     def init_poses(self, mesh=None, normalize=None, save=True, **overrides):
@@ -1313,62 +1295,33 @@ class Runner:
         pose_sil: block.  Rank 0 writes poses/init/obj_infos/<stem>.npz (export_poses) and poses/init/init.json (per frame: view, rank,
         iou_bank, iou_fit, iou_final, angle_prev_deg; the settings) and logs init/* to <exp>/board.  With train.refine_poses on, the
         PoseRefiner is re-seeded from the new poses.  Returns the dict of init.json plus dir (single process: run it on one rank)."""
-        from . import metrics
         from .pose_init import init_poses
         if self.world > 1:
             raise ValueError("init_poses runs on one rank (the final refinement optimises the poses of all frames jointly)")
-        unknown = sorted(set(overrides) - set(POSE_INIT_DEFAULTS))
-        if unknown:
-            raise ValueError(f"init_poses: unknown pose_init setting(s) {unknown}; known: {sorted(POSE_INIT_DEFAULTS)}")
-        ic = dict(POSE_INIT_DEFAULTS)
-        ic.update(self.conf.get("pose_init") or {})
-        ic.update({k: v for k, v in overrides.items() if v is not None})
-        pc = dict(POSE_SIL_DEFAULTS)
-        pc.update(self.conf.get("pose_sil") or {})
-        di = self.conf["data_info"]
-        if mesh is None:
-            mesh = di.get("obj_path")
-            if normalize is None:
-                normalize = "reference" if di.get("normalize_mesh") else "none"
-        normalize = normalize if normalize is not None else "none"
-        if mesh is None:
-            raise ValueError("init_poses: no template mesh: give --vis_mesh (with --vis_normalize) or data_info.obj_path (with "
-                             "normalize_mesh) in the config")
-        if normalize not in ("none", "reference"):
-            raise ValueError(f"init_poses: normalize must be 'none' or 'reference', got {normalize!r}")
-        verts, faces = metrics.load_mesh(str(mesh))
-        if normalize == "reference":
-            verts = metrics.normalize_like_reference(verts)[0]
-        verts, faces = verts.to(self.device, torch.float32).contiguous(), faces.to(self.device, torch.int64).contiguous()
-        if faces.shape[0] == 0:
-            raise ValueError(f"init_poses: the template {mesh} has no faces")
+        ic = merge("pose_init", POSE_INIT_DEFAULTS, self.conf.get("pose_init"), overrides, who="init_poses", check_overrides=True)
+        pc = merge("pose_sil", POSE_SIL_DEFAULTS, self.conf.get("pose_sil"))
+        verts, faces, mesh, normalize = self._template_mesh("init_poses", mesh, normalize)
         res = init_poses(verts, faces, self.dataset,
                          pose_sil={k: pc[k] for k in ("iters", "lr", "rot_lr_mult", "sigma_px", "sigma_end_px", "cut", "edge_offset_px",
                                                       "lw_sil", "lw_smooth", "frame_chunk", "report_freq")}, **ic)
         res.pop("R"); res.pop("T")
         res.update(iter=self.iter_step, mesh=str(mesh), normalize=normalize, faces=int(faces.shape[0]))
-        if self.pose_refiner is not None:
-            from .pose import PoseRefiner
-            tr = self.conf["train"]
-            self.pose_refiner = PoseRefiner(self.dataset.R, self.dataset.T, lr=tr["pose_lr"], rot_lr_mult=tr["pose_rot_lr_mult"]).to(self.device)
+        self._reseed_pose_refiner()
         if save:
             d = os.path.join(self.base_exp_dir, "poses", "init")
             self.export_poses(os.path.join(d, "obj_infos"))
-            with open(os.path.join(d, "init.json"), "w") as f:
-                json.dump(res, f, indent=1)
+            self._write_json(d, "init.json", res)
             res["dir"] = d
             self.last_pose_dir = d
-            if self._board is None:
-                from .tb_events import make_writer
-                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+            board = self._board_writer()
             for k, fr in enumerate(res["frames"]):
                 for key in ("iou_bank", "iou_fit", "iou_final", "angle_prev_deg"):
                     if fr[key] is not None:
-                        self._board.add_scalar("init/" + key, float(fr[key]), k)
+                        board.add_scalar("init/" + key, float(fr[key]), k)
             for key in ("iou_fit_mean", "iou_final_mean"):
                 if res[key] is not None:
-                    self._board.add_scalar("init/" + key, float(res[key]), self.iter_step)
-            self._board.flush()
+                    board.add_scalar("init/" + key, float(res[key]), self.iter_step)
+            board.flush()
         return res
 
     @torch.no_grad()
@@ -1389,30 +1342,11 @@ class Runner:
         from .scene import write_correspondences_to_disk
         if self.world > 1:
             raise ValueError("match_frames runs on one rank")
-        unknown = sorted(set(overrides) - set(MATCH_DEFAULTS))
-        if unknown:
-            raise ValueError(f"match_frames: unknown match setting(s) {unknown}; known: {sorted(MATCH_DEFAULTS)}")
-        mc = dict(self.conf.get("match") or {})
-        mc.update({k: v for k, v in overrides.items() if v is not None})
-        if guide is not None:
-            mc["guide"] = guide
-        if offsets is not None:
-            mc["offsets"] = offsets
-        if warp is not None:
-            mc["warp"] = warp
+        mc = merge("match", MATCH_DEFAULTS, self.conf.get("match"), dict(overrides, guide=guide, offsets=offsets, warp=warp),
+                   who="match_frames", check_overrides=True)
         verts = faces = name = None
-        if (mc.get("guide") or MATCH_DEFAULTS["guide"]) == "mesh":
-            pc = dict(POSE_SIL_DEFAULTS)
-            pc.update(self.conf.get("pose_sil") or {})
-            vc = dict(MESH_VIS_DEFAULTS)
-            vc.update(self.conf.get("mesh_vis") or {})
-            mesh = mesh if mesh is not None else vc["mesh"]
-            normalize = normalize if normalize is not None else vc["normalize"]
-            resolution = int(resolution if resolution is not None else pc["resolution"])
-            verts, faces, name, _ = self._select_mesh("match_frames", mesh, normalize, resolution, clean, extract, simplify)
-            if faces.shape[0] == 0:
-                raise ValueError(f"match_frames: the mesh {name} has no faces")
-            verts, faces = verts.to(torch.float32).contiguous(), faces.to(torch.int64).contiguous()
+        if (mc["guide"] or MATCH_DEFAULTS["guide"]) == "mesh":
+            verts, faces, name, _, _ = self._guide_mesh("match_frames", mesh, normalize, resolution, clean, extract, simplify)
         matches, res = match_frames(self.dataset, verts, faces, **mc)
         res.update(iter=self.iter_step, mesh=name)
         self.dataset.set_correspondences(matches)
@@ -1424,16 +1358,13 @@ class Runner:
                     if f.endswith(".npz"):
                         os.remove(os.path.join(cdir, f))
             write_correspondences_to_disk(matches, d, self.dataset.stems)
-            with open(os.path.join(d, "match.json"), "w") as f:
-                json.dump(res, f, indent=1)
+            self._write_json(d, "match.json", res)
             res["dir"] = d
             self.last_match_dir = d
-            if self._board is None:
-                from .tb_events import make_writer
-                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
-            self._board.add_scalar("match/kept", float(res["totals"]["kept"]), self.iter_step)
-            self._board.add_scalar("match/kept_share", float(res["totals"]["kept_share"]), self.iter_step)
-            self._board.flush()
+            board = self._board_writer()
+            board.add_scalar("match/kept", float(res["totals"]["kept"]), self.iter_step)
+            board.add_scalar("match/kept_share", float(res["totals"]["kept_share"]), self.iter_step)
+            board.flush()
         return res
 
     @torch.no_grad()
@@ -1454,28 +1385,12 @@ class Runner:
         from . import mvs
         if self.world > 1:
             raise ValueError("mvs_depth runs on one rank")
-        voxel = overrides.pop("voxel", None)
-        block = dict(self.conf.get("mvs") or {})
-        block_voxel = block.pop("voxel", None)
-        voxel = block_voxel if voxel is None else voxel
-        for where, keys in (("", overrides), (" in the config", block)):
-            unknown = sorted(set(keys) - set(MVS_DEFAULTS))
-            if unknown:
-                raise ValueError(f"mvs_depth: unknown mvs setting(s) {unknown}{where}; known: {sorted(MVS_DEFAULTS) + ['voxel']}")
-        mc = dict(block)
-        mc.update({k: v for k, v in overrides.items() if v is not None})
+        # voxel is this mode's own key of the block (mvs.fuse takes it, mvs.depth_maps does not)
+        mc = merge("mvs", dict(MVS_DEFAULTS, voxel=None), self.conf.get("mvs"), overrides, who="mvs_depth", check_block=True,
+                   check_overrides=True)
+        voxel = mc.pop("voxel")
         mvs.check_settings(mc)
-        pc = dict(POSE_SIL_DEFAULTS)
-        pc.update(self.conf.get("pose_sil") or {})
-        vc = dict(MESH_VIS_DEFAULTS)
-        vc.update(self.conf.get("mesh_vis") or {})
-        mesh = mesh if mesh is not None else vc["mesh"]
-        normalize = normalize if normalize is not None else vc["normalize"]
-        resolution = int(resolution if resolution is not None else pc["resolution"])
-        verts, faces, name, _ = self._select_mesh("mvs_depth", mesh, normalize, resolution, clean, extract, simplify)
-        if faces.shape[0] == 0:
-            raise ValueError(f"mvs_depth: the mesh {name} has no faces")
-        verts, faces = verts.to(torch.float32).contiguous(), faces.to(torch.int64).contiguous()
+        verts, faces, name, _, _ = self._guide_mesh("mvs_depth", mesh, normalize, resolution, clean, extract, simplify)
         ds = self.dataset
         out = mvs.depth_maps(ds, verts, faces, frames=frames, **mc)
         res = out["stats"]
@@ -1498,32 +1413,20 @@ class Runner:
             mvs.write_cloud_ply(os.path.join(d, "cloud.ply"), pts, nrm, col)
             res["cloud_points"] = int(pts.shape[0])
             res["seconds"]["write"] = time.time() - t0
-            with open(os.path.join(d, "mvs.json"), "w") as f:
-                json.dump(res, f, indent=1)
+            self._write_json(d, "mvs.json", res)
             res["dir"] = d
             self.last_mvs_dir = d
-            if self._board is None:
-                from .tb_events import make_writer
-                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
-            self._board.add_scalar("mvs/kept_share", float(res["totals"]["kept_share"]), self.iter_step)
+            board = self._board_writer()
+            board.add_scalar("mvs/kept_share", float(res["totals"]["kept_share"]), self.iter_step)
             if res["totals"]["guide_dev_median"] is not None:
-                self._board.add_scalar("mvs/guide_dev_median", float(res["totals"]["guide_dev_median"]), self.iter_step)
-            self._board.flush()
+                board.add_scalar("mvs/guide_dev_median", float(res["totals"]["guide_dev_median"]), self.iter_step)
+            board.flush()
         return res
 
     def _sdf_init_conf(self, **overrides):
         """The YAML's optional sdf_init: block over SDF_INIT_DEFAULTS, then the overrides that are not None; an unknown key raises."""
         from .sdf_init import check_settings
-        unknown = sorted(set(overrides) - set(SDF_INIT_DEFAULTS))
-        if unknown:
-            raise ValueError(f"init_sdf: unknown sdf_init setting(s) {unknown}; known: {sorted(SDF_INIT_DEFAULTS)}")
-        block = self.conf.get("sdf_init") or {}
-        unknown = sorted(set(block) - set(SDF_INIT_DEFAULTS))
-        if unknown:
-            raise ValueError(f"init_sdf: unknown sdf_init setting(s) {unknown} in the config; known: {sorted(SDF_INIT_DEFAULTS)}")
-        c = dict(SDF_INIT_DEFAULTS)
-        c.update(block)
-        c.update({k: v for k, v in overrides.items() if v is not None})
+        c = merge("sdf_init", SDF_INIT_DEFAULTS, self.conf.get("sdf_init"), overrides, who="init_sdf", check_block=True, check_overrides=True)
         check_settings(c)
         return c
 
@@ -1540,7 +1443,6 @@ class Runner:
         sdf_init/<template>_fit.ply (the fitted network's zero level set at `resolution`), and logs sdf_init/* to <exp>/board.
         Returns the dict of init.json plus dir and checkpoint.  The template is a category-level prior: training moves away from
         it."""
-        from . import metrics
         from .sdf_init import fit_sdf_to_mesh
         if self.world > 1:
             raise ValueError("init_sdf runs on one rank (the fit is a single-process loop; start training on several afterwards)")
@@ -1548,33 +1450,14 @@ class Runner:
         if self.iter_step != 0:
             raise ValueError(f"init_sdf: this run has already trained to iteration {self.iter_step}; the warm start replaces the "
                              "network's initialisation and runs only at iteration 0 (use a fresh exp_name)")
-        di = self.conf["data_info"]
-        if mesh is None:
-            mesh = di.get("obj_path")
-            if normalize is None:
-                normalize = "reference" if di.get("normalize_mesh") else "none"
-        normalize = normalize if normalize is not None else "none"
-        if mesh is None:
-            raise ValueError("init_sdf: no template mesh: give --vis_mesh (with --vis_normalize) or data_info.obj_path (with "
-                             "normalize_mesh) in the config")
-        if normalize not in ("none", "reference"):
-            raise ValueError(f"init_sdf: normalize must be 'none' or 'reference', got {normalize!r}")
-        verts, faces = metrics.load_mesh(str(mesh))
-        if normalize == "reference":
-            verts = metrics.normalize_like_reference(verts)[0]
-        verts, faces = verts.to(self.device, torch.float32).contiguous(), faces.to(self.device, torch.int64).contiguous()
-        if faces.shape[0] == 0:
-            raise ValueError(f"init_sdf: the template {mesh} has no faces")
+        verts, faces, mesh, normalize = self._template_mesh("init_sdf", mesh, normalize)
         faces_in = int(faces.shape[0])
         self.last_simplify_stats = None
         if self._simplify_conf(simplify_mode)["mode"] != "none":
             verts, faces = self._simplify_mesh(verts, faces, simplify_mode)
         st = self.store
         st.exp_avg.zero_(); st.exp_avg_sq.zero_(); st.step_count = 0
-        if save and self._board is None:
-            from .tb_events import make_writer
-            self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
-        board = self._board if save else None
+        board = self._board_writer() if save else None
         res = fit_sdf_to_mesh(self.renderer, verts, faces,
                               report=(lambda it, loss: board.add_scalar("sdf_init/loss", loss, it)) if board is not None else None, **sc)
         # fresh optimiser moments: the checkpoint, and a training that goes on in this process, start their own Adam
@@ -1592,19 +1475,18 @@ class Runner:
             res["fit_mesh_faces"] = int(ff.shape[0])
             write_ply(res["fit_mesh"], fv, ff)
             res["checkpoint"] = self.save_checkpoint()
-            with open(os.path.join(d, "init.json"), "w") as f:
-                json.dump(res, f, indent=1)
+            self._write_json(d, "init.json", res)
             res["dir"] = d
             for k in ("heldout_before", "heldout_after", "seconds"):
-                self._board.add_scalar("sdf_init/" + k, float(res[k]), self.iter_step)
-            self._board.flush()
+                board.add_scalar("sdf_init/" + k, float(res[k]), self.iter_step)
+            board.flush()
         return res
 
     def _visual_hull_conf(self, **overrides):
         """The YAML's optional visual_hull: block over VISUAL_HULL_DEFAULTS, then the overrides that are not None; an unknown or bad
         key raises."""
-        from .visual_hull import merge_settings
-        return merge_settings(self.conf.get("visual_hull"), **overrides)
+        from .visual_hull import hull_settings
+        return hull_settings(self.conf.get("visual_hull"), **overrides)
 
     @torch.no_grad()
     def visual_hull(self, save=True, simplify=None, **overrides):
@@ -1649,17 +1531,14 @@ class Runner:
             if sv is not None:
                 res["mesh_simple"] = os.path.join(d, "hull_simple.ply")
                 write_ply(res["mesh_simple"], sv, sf)
-            with open(os.path.join(d, "hull.json"), "w") as f:
-                json.dump(res, f, indent=1)
+            self._write_json(d, "hull.json", res)
             res["dir"] = d
-            if self._board is None:
-                from .tb_events import make_writer
-                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
+            board = self._board_writer()
             if sil["iou_mean"] is not None:
-                self._board.add_scalar("hull/iou_mean", float(sil["iou_mean"]), self.iter_step)
-            self._board.add_scalar("hull/volume", float(stats["volume"]), self.iter_step)
-            self._board.add_scalar("hull/sole_carved_max", float(stats["sole_carved"]["share_max"]), self.iter_step)
-            self._board.flush()
+                board.add_scalar("hull/iou_mean", float(sil["iou_mean"]), self.iter_step)
+            board.add_scalar("hull/volume", float(stats["volume"]), self.iter_step)
+            board.add_scalar("hull/sole_carved_max", float(stats["sole_carved"]["share_max"]), self.iter_step)
+            board.flush()
         return res
 
     @torch.no_grad()
@@ -1680,7 +1559,7 @@ class Runner:
         from .mesh_vis import overlay_frames, silhouette_summary
         if self.world > 1:
             raise ValueError("fuse_depth runs on one rank")
-        fz = depth_fuse.merge_settings(self.conf.get("depth_fuse"), **overrides)
+        fz = depth_fuse.fuse_settings(self.conf.get("depth_fuse"), **overrides)
         hc = self._visual_hull_conf()
         if mvs_dir is None:
             mvs_dir = self.last_mvs_dir
@@ -1729,18 +1608,15 @@ class Runner:
             os.makedirs(d, exist_ok=True)
             res["mesh"] = os.path.join(d, "fused.ply")
             write_ply(res["mesh"], verts, faces)
-            with open(os.path.join(d, "fuse.json"), "w") as f:
-                json.dump(res, f, indent=1)
+            self._write_json(d, "fuse.json", res)
             res["dir"] = d
             self.last_fuse_dir = d
-            if self._board is None:
-                from .tb_events import make_writer
-                self._board = make_writer(os.path.join(self.base_exp_dir, "board"))
-            self._board.add_scalar("fuse/volume", float(stats["volume"]), self.iter_step)
-            self._board.add_scalar("fuse/carved_cells", float(stats["carved_cells"]), self.iter_step)
+            board = self._board_writer()
+            board.add_scalar("fuse/volume", float(stats["volume"]), self.iter_step)
+            board.add_scalar("fuse/carved_cells", float(stats["carved_cells"]), self.iter_step)
             if res["residual_median_all"] is not None:
-                self._board.add_scalar("fuse/residual_median", float(res["residual_median_all"]), self.iter_step)
-            self._board.flush()
+                board.add_scalar("fuse/residual_median", float(res["residual_median_all"]), self.iter_step)
+            board.flush()
         return res
 
     def _scene_gt_mesh(self, resolution, chunk=1 << 22, mode="dense"):

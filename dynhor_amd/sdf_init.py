@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from .mesh_sdf import MeshSDF
+from .settings import is_int
 
 # iters x points: 2000 x 65,536 samples against a 5,000-face template is 6.6e11 (point, face) pairs in all.  lr is the training
 # default's double (no warm-up: the fit is short and starts from the geometric initialisation, which is already a distance field);
@@ -37,10 +38,10 @@ SDF_INIT_DEFAULTS = {"iters": 2000, "points": 65536, "ray_points": 8, "lr": 1e-3
 def check_settings(c: dict):
     """ValueError unless the settings (a full dict over SDF_INIT_DEFAULTS) make sense."""
     for k in ("iters", "points", "ray_points", "heldout_points", "report_freq", "resolution"):
-        if isinstance(c[k], bool) or not isinstance(c[k], int) or c[k] < (0 if k == "iters" else 1):
+        if not is_int(c[k]) or c[k] < (0 if k == "iters" else 1):
             raise ValueError(f"sdf_init {k} must be a {'non-negative' if k == 'iters' else 'positive'} integer, got {c[k]!r}")
     for k in ("seed", "heldout_seed"):
-        if isinstance(c[k], bool) or not isinstance(c[k], int):
+        if not is_int(c[k]):
             raise ValueError(f"sdf_init {k} must be an integer, got {c[k]!r}")
     if c["points"] % c["ray_points"]:
         raise ValueError(f"sdf_init points ({c['points']}) must be a multiple of ray_points ({c['ray_points']})")

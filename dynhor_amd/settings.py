@@ -1,0 +1,54 @@
+"""The one layering of every settings block -- defaults, then the YAML's optional block, then the overrides that are not None -- and
+the handful of checks most blocks share.  Plain functions; a block's own domain rules stay in its module.
+
+Which side rejects an unknown key differs from block to block.  That is history, not design, and it is kept as it was (C: the
+config's block, O: the overrides, -: nobody):
+
+    mesh_clean, mesh_color, mesh_texture, mesh_extract, mesh_simplify, mesh_vis       -   (the overrides are named arguments)
+    eval                                                                              -   (and a null in the block counts as not set)
+    surface_render                                                                    C   ("unknown keys", in Runner._surface_conf)
+    image_eval                                                                        C   ("unknown keys")
+    sdf_init                                                                          C O
+    visual_hull, depth_fuse                                                           C O (the block first; an override at None is not looked at)
+    mvs                                                                               C O (voxel is the Runner's own key)
+    match                                                                             O   (the block: match.check_settings, after the guide mesh)
+    pose_sil                                                                          O
+    pose_init                                                                         O   (the block: pose_init.init_poses, after the template)
+    pose_photo, pose_corr                                                             C   (with the mode, in refine_poses_silhouette's wording)
+"""
+from __future__ import annotations
+
+import math
+
+
+def is_int(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def is_num(v) -> bool:
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+
+
+def merge(name, defaults, block, overrides=None, *, who=None, check_block=False, check_overrides=False) -> dict:
+    """dict(defaults), updated with the YAML's `block` (None: empty), then with the `overrides` that are not None.  check_overrides /
+    check_block: ValueError for a key `defaults` does not have (the overrides are looked at first, a None among them too), as
+    "<name>: unknown setting(s) [..]" -- "<who>: unknown <name> setting(s) [..]" when the calling mode `who` is given -- with
+    " in the config" for the block; check_block="keys": the block's older wording "<name>: unknown keys [..]"."""
+    block, overrides = block or {}, overrides or {}
+    head = f"{who}: unknown {name} setting(s)" if who else f"{name}: unknown setting(s)"
+    for on, src, where in ((check_overrides, overrides, ""), (check_block, block, " in the config")):
+        unknown = sorted(set(src) - set(defaults))
+        if on and unknown:
+            raise ValueError(f"{name}: unknown keys {unknown}; known: {sorted(defaults)}" if on == "keys" else
+                             f"{head} {unknown}{where}; known: {sorted(defaults)}")
+    return {**defaults, **block, **{k: v for k, v in overrides.items() if v is not None}}
+
+
+def int_in(block, key, v, lo, hi):
+    if not is_int(v) or not lo <= v <= hi:
+        raise ValueError(f"{block} {key} must be an integer in [{lo}, {hi}], got {v!r}")
+
+
+def one_of(block, key, v, choices):
+    if v not in choices:
+        raise ValueError(f"{block} {key} must be one of {choices}, got {v!r}")

@@ -23,6 +23,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
+from .settings import is_int
 
 MARCH, REFINE, HIT, MISS, FAIL = 0, 1, 2, 3, 4
 STATE_NAMES = ("march", "refine", "hit", "miss", "fail")
@@ -41,13 +42,9 @@ def _p(t):
     return _lib.ptr(t) if t is not None else _NULL
 
 
-def _is_int(v):
-    return isinstance(v, int) and not isinstance(v, bool)
-
-
 def _check_image(fn, H, W, level):
     for name, v in (("H", H), ("W", W), ("level", level)):
-        if not _is_int(v) or v < 1:
+        if not is_int(v) or v < 1:
             raise ValueError(f"{fn}: {name} must be an integer >= 1, got {v!r}")
 
 
@@ -60,11 +57,11 @@ def _check_trace_params(fn, bound, eps, relax, min_step, max_step, refine_steps,
         pos(name, v)
     if max_step < min_step:
         raise ValueError(f"{fn}: max_step {max_step!r} is below min_step {min_step!r}")
-    if not _is_int(refine_steps) or not 1 <= refine_steps <= 255:
+    if not is_int(refine_steps) or not 1 <= refine_steps <= 255:
         raise ValueError(f"{fn}: refine_steps must be an integer in [1, 255], got {refine_steps!r}")
-    if not _is_int(max_steps) or max_steps < 1:
+    if not is_int(max_steps) or max_steps < 1:
         raise ValueError(f"{fn}: max_steps must be an integer >= 1, got {max_steps!r}")
-    if not _is_int(compact_every) or compact_every < 1:
+    if not is_int(compact_every) or compact_every < 1:
         raise ValueError(f"{fn}: compact_every must be an integer >= 1, got {compact_every!r}")
 
 

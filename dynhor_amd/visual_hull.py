@@ -34,8 +34,8 @@ import math
 import torch
 
 from . import _lib
-from .mesh_clean import _device_tensor
-from .mesh_color import _cams
+from ._args import check_cams, device_tensor, lap
+from .settings import int_in, is_int, is_num, merge
 
 MAX_RESOLUTION = 512
 # resolution: grid points per axis of the fine grid (at most MAX_RESOLUTION: 512^3 points carry 1.6 GB of coordinates and 2.1 GB of
@@ -51,50 +51,38 @@ N_WORST = 5
 SIGNED_MAP_CACHE_BYTES = 4 << 30
 
 
-def _is_int(v):
-    return isinstance(v, int) and not isinstance(v, bool)
-
-
-def _is_num(v):
-    return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
-
-
 def check_settings(c: dict):
     """ValueError unless c is a full, sensible dict over VISUAL_HULL_DEFAULTS; the message names the unknown, missing or bad key."""
-    unknown = sorted(set(c) - set(VISUAL_HULL_DEFAULTS))
-    if unknown:
-        raise ValueError(f"visual_hull: unknown setting(s) {unknown}; known: {sorted(VISUAL_HULL_DEFAULTS)}")
+    merge("visual_hull", VISUAL_HULL_DEFAULTS, None, c, check_overrides=True)
     missing = sorted(set(VISUAL_HULL_DEFAULTS) - set(c))
     if missing:
         raise ValueError(f"visual_hull: missing setting(s) {missing}")
     for k in ("resolution", "coarse_resolution"):
-        if not _is_int(c[k]) or not 2 <= c[k] <= MAX_RESOLUTION:
-            raise ValueError(f"visual_hull {k} must be an integer in [2, {MAX_RESOLUTION}], got {c[k]!r}")
-    if c["bound"] != "auto" and not (_is_num(c["bound"]) and c["bound"] > 0):
+        int_in("visual_hull", k, c[k], 2, MAX_RESOLUTION)
+    if c["bound"] != "auto" and not (is_num(c["bound"]) and c["bound"] > 0):
         raise ValueError(f"visual_hull bound must be 'auto' or a positive number, got {c['bound']!r}")
-    if not _is_num(c["band_px"]) or not 1 <= c["band_px"] <= 2048:
+    if not is_num(c["band_px"]) or not 1 <= c["band_px"] <= 2048:
         raise ValueError(f"visual_hull band_px must be a number in [1, 2048], got {c['band_px']!r}")
-    if not _is_int(c["min_carve_votes"]) or not 1 <= c["min_carve_votes"] <= 8:
-        raise ValueError(f"visual_hull min_carve_votes must be an integer in [1, 8], got {c['min_carve_votes']!r}")
-    if not _is_num(c["min_seen"]) or not 0 <= c["min_seen"] <= 1:
+    int_in("visual_hull", "min_carve_votes", c["min_carve_votes"], 1, 8)
+    if not is_num(c["min_seen"]) or not 0 <= c["min_seen"] <= 1:
         raise ValueError(f"visual_hull min_seen must be a number in [0, 1], got {c['min_seen']!r}")
-    if not _is_num(c["outside_value"]) or not c["outside_value"] > 0:
+    if not is_num(c["outside_value"]) or not c["outside_value"] > 0:
         raise ValueError(f"visual_hull outside_value must be a positive number, got {c['outside_value']!r}")
     for k in ("frame_chunk", "point_chunk"):
-        if not _is_int(c[k]) or c[k] < 1:
+        if not is_int(c[k]) or c[k] < 1:
             raise ValueError(f"visual_hull {k} must be a positive integer, got {c[k]!r}")
 
 
-def merge_settings(block=None, **overrides) -> dict:
-    """VISUAL_HULL_DEFAULTS, then the YAML's optional visual_hull: block, then the overrides that are not None; checked."""
-    c = dict(VISUAL_HULL_DEFAULTS)
-    for src, where in ((block or {}, " in the config"), ({k: v for k, v in overrides.items() if v is not None}, "")):
-        unknown = sorted(set(src) - set(VISUAL_HULL_DEFAULTS))
-        if unknown:
-            raise ValueError(f"visual_hull: unknown setting(s) {unknown}{where}; known: {sorted(VISUAL_HULL_DEFAULTS)}")
-        c.update(src)
+def hull_settings(block=None, **overrides) -> dict:
+    """VISUAL_HULL_DEFAULTS, then the YAML's optional visual_hull: block, then the overrides that are not None; checked.  The block's
+    keys are looked at first, and an override at None is not looked at at all."""
+    c = merge("visual_hull", VISUAL_HULL_DEFAULTS, block, check_block=True)
+    c = merge("visual_hull", VISUAL_HULL_DEFAULTS, c, {k: v for k, v in overrides.items() if v is not None}, check_overrides=True)
     check_settings(c)
     return c
+
+
+merge_settings = hull_settings           # the name the config tests and earlier callers know
 
 
 def signed_label_distance(label: torch.Tensor, band_px) -> torch.Tensor:
@@ -103,8 +91,8 @@ def signed_label_distance(label: torch.Tensor, band_px) -> torch.Tensor:
     integers and sqrt is correctly rounded."""
     from .pose_sil import label_edt
     fn = "signed_label_distance"
-    label = _device_tensor(fn, "label", label, torch.int8, lambda s: len(s) == 3, "[F,H,W]")
-    if not _is_num(band_px) or not band_px > 0:
+    label = device_tensor(fn, "label", label, torch.int8, lambda s: len(s) == 3, "[F,H,W]")
+    if not is_num(band_px) or not band_px > 0:
         raise ValueError(f"{fn}: band_px must be a positive number, got {band_px!r}")
     rmax = int(math.ceil(band_px)) + 1
     s = label_edt(label, 1, rmax)
@@ -118,15 +106,15 @@ def hull_accumulate(points, sd, R, T, K, frame0: int, topk, arg, seen):
     (signed_label_distance of the chunk), R [F,3,3], T [F,3], K [3,3], frame0 = the global index of the chunk's first frame; topk f32
     [n,m] (m in 1..8, started at -inf), arg int32 [n] (started at -1), seen int32 [n] (started at 0)."""
     fn = "hull_accumulate"
-    points = _device_tensor(fn, "points", points, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[n,3]")
+    points = device_tensor(fn, "points", points, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[n,3]")
     n = points.shape[0]
-    sd = _device_tensor(fn, "sd", sd, torch.float32, lambda s: len(s) == 3, "[F,H,W]")
+    sd = device_tensor(fn, "sd", sd, torch.float32, lambda s: len(s) == 3, "[F,H,W]")
     F, H, W = sd.shape
-    R, T, K = _cams(fn, F, R, T, K, points.device)
+    R, T, K = check_cams(fn, F, R, T, K, points.device)
     for name, t, dtype, ok, txt in (("topk", topk, torch.float32, lambda s: len(s) == 2 and s[0] == n and 1 <= s[1] <= 8, f"[{n},1..8]"),
                                     ("arg", arg, torch.int32, lambda s: s == (n,), f"[{n}]"),
                                     ("seen", seen, torch.int32, lambda s: s == (n,), f"[{n}]")):
-        if _device_tensor(fn, name, t, dtype, ok, txt) is not t:
+        if device_tensor(fn, name, t, dtype, ok, txt) is not t:
             raise ValueError(f"{fn}: {name} is updated in place and must be contiguous")
     if len({t.device for t in (points, sd, topk, arg, seen)}) != 1:
         raise ValueError(f"{fn}: every tensor must be on {points.device}")
@@ -169,9 +157,9 @@ def hull_field(points, dataset, frames=None, min_carve_votes=None, min_seen=None
     VISUAL_HULL_DEFAULTS.  timer: a dict that gains the seconds of "signed_distance" and "accumulate" (it synchronises; None: no
     waiting).  signed_maps: a dict of the caller's in which the signed map of every frame chunk is kept and looked up again, keyed by
     (first frame, count, band_px): a second call over the same frames then forms none (None: nothing is kept)."""
-    c = merge_settings(None, min_carve_votes=min_carve_votes, min_seen=min_seen, outside_value=outside_value, band_px=band_px,
+    c = hull_settings(None, min_carve_votes=min_carve_votes, min_seen=min_seen, outside_value=outside_value, band_px=band_px,
                        frame_chunk=frame_chunk, point_chunk=point_chunk)
-    points = _device_tensor("hull_field", "points", points, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[n,3]")
+    points = device_tensor("hull_field", "points", points, torch.float32, lambda s: len(s) == 2 and s[1] == 3, "[n,3]")
     dev, n = points.device, points.shape[0]
     m = max(c["min_carve_votes"], 2)
     topk = torch.full((n, m), float("-inf"), dtype=torch.float32, device=dev)
@@ -180,29 +168,19 @@ def hull_field(points, dataset, frames=None, min_carve_votes=None, min_seen=None
     runs, n_frames = _frame_runs(frames, dataset.n_images, c["frame_chunk"])
     R = dataset.R.reshape(-1, 3, 3)
 
-    def clock(key, t0):
-        if timer is not None:
-            import time
-            torch.cuda.synchronize(dev)
-            t1 = time.perf_counter()
-            if t0 is not None:
-                timer[key] = timer.get(key, 0.0) + (t1 - t0)
-            return t1
-        return None
-
     for f0, nf in runs:
-        t0 = clock(None, None)
+        t0 = lap(timer, None, None, dev)
         key = (f0, nf, float(c["band_px"]))
         sd = signed_maps.get(key) if signed_maps is not None else None
         if sd is None:
             sd = signed_label_distance(dataset.label[f0:f0 + nf], c["band_px"])
             if signed_maps is not None:
                 signed_maps[key] = sd
-        t0 = clock("signed_distance", t0)
+        t0 = lap(timer, "signed_distance", t0, dev)
         for p0 in range(0, n, c["point_chunk"]):
             p1 = min(p0 + c["point_chunk"], n)
             hull_accumulate(points[p0:p1], sd, R[f0:f0 + nf], dataset.T[f0:f0 + nf], dataset.K, f0, topk[p0:p1], arg[p0:p1], seen[p0:p1])
-        clock("accumulate", t0)
+        lap(timer, "accumulate", t0, dev)
         del sd
     h = field_from_state(topk, seen, n_frames, c["min_carve_votes"], c["min_seen"], c["outside_value"])
     return h, topk, arg, seen
@@ -309,7 +287,7 @@ def visual_hull(dataset, timer=None, **settings):
     import time
     from .mesh import marching_cubes
     from .schedules import frame_names
-    c = merge_settings(None, **settings)
+    c = hull_settings(None, **settings)
     dev = dataset.label.device
     fc = {k: c[k] for k in ("min_carve_votes", "min_seen", "outside_value", "band_px", "frame_chunk", "point_chunk")}
     F, N = dataset.n_images, c["resolution"]
