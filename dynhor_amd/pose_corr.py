@@ -12,8 +12,9 @@ of frame i, position q in frame j, confidence c: Dataset.set_correspondences, --
 (3), the counted matches and those inside the Huber band; one lane per match, block-ordered fp64 sums, bitwise the same for every
 order of the pairs and every split of them into calls.  ``frame_grads`` (dh_pose_corr_frames) folds the pairs' rows into per-frame
 gradients in the fixed order of a list built once on the host.  ``CorrespondenceTerm`` holds the matches, the pair table and that list
-on the device and rasterises the z-buffers of the source frames in chunks; ``SilhouettePoseOptimizer(corr=, lw_corr=)`` adds
-lw_corr / n_live_pairs * rows / max(sum c, tiny) to the pose gradient (n_live_pairs = the pairs with a counted match).
+on the device and rasterises the z-buffers of the source frames in chunks; bound to a ``SilhouettePoseOptimizer`` (``corr=``) it adds
+lw_corr / n_live_pairs * rows / max(sum c, TINY) to the pose gradient (n_live_pairs = the pairs with a counted match); L_corr = the
+mean over the live pairs of sum c rho / max(sum c, TINY).
 
 Limits: matches alone leave one common rotation of the object frame free (keep a frame fixed, or compare relative rotations); one plane
 per match, so on a coarse mesh the normal is a facet's; Huber is the only outlier handling; the matches are not refreshed while the
@@ -119,7 +120,8 @@ class CorrespondenceTerm:
     """The matches (f32 [M,5] = (p_x, p_y, q_x, q_y, c) on the device, a pair's matches consecutive), the frame pairs (host lists
     pair_i, pair_j, pair_first, pair_count) and the settings, for images of H x W over n_frames frames.  active (bool [F] or None =
     all): a pair is kept when at least one of its frames is active (the inactive one anchors the other).  The kept pairs keep their
-    order; sums(...) returns their rows, chunked over the source frames in groups of frame_chunk z-buffers."""
+    order; sums(...) returns their rows, chunked over the source frames in groups of frame_chunk z-buffers.  bind(opt, weight) attaches
+    the term to a SilhouettePoseOptimizer, which then calls sums / add_grads / stats; settings() is its share of refine_poses' result."""
 
     def __init__(self, matches, pair_i, pair_j, pair_first, pair_count, n_frames: int, H: int, W: int, active=None,
                  delta_px=DEFAULTS["delta_px"], min_cos=DEFAULTS["min_cos"], frame_chunk: int = 16):
@@ -186,6 +188,31 @@ class CorrespondenceTerm:
     def grads(self, rows, scale):
         """frame_grads of the rows of sums() with the per-pair factors `scale`."""
         return frame_grads(rows, scale, self.start, self.entries)
+
+    def bind(self, opt, weight: float):
+        """Attach the term at weight `weight` to the optimiser `opt` (the moving frames were given as `active` at construction)."""
+        if (self.F, self.H, self.W) != (opt.F, opt.H, opt.W) or self.device != opt.device:
+            raise ValueError(f"SilhouettePoseOptimizer: corr holds frames {(self.F, self.H, self.W)} on {self.device}, the labels are "
+                             f"{(opt.F, opt.H, opt.W)} on {opt.device}")
+        self.weight = float(weight)
+
+    def add_grads(self, rows, gR, gT):
+        """gR [F,3,3], gT [F,3] (float64) += weight / n_live_pairs * the frames' share of rows / max(sum c, TINY).  No host read."""
+        live = (rows[:, 26] > 0).sum().clamp(min=1).to(torch.float64)
+        cR, cT = self.grads(rows, (self.weight / live) / rows[:, 1].clamp(min=TINY))
+        gR += cR
+        gT += cT
+
+    def stats(self, rows):
+        """(L_corr, the stats' extra keys) of the rows of sums() on the CPU."""
+        live = rows[:, 26] > 0
+        loss = float((rows[live, 0] / rows[live, 1].clamp(min=TINY)).sum() / max(1, int(live.sum())))
+        return loss, {"loss_corr": loss, "corr_matches": int(rows[:, 26].sum().round()),
+                      "corr_inliers": float(rows[:, 27].sum() / rows[:, 26].sum().clamp(min=1.0))}
+
+    def settings(self) -> dict:
+        return {"pairs": self.n_pairs, "matches": int(sum(self.pair_count)), "lw_corr": self.weight, "delta_px": self.delta_px,
+                "min_cos": self.min_cos}
 
     @torch.no_grad()
     def residuals(self, verts, faces, R, T, K):

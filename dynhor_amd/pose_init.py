@@ -43,6 +43,7 @@ import torch
 
 from . import _lib
 from ._args import check_faces, check_verts, device_tensor
+from .mesh_align import rotation_angle_deg
 from .mesh_color import raster_depth
 from .pose_sil import DEFAULTS as POSE_SIL_DEFAULTS
 from .settings import merge
@@ -69,12 +70,6 @@ def arvo_rotations(n: int, seed: int = 0) -> torch.Tensor:
     v = torch.stack([b.cos() * x[2].sqrt(), b.sin() * x[2].sqrt(), (1.0 - x[2]).sqrt()], -1)
     M = 2.0 * v[:, :, None] * v[:, None, :] - torch.eye(3, dtype=torch.float64)
     return M @ Rz
-
-
-def rotation_angle_deg(Ra: torch.Tensor, Rb: torch.Tensor) -> torch.Tensor:
-    """The angle in degrees of Ra^T Rb, broadcast over the leading dimensions."""
-    tr = (Ra * Rb).sum(dim=(-2, -1))
-    return torch.rad2deg(torch.acos(((tr - 1.0) * 0.5).clamp(-1.0, 1.0)))
 
 
 def crop_squares(boxes: torch.Tensor, S: int, expansion: float = BOX_EXPANSION) -> torch.Tensor:

@@ -13,8 +13,9 @@ it, lands on a pixel of its colour (csrc/pose_photo.hip, include/dynhor_hip.h):
     boundary: the decisions are fp32 and discrete, the values fp64.
   * ``surface_points``: area-weighted samples (``metrics.sample_surface``) with interpolated unit normals and colours from vertex
     colours or a texture.
-  * ``PhotometricTerm``: the points, the blurred active frames of the current level and the settings; ``SilhouettePoseOptimizer``
-    takes one as ``photo=`` and adds lw_photo / n_active * sums[2:14] / max(sum om, tiny) to the pose gradient.
+  * ``PhotometricTerm``: the points, the blurred active frames of the current level and the settings.  Bound to a
+    ``SilhouettePoseOptimizer`` (``photo=``) it evaluates the active frames in the optimiser's chunks and adds lw_photo / n_active *
+    rows[2:14] / max(sum om, TINY) to the pose gradient; L_photo = the mean over the active frames of sum om rho / max(sum om, TINY).
 
 Limits: lighting that moves with the hand is absorbed only by the Huber term (no per-frame gain and bias); colours baked from the views
 at wrong poses are a blurred but consistent target; the point colours are not blurred at the coarse levels.  ``pose_init`` does not use
@@ -162,7 +163,8 @@ def level_at(k: int, iters: int, levels) -> float:
 class PhotometricTerm:
     """The coloured points (pts, normals, colors f32 [N,3] on the device), the frames (rgb u8 [F,H,W,3], usable u8 [F,H,W]) and the
     settings.  set_frames(active_idx) picks the frames the optimiser moves; set_level(sigma) blurs them (16 bytes per pixel and
-    frame: an error that names --pose_frames when that exceeds max_bytes); sums(...) evaluates a chunk of them."""
+    frame: an error that names --pose_frames when that exceeds max_bytes).  bind(opt, weight) attaches the term to a
+    SilhouettePoseOptimizer, which then calls sums / add_grads / stats; settings() is the term's share of refine_poses' result."""
 
     def __init__(self, pts, normals, colors, rgb, usable, levels=DEFAULTS["levels"], delta=DEFAULTS["delta"], a_min=DEFAULTS["a_min"],
                  min_cos=DEFAULTS["min_cos"], depth_eps=DEFAULTS["depth_eps"], max_bytes=MAX_BYTES):
@@ -182,8 +184,6 @@ class PhotometricTerm:
             raise ValueError(f"{fn}: delta > 0 and a_min >= 0, got {delta}, {a_min}")
         self.delta, self.a_min, self.min_cos, self.depth_eps = float(delta), float(a_min), float(min_cos), float(depth_eps)
         self.max_bytes = int(max_bytes)
-        self.sigma = None
-        self.img = None
         self.set_frames(None)
 
     def set_frames(self, active_idx):
@@ -206,14 +206,47 @@ class PhotometricTerm:
             self.img = blur_frames(self._rgb, self._usable, sigma)
             self.sigma = sigma
 
-    def sums(self, verts, faces, R, T, K, f0: int, f1: int) -> torch.Tensor:
-        """photo_sums of the active frames f0..f1-1 at the poses R, T (contiguous, f1 - f0 frames) of the mesh (verts, faces)."""
+    def bind(self, opt, weight: float):
+        """Attach the term at weight `weight` to the optimiser `opt`: its active frames and its frame_chunk."""
+        if tuple(self.rgb.shape[:3]) != (opt.F, opt.H, opt.W) or self.rgb.device != opt.device:
+            raise ValueError(f"SilhouettePoseOptimizer: photo holds frames {tuple(self.rgb.shape[:3])} on {self.rgb.device}, the labels "
+                             f"are {(opt.F, opt.H, opt.W)} on {opt.device}")
+        self.weight = float(weight)
+        self.frame_chunk, self.active_idx = opt.frame_chunk, opt.active_idx
+        self.set_frames(opt.active_idx if len(opt.active_list) != opt.F else None)
+
+    def sums(self, verts, faces, R, T, K) -> torch.Tensor:
+        """photo_sums of the active frames, float64 [n_active,16], at the poses R f32 [F,3,3], T f32 [F,3] of all frames: each chunk of
+        frame_chunk frames on the z-buffer of the mesh (verts, faces) at its poses."""
         if self.img is None:
             self.set_level(self.levels[0])
-        H, W = self._usable.shape[1:]
-        zbuf = raster_depth(verts, faces, R, T, K, H, W)
-        return photo_sums(self.pts, self.normals, self.colors, self.img[f0:f1], zbuf, R, T, K, self.depth_eps, self.min_cos, self.a_min,
-                          self.delta)
+        R, T = R[self.active_idx], T[self.active_idx]
+        n, H, W = self._usable.shape
+        out = []
+        for f0 in range(0, n, self.frame_chunk):
+            f1 = min(n, f0 + self.frame_chunk)
+            Rc, Tc = R[f0:f1].contiguous(), T[f0:f1].contiguous()
+            zbuf = raster_depth(verts, faces, Rc, Tc, K, H, W)
+            out.append(photo_sums(self.pts, self.normals, self.colors, self.img[f0:f1], zbuf, Rc, Tc, K, self.depth_eps, self.min_cos,
+                                  self.a_min, self.delta))
+        return torch.cat(out)
+
+    def add_grads(self, rows, gR, gT):
+        """gR [F,3,3], gT [F,3] (float64) += weight / n_active * rows[2:14] / max(sum om, TINY) at the active frames.  No host read."""
+        n = rows.shape[0]
+        scale = (self.weight / n) / rows[:, 1].clamp(min=TINY)
+        gR[self.active_idx] += rows[:, 2:11].reshape(n, 3, 3) * scale[:, None, None]
+        gT[self.active_idx] += rows[:, 11:14] * scale[:, None]
+
+    def stats(self, rows):
+        """(L_photo, the stats' extra keys) of the rows of sums() on the CPU."""
+        loss = float((rows[:, 0] / rows[:, 1].clamp(min=TINY)).mean())
+        return loss, {"loss_photo": loss, "photo_pairs": [int(x) for x in rows[:, 14].round().tolist()],
+                      "photo_inliers": float(rows[:, 15].sum() / rows[:, 14].sum().clamp(min=1.0))}
+
+    def settings(self) -> dict:
+        return {"points": int(self.pts.shape[0]), "levels": list(self.levels), "lw_photo": self.weight, "delta": self.delta,
+                "a_min": self.a_min, "min_cos": self.min_cos, "depth_eps": self.depth_eps}
 
 
 def make_term(verts, faces, dataset, n_points=DEFAULTS["points"], seed=DEFAULTS["seed"], vertex_colors=None, uv=None, texture=None,

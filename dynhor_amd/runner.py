@@ -1276,10 +1276,9 @@ class Runner:
             for st in res["curve"]:
                 for k in ("loss", "loss_sil", "loss_smooth", "iou_mean", "iou_min", "sigma"):
                     board.add_scalar("pose_sil/" + k, float(st[k]), int(st["iter"]))
-                if "loss_photo" in st:
-                    board.add_scalar("pose/loss_photo", float(st["loss_photo"]), int(st["iter"]))
-                if "loss_corr" in st:
-                    board.add_scalar("pose/loss_corr", float(st["loss_corr"]), int(st["iter"]))
+                for k in st:                                        # the optional terms' losses, in the order they were added
+                    if k.startswith("loss_") and k not in ("loss_sil", "loss_smooth"):
+                        board.add_scalar("pose/" + k, float(st[k]), int(st["iter"]))
             for k in ("iou_mean_before", "iou_mean_after"):
                 if res[k] is not None:
                     board.add_scalar("pose_sil/" + k, float(res[k]), self.iter_step)

@@ -206,7 +206,7 @@ def test_the_step_source_reads_nothing_back():
     from dynhor_amd import pose_corr, pose_sil
     from tests.test_cpu_no_host_sync import FORBIDDEN
     for fn in (pose_sil.SilhouettePoseOptimizer.step, pose_sil.SilhouettePoseOptimizer.evaluate, pose_corr.corr_sums, pose_corr.frame_grads,
-               pose_corr.CorrespondenceTerm.sums, pose_corr.CorrespondenceTerm.grads):
+               pose_corr.CorrespondenceTerm.sums, pose_corr.CorrespondenceTerm.grads, pose_corr.CorrespondenceTerm.add_grads):
         src = re.sub(r'"""[\s\S]*?"""', "", inspect.getsource(fn))
         src = "\n".join(ln.split("#")[0] for ln in src.splitlines())
         for pat in FORBIDDEN:

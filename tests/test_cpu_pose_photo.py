@@ -271,7 +271,7 @@ def test_the_step_source_reads_nothing_back():
     import re
     from dynhor_amd import pose_photo, pose_sil
     from tests.test_cpu_no_host_sync import FORBIDDEN
-    for fn in (pose_photo.photo_sums, pose_photo.PhotometricTerm.sums, pose_sil.SilhouettePoseOptimizer.step,
+    for fn in (pose_photo.photo_sums, pose_photo.PhotometricTerm.sums, pose_photo.PhotometricTerm.add_grads, pose_sil.SilhouettePoseOptimizer.step,
                pose_sil.SilhouettePoseOptimizer.evaluate):
         src = re.sub(r'"""[\s\S]*?"""', "", inspect.getsource(fn))
         src = "\n".join(ln.split("#")[0] for ln in src.splitlines())
