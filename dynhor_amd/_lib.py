@@ -90,6 +90,9 @@ SIGNATURES = {
     "dh_render_scan_bwd_packed": (_i32, [_vp] * 7 + [_f32, _f32, _vp, _i64] + [_vp] * 13),
     "dh_neus_loss": (_i32, [_vp] * 6 + [_i64, _f32, _f32, _f32] + [_vp] * 6),
     "dh_corr_loss": (_i32, [_vp] * 7 + [_i32, _vp, _i64, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "dh_prior_loss_workspace": (_i64, [_i64]),
+    "dh_prior_loss": (_i32, [_vp] * 6 + [_i64, _i32, _f32, _f32, _f32, _f32, _i32] + [_vp] * 5),
+    "dh_prior_loss_packed": (_i32, [_vp] * 6 + [_i64, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _i32] + [_vp] * 5),
     "dh_nearest_sqdist_workspace": (_i64, [_i64, _i64]),
     "dh_nearest_sqdist": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "dh_mesh_sdf_record_floats": (_i32, []),

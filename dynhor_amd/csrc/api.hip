@@ -451,6 +451,54 @@ int dh_corr_loss(const float* rays_o, const float* rays_d, const float* z, const
                             stats, residual_px, d_weights, pose_adjoints, static_cast<hipStream_t>(stream));
 }
 
+int64_t dh_prior_loss_workspace(int64_t B) {
+    if (B < 0) return DH_ERR_BAD_ARG;
+    return prior_loss_workspace(B);
+}
+
+namespace {
+// the checks the two forms of dh_prior_loss share; DH_OK + *run = false for the no-op
+int prior_args(const float* rays, const float* R, const float* samples, const float* weights, const float* prior, int64_t B,
+               float depth_weight, float depth_delta, float normal_weight, const float* stats, const float* d_weights, const void* ws,
+               bool* run) {
+    *run = false;
+    if (B < 0 || !(depth_delta > 0.f) || !(depth_weight >= 0.f) || !(normal_weight >= 0.f)) return DH_ERR_BAD_ARG;   // NaN fails too
+    if (B == 0) return DH_OK;
+    if (!rays || !R || !stats || !ws || misaligned16(ws)) return DH_ERR_BAD_ARG;
+    if (prior && (!samples || !weights || !d_weights)) return DH_ERR_BAD_ARG;
+    *run = true;
+    return DH_OK;
+}
+}  // namespace
+
+int dh_prior_loss(const float* rays, const float* R, const float* z, const float* weights, const float* normal_map,
+                  const float* prior_depth, int64_t B, int n, float sample_dist, float depth_weight, float depth_delta,
+                  float normal_weight, int accumulate, float* stats, float* d_weights, float* d_normal_map, void* ws, void* stream) {
+    if (n < 1) return DH_ERR_BAD_ARG;
+    bool run;
+    const int rc = prior_args(rays, R, z, weights, prior_depth, B, depth_weight, depth_delta, normal_weight, stats, d_weights, ws, &run);
+    if (rc != DH_OK || !run) return rc;
+    return launch_prior_loss(rays, R, z, weights, normal_map, prior_depth, B, n, nullptr, nullptr, n, sample_dist, depth_weight,
+                             depth_delta, normal_weight, accumulate, stats, d_weights, d_normal_map, ws,
+                             static_cast<hipStream_t>(stream));
+}
+
+int dh_prior_loss_packed(const float* rays, const float* R, const float* t_start, const float* weights, const float* normal_map,
+                         const float* prior_depth, int64_t B, const int64_t* seg_off, const int32_t* seg_cnt, int max_samples,
+                         float step, float depth_weight, float depth_delta, float normal_weight, int accumulate, float* stats,
+                         float* d_weights, float* d_normal_map, void* ws, void* stream) {
+    if (max_samples < 0) return DH_ERR_BAD_ARG;
+    if (max_samples > 1024) return DH_ERR_UNSUPPORTED;
+    bool run;
+    const int rc = prior_args(rays, R, t_start, weights, prior_depth, B, depth_weight, depth_delta, normal_weight, stats, d_weights, ws,
+                              &run);
+    if (rc != DH_OK || !run) return rc;
+    if (!seg_off || !seg_cnt) return DH_ERR_BAD_ARG;
+    return launch_prior_loss(rays, R, t_start, weights, normal_map, prior_depth, B, 0, seg_off, seg_cnt, max_samples, step, depth_weight,
+                             depth_delta, normal_weight, accumulate, stats, d_weights, d_normal_map, ws,
+                             static_cast<hipStream_t>(stream));
+}
+
 int64_t dh_hashgrid_entries(void) { return hashgrid_entries(); }
 
 int dh_hashgrid_level(int level, float* scale, uint32_t* resolution, uint32_t* offset, uint32_t* dense) {

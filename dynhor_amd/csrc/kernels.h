@@ -203,6 +203,12 @@ int launch_icp_moments(const float* src, const float* tgt, const float* nrm, con
 
 // the last step of a reproducible fp64 sum (sums64.h; the kernel lives in icp.hip): out[g, k] = the `blocks` partials [K] (K <= 64) of
 // each of `groups` groups added in block order
+// depth / masked normal priors of the training step (prior_loss.hip); seg_off == nullptr: dense rays [B,n]
+int64_t prior_loss_workspace(int64_t B);
+int launch_prior_loss(const float* rays, const float* R, const float* z, const float* weights, const float* nmap, const float* prior,
+                      int64_t B, int n, const int64_t* seg_off, const int32_t* seg_cnt, int max_samples, float sample_dist,
+                      float depth_w, float delta, float normal_w, int accumulate, float* stats, float* d_weights, float* d_nmap,
+                      void* ws, hipStream_t st);
 int launch_sum64_reduce(const double* partial, int64_t groups, int blocks, int K, double* out, hipStream_t st);
 
 // mesh cleaning (mesh_clean.hip): label dilation, silhouette votes per vertex, connected components by union-find

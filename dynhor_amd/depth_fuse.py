@@ -139,25 +139,35 @@ def map_weights(depth, normal_enc, Kinv, mode="cos", floor_weight=DEPTH_FUSE_DEF
     return torch.where(torch.isfinite(depth), w, torch.zeros_like(w))
 
 
-def read_maps(mvs_dir, stems, H, W):
-    """(depth f32 [F,H,W] with inf where there is none, normal u8 [F,H,W,3] with 128 where there is none, present: [F] bool) of
-    mvs_depth's depth/<stem>.npy and monocular_normal/<stem>.png, on the CPU.  A frame without a depth file is all inf; one without a
-    normal file is all 128; a map of another shape raises ValueError."""
+def read_depth_maps(depth_dir, stems, H, W, who="fuse_depth"):
+    """(depth f32 [F,H,W] with inf where there is none, present: [F] bool) of a folder of <stem>.npy, on the CPU.  A frame without a
+    file is all inf, a value that is not finite becomes inf, a map of another shape raises ValueError and names the file."""
     import numpy as np
-    F = len(stems)
-    depth = torch.full((F, H, W), float("inf"), dtype=torch.float32)
-    normal = torch.full((F, H, W, 3), 128, dtype=torch.uint8)
+    depth = torch.full((len(stems), H, W), float("inf"), dtype=torch.float32)
     present = []
     for f, stem in enumerate(stems):
-        p = os.path.join(mvs_dir, "depth", str(stem) + ".npy")
+        p = os.path.join(depth_dir, str(stem) + ".npy")
         present.append(os.path.exists(p))
         if not present[-1]:
             continue
         z = np.load(p)
         if z.shape != (H, W):
-            raise ValueError(f"fuse_depth: {p} holds a map of shape {tuple(z.shape)}, the frames are {H} x {W}")
+            raise ValueError(f"{who}: {p} holds a map of shape {tuple(z.shape)}, the frames are {H} x {W}")
         z = torch.from_numpy(z.astype(np.float32))
         depth[f] = torch.where(torch.isfinite(z), z, torch.full_like(z, float("inf")))
+    return depth, present
+
+
+def read_maps(mvs_dir, stems, H, W):
+    """(depth f32 [F,H,W] with inf where there is none, normal u8 [F,H,W,3] with 128 where there is none, present: [F] bool) of
+    mvs_depth's depth/<stem>.npy and monocular_normal/<stem>.png, on the CPU.  A frame without a depth file is all inf; one without a
+    normal file is all 128; a map of another shape raises ValueError."""
+    import numpy as np
+    depth, present = read_depth_maps(os.path.join(mvs_dir, "depth"), stems, H, W)
+    normal = torch.full((len(stems), H, W, 3), 128, dtype=torch.uint8)
+    for f, stem in enumerate(stems):
+        if not present[f]:
+            continue
         p = os.path.join(mvs_dir, "monocular_normal", str(stem) + ".png")
         if os.path.exists(p):
             from PIL import Image

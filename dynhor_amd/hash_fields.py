@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from . import _lib
 from .fields import ParamStore, SingleVarianceNetwork, _WNLinearParams
-from .renderer import NeuSRenderer, _p
+from .renderer import NeuSRenderer, _p, add_prior_stats, prior_loss
 
 import ctypes as _ct
 _NULLP = _ct.c_void_p(0)
@@ -308,7 +308,7 @@ class HashNeuSRenderer(NeuSRenderer):
             z = lambda *shape, dt=torch.float32: torch.zeros(*shape, dtype=dt, device=dev)
             buf = SimpleNamespace(B=B, cap=cap, cnt_raw=z(B, dt=torch.int32), t_start=z(cap), pts=z(cap, 3), dirs=z(cap, 3),
                                   ray_idx=z(cap, dt=torch.int32), sdf=z(cap), normals=z(cap, 3), colors=z(cap, 3), feat=z(cap, 13),
-                                  weights=z(cap), cdf=z(cap), inside=z(cap), d_sdf=z(cap), d_normals=z(cap, 3), d_colors=z(cap, 3),
+                                  weights=z(cap), cdf=z(cap), inside=z(cap), d_sdf=z(cap), d_normals=z(cap, 3), d_colors=z(cap, 3), d_weights=z(cap),
                                   d_feat=z(cap, 13), caps=torch.tensor(self._cap_ladder, dtype=torch.int32, device=dev))
             self._packed_buf[role] = buf
         return buf
@@ -385,7 +385,7 @@ class HashNeuSRenderer(NeuSRenderer):
         return s
 
     @torch.no_grad()
-    def _backward_packed(self, s, d_color, d_wsum, d_nmap, eik_coef):
+    def _backward_packed(self, s, d_color, d_wsum, d_nmap, eik_coef, d_weights=None):
         L, T, st = _lib.lib(), self.timer, self.store
         if s.ws_token != self._ws_token:
             raise RuntimeError("workspace was overwritten by a later render before backward()")
@@ -395,7 +395,7 @@ class HashNeuSRenderer(NeuSRenderer):
         d_inv_s = torch.empty(B, device=dev)
         _lib.check(L.dh_render_scan_bwd_packed(_p(s.rays_o), _p(s.rays_d), _p(m.t_start), _p(s.sdf), _p(s.normals), _p(s.colors),
                                                _p(s.inv_s), s.car, m.step, _p(s.bg), B, _p(m.off), _p(m.cnt), _p(d_color),
-                                               _p(d_wsum), _NULLP, _NULLP, _p(d_nmap), _p(eik_coef), _p(d_sdf), _p(d_normals),
+                                               _p(d_wsum), _p(d_weights), _NULLP, _p(d_nmap), _p(eik_coef), _p(d_sdf), _p(d_normals),
                                                _p(d_colors), _p(d_inv_s), _lib.stream()))
         grad = st.grad_bucket()
         T("hash_color_backward", L.dh_hash_color_backward, _p(st.packed), _p(s.feat), _p(s.normals), _p(m.dirs), _p(d_colors),
@@ -412,11 +412,18 @@ class HashNeuSRenderer(NeuSRenderer):
     @torch.no_grad()
     def train_step_core(self, rays, near, far, R, cos_anneal_ratio, igr_weight=0.1, mask_weight=0.1, normal_weight=0.0,
                         background_rgb=None, t_rand=None, **kw):
+        """The parent's step on the hierarchical sampler; on the occupancy-grid sampler the packed one, with the priors of
+        dh_prior_loss_packed (prior_depth, depth_weight, depth_delta, normal_skip_missing as the parent takes them)."""
         if self.sampler != "occgrid":
             return super().train_step_core(rays, near, far, R, cos_anneal_ratio, igr_weight, mask_weight, normal_weight,
                                            background_rgb=background_rgb, t_rand=t_rand, **kw)
         if kw.get("corr") is not None or kw.get("ray_grads"):
             raise ValueError("the correspondence term / pose refinement run on the hierarchical sampler")
+        prior_depth, depth_weight = kw.get("prior_depth"), float(kw.get("depth_weight", 0.0))
+        if depth_weight > 0.0 and prior_depth is None:
+            raise ValueError("train_step_core: depth_weight > 0 needs prior_depth [B]")
+        use_depth = depth_weight > 0.0
+        masked_normal = bool(kw.get("normal_skip_missing", False)) and normal_weight > 0.0
         L = _lib.lib()
         dev = rays.device
         B = rays.shape[0]
@@ -439,9 +446,18 @@ class HashNeuSRenderer(NeuSRenderer):
         eik_coef = torch.empty(1, device=dev)
         Rc = R.contiguous().float() if R is not None else None
         _lib.check(L.dh_neus_loss(_p(s.color), _p(s.wsum), _p(s.nmap), _p(s.eik), _p(rays), _p(Rc), B, float(igr_weight),
-                                  float(mask_weight), float(normal_weight), _p(stats), _p(d_color), _p(d_wsum), _p(d_nmap),
-                                  _p(eik_coef), _lib.stream()))
-        self._backward_packed(s, d_color, d_wsum, d_nmap, eik_coef)
+                                  float(mask_weight), 0.0 if masked_normal else float(normal_weight), _p(stats), _p(d_color),
+                                  _p(d_wsum), _p(d_nmap), _p(eik_coef), _lib.stream()))
+        d_weights = None
+        if use_depth or masked_normal:
+            if use_depth:
+                d_weights = m.buf.d_weights
+            self.last_prior_stats = prior_loss(rays, Rc, m.t_start, s.weights, s.nmap if masked_normal else None,
+                                               prior_depth if use_depth else None, m.step, depth_weight, kw.get("depth_delta", 0.02),
+                                               normal_weight if masked_normal else 0.0, False, d_weights,
+                                               d_nmap if masked_normal else None, packed=(m.off, m.cnt, self._cap_ladder[0]))
+            add_prior_stats(stats, self.last_prior_stats, use_depth, masked_normal)
+        self._backward_packed(s, d_color, d_wsum, d_nmap, eik_coef, d_weights)
         self.last_state = s
         self._last_march = m
         return stats

@@ -101,6 +101,37 @@ class _RenderCoreFn(torch.autograd.Function):
                                                            for p, off, cnt in r.store.slices)
 
 
+@torch.no_grad()
+def prior_loss(rays, R, z, weights, nmap, prior_depth, sample_dist, depth_weight, depth_delta, normal_weight, accumulate, d_weights,
+               d_nmap, packed=None):
+    """dh_prior_loss (packed = (seg_off, seg_cnt, max_samples): dh_prior_loss_packed, z = t_start, sample_dist = step): stats [8] on
+    the device = L_d, sum v, mean |e|, depth_weight L_d, masked normal loss, its ray count, normal_weight * it, 0.  Writes (or, with
+    accumulate, adds to) d_weights and writes d_nmap; no host read."""
+    L = _lib.lib()
+    B = rays.shape[0]
+    stats = torch.empty(8, device=rays.device)
+    ws = torch.empty(max(16, int(L.dh_prior_loss_workspace(B))), dtype=torch.uint8, device=rays.device)
+    pd = None if prior_depth is None else prior_depth.contiguous().float()
+    tail = (float(depth_weight), float(depth_delta), float(normal_weight), 1 if accumulate else 0, _p(stats), _p(d_weights), _p(d_nmap),
+            _p(ws), _lib.stream())
+    if packed is None:
+        _lib.check(L.dh_prior_loss(_p(rays), _p(R), _p(z), _p(weights), _p(nmap), _p(pd), B, int(z.shape[1]), float(sample_dist), *tail))
+    else:
+        off, cnt, max_samples = packed
+        _lib.check(L.dh_prior_loss_packed(_p(rays), _p(R), _p(z), _p(weights), _p(nmap), _p(pd), B, _p(off), _p(cnt), int(max_samples),
+                                          float(sample_dist), *tail))
+    return stats
+
+
+def add_prior_stats(stats, pstats, use_depth, masked_normal):
+    """Fold dh_prior_loss's weighted terms into dh_neus_loss's stats [8]: the total, and the normal loss the masked term replaces."""
+    if use_depth:
+        stats[0] += pstats[3]
+    if masked_normal:
+        stats[0] += pstats[6]
+        stats[4] = pstats[4]
+
+
 class NeuSRenderer:
     def __init__(self, nerf, sdf_network: SDFNetwork, deviation_network: SingleVarianceNetwork,
                  color_network: RenderingNetwork, n_samples, n_importance, n_outside, up_sample_steps, perturb,
@@ -438,7 +469,7 @@ class NeuSRenderer:
     @torch.no_grad()
     def train_step_core(self, rays, near, far, R, cos_anneal_ratio, igr_weight=0.1, mask_weight=0.1, normal_weight=0.0,
                         background_rgb=None, t_rand=None, corr=None, corr_weight=0.0, corr_frames=None, corr_delta_px=4.0,
-                        ray_grads=False):
+                        ray_grads=False, prior_depth=None, depth_weight=0.0, depth_delta=0.02, normal_skip_missing=False):
         """rays [B,14] (dh_gen_rays layout), R [3,3] object->camera of the frame.  Returns stats [8] on device:
         loss, colour, eikonal, mask, normal, psnr, sum(obj*keep), sum(keep); leaves the flat gradient in
         store.grad_flat.  No host synchronisation.
@@ -448,10 +479,20 @@ class NeuSRenderer:
         ray_grads (pose refinement): additionally leaves d loss / d rays_o, d loss / d rays_d [B,3] (sample depths constant)
         and the normal loss's direct gradient w.r.t. R in self.last_ray_grads = (d_rays_o, d_rays_d, d_R or None); with the
         correspondence term active as well, self.last_partner_pose_grads = (d_R_all [F,3,3], d_T_all [F,3]) holds its gradient
-        w.r.t. the partner frames' poses (None otherwise)."""
+        w.r.t. the partner frames' poses (None otherwise).
+        Priors with a validity (dh_prior_loss, DESIGN_NEXT_ROWS.md section 27): prior_depth [B] (camera z, inf = none) with
+        depth_weight > 0 adds depth_weight * the Huber depth term on the expected depth; normal_skip_missing (with normal_weight > 0)
+        takes the normal term over the rays that HAVE a monocular normal: dh_neus_loss then runs at normal weight 0 and the masked
+        term supplies d_nmap and stats[4].  Either leaves self.last_prior_stats [8]; neither launches anything when off.  The depth
+        term needs no adjoint of its own under ray_grads: c_z = (R d)_z is the z of the camera-frame direction K^-1 (u, v, 1),
+        which no pose enters, and the sample depths are constants there already, so all of it flows through d_weights."""
         L = _lib.lib()
         dev = rays.device
         B = rays.shape[0]
+        if depth_weight > 0.0 and prior_depth is None:
+            raise ValueError("train_step_core: depth_weight > 0 needs prior_depth [B]")
+        use_depth = depth_weight > 0.0
+        masked_normal = bool(normal_skip_missing) and normal_weight > 0.0
         rays_o = rays[:, 0:3].contiguous()
         rays_d = rays[:, 3:6].contiguous()
         z_vals = self.sample_z(rays_o, rays_d, near, far, t_rand=t_rand)
@@ -464,8 +505,8 @@ class NeuSRenderer:
         eik_coef = torch.empty(1, device=dev)
         Rc = R.contiguous().float() if R is not None else None
         _lib.check(L.dh_neus_loss(_p(s.color), _p(s.wsum), _p(s.nmap), _p(s.eik), _p(rays), _p(Rc), B, float(igr_weight),
-                                  float(mask_weight), float(normal_weight), _p(stats), _p(d_color), _p(d_wsum),
-                                  _p(d_nmap), _p(eik_coef), _lib.stream()))
+                                  float(mask_weight), 0.0 if masked_normal else float(normal_weight), _p(stats), _p(d_color),
+                                  _p(d_wsum), _p(d_nmap), _p(eik_coef), _lib.stream()))
         d_weights = None
         if corr is not None and corr_weight > 0.0:
             R_all, T_all, K = corr_frames
@@ -479,6 +520,15 @@ class NeuSRenderer:
                                       _p(d_weights), _p(pose_adj), _lib.stream()))
             stats[0] += cstats[3]
             self.last_corr_stats, self.last_corr_residual_px = cstats, resid
+        if use_depth or masked_normal:
+            stacked = d_weights is not None
+            if use_depth and not stacked:
+                d_weights = torch.empty(B, s.n, device=dev)
+            self.last_prior_stats = prior_loss(rays, Rc, z_vals, s.weights, s.nmap if masked_normal else None,
+                                               prior_depth if use_depth else None, s.sample_dist, depth_weight if use_depth else 0.0,
+                                               depth_delta, normal_weight if masked_normal else 0.0, stacked,
+                                               d_weights if use_depth else None, d_nmap if masked_normal else None)
+            add_prior_stats(stats, self.last_prior_stats, use_depth, masked_normal)
         self._backward_core(s, d_color, d_wsum, d_weights, None, d_nmap, eik_coef, persistent=True)
         self.last_state = s
         if ray_grads:

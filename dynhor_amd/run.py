@@ -169,6 +169,10 @@ def build_parser():
                     help="fuse_depth: grid points per axis, at most 512 (default: the config's depth_fuse.resolution, else 128)")
     ap.add_argument("--fuse_trunc_cells", type=float, default=None,
                     help="fuse_depth: the truncation distance in cells of the grid (default: the config's depth_fuse.trunc_cells, else 4)")
+    ap.add_argument("--prior_dir", type=str, default=None,
+                    help="train: a folder in mvs_depth's layout; sets data_info.depth to its depth/ and data_info.monocular_normal to its "
+                         "monocular_normal/ (auto: the newest <exp>/mvs/*/).  The terms themselves are train.depth_weight and "
+                         "train.normal_weight with train.normal_skip_missing")
     return ap
 
 
@@ -196,7 +200,7 @@ def main():
 
     from .runner import Runner
     runner = Runner(conf_path=args.config_path, mode=args.mode, is_continue=args.is_continue,
-                    device=f"cuda:{local_rank}", exp_root=args.exp_root)
+                    device=f"cuda:{local_rank}", exp_root=args.exp_root, prior_dir=args.prior_dir)
     if args.mode == "train":
         runner.train(args.iters)
         if runner.rank == 0:

@@ -31,7 +31,7 @@ from .pose_photo import DEFAULTS as POSE_PHOTO_DEFAULTS
 from .pose_sil import DEFAULTS as POSE_SIL_DEFAULTS
 from .renderer import NeuSRenderer
 from .sdf_init import SDF_INIT_DEFAULTS
-from .settings import int_in, is_int, merge, one_of
+from .settings import PRIOR_DEFAULTS, int_in, is_int, merge, one_of, prior_settings
 
 DEFAULT_CONF = {
     "seq_name": "synthetic", "exp_name": "neus",
@@ -47,6 +47,9 @@ DEFAULT_CONF = {
               "roctx": False,
               # full loss stack (BASELINE.json configs[4]): dense-correspondence reprojection term, DESIGN.md section 9
               "corr_weight": 0.0, "corr_fraction": 0.25, "corr_delta_px": 4.0, "corr_vote_freq": 0, "corr_vote_tau_px": 8.0,
+              # priors with a validity (dh_prior_loss, DESIGN_NEXT_ROWS.md section 27; settings.PRIOR_DEFAULTS): the depth term reads
+              # data_info.depth; normal_skip_missing takes the normal term over the pixels that have a normal.  First settings, not tuned
+              **PRIOR_DEFAULTS,
               # per-frame pose refinement: 6-D rotation + translation per frame, rotation at 10x lr
               "refine_poses": False, "pose_lr": 1e-4, "pose_rot_lr_mult": 10.0, "pose_start_iter": 0},
     # family "neus": the 8x256 / 4x256 fp32 MLPs (BASELINE.json configs[1]); "hash": hash-grid + shallow MLPs (configs[3])
@@ -133,9 +136,20 @@ def _merge(base, over):
     return out
 
 
+def _newest_mvs_dir(base_exp_dir, who):
+    """The newest <exp>/mvs/*/ that holds a depth/ folder (fuse_depth's default, --prior_dir auto)."""
+    root = os.path.join(base_exp_dir, "mvs")
+    runs = sorted(d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d, "depth"))) if os.path.isdir(root) else []
+    if not runs:
+        raise ValueError(f"{who}: no depth maps under {root}: run --mode mvs_depth first, or give --mvs_dir")
+    return os.path.join(root, runs[-1])
+
+
 class Runner:
     def __init__(self, conf_path=None, mode="train", case=None, is_continue=False, conf: dict | None = None,
-                 dataset: Dataset | None = None, device=None, exp_root="exps"):
+                 dataset: Dataset | None = None, device=None, exp_root="exps", prior_dir=None):
+        """prior_dir: a folder in mvs_depth's layout -- sets data_info.depth to <prior_dir>/depth and data_info.monocular_normal to
+        <prior_dir>/monocular_normal; "auto": the newest <exp>/mvs/*/, as fuse_depth finds it."""
         if conf is None:
             with open(conf_path, "r") as f:
                 conf = yaml.safe_load(f)
@@ -163,7 +177,16 @@ class Runner:
         self.use_white_bkgd = tr["use_white_bkgd"]; self.keep_only = tr["keep_only"]
         self.corr_weight = tr["corr_weight"]; self.corr_fraction = tr["corr_fraction"]; self.corr_delta_px = tr["corr_delta_px"]
         self.corr_vote_freq = tr["corr_vote_freq"]; self.corr_vote_tau_px = tr["corr_vote_tau_px"]
+        pr = prior_settings(tr)
+        self.depth_weight, self.depth_delta, self.depth_start_iter = pr["depth_weight"], pr["depth_delta"], pr["depth_start_iter"]
+        self.normal_skip_missing = pr["normal_skip_missing"]
         self.iter_step = 0
+        if prior_dir is not None:
+            d = _newest_mvs_dir(self.base_exp_dir, "--prior_dir auto") if prior_dir == "auto" else str(prior_dir)
+            if not os.path.isdir(os.path.join(d, "depth")):
+                raise ValueError(f"--prior_dir: {d} holds no depth/ folder: run --mode mvs_depth first, or give its folder")
+            self.conf["data_info"] = dict(self.conf["data_info"], depth=os.path.join(d, "depth"),
+                                          monocular_normal=os.path.join(d, "monocular_normal"))
 
         if dataset is None:
             di = self.conf["data_info"]
@@ -173,6 +196,9 @@ class Runner:
             else:
                 dataset = Dataset.from_synthetic(device=self.device, **di["synthetic"])
         self.dataset = dataset
+        if self.depth_weight > 0.0 and self.dataset.depth is None:
+            raise ValueError("train.depth_weight > 0 needs depth maps: point data_info.depth at a folder of <stem>.npy (mvs_depth "
+                             "writes one: --prior_dir), or put them under <dataroot>/depth")
 
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(tr["seed"])          # identical initial weights on every rank
@@ -284,11 +310,18 @@ class Runner:
         bg = torch.ones(3, device=self.device) if self.use_white_bkgd else None
         # the per-ray perturbation of the coarse samples comes from the SAME checkpointed stream as the pixels
         t_rand = torch.rand([rays.shape[0], 1], device=self.device, generator=self.ray_gen) if self.renderer.perturb > 0 else None
+        prior = {}
+        if self.depth_weight > 0.0 and self.iter_step >= self.depth_start_iter:
+            prior.update(prior_depth=self.dataset.prior_depth_at(frame, *self.dataset._last_pixels), depth_weight=self.depth_weight,
+                         depth_delta=self.depth_delta)
+        if self.normal_skip_missing:
+            prior["normal_skip_missing"] = True
         stats = self.renderer.train_step_core(rays, near, far, self.dataset.R[frame], self.get_cos_anneal_ratio(),
                                               self.igr_weight, self.mask_weight, self.normal_weight, background_rgb=bg,
                                               t_rand=t_rand, corr=corr, corr_weight=self.corr_weight,
                                               corr_frames=self.dataset.corr_frames() if corr is not None else None,
-                                              corr_delta_px=self.corr_delta_px, ray_grads=refine)
+                                              corr_delta_px=self.corr_delta_px, ray_grads=refine, **prior)
+        self._prior_on = bool(prior)
         if refine:
             # chain the per-ray adjoints into this frame's 9 pose numbers (torch autograd over the ray formula), step, and
             # write the refined pose back into the resident frame table the HIP ray gather reads
@@ -350,6 +383,10 @@ class Runner:
                **({"Loss/corr_loss": float(self.renderer.last_corr_stats[0]), "Statistics/corr_residual_px": float(self.renderer.last_corr_stats[2])}
                   if self.corr_weight > 0.0 and getattr(self.renderer, "last_corr_stats", None) is not None else {}),
                "Statistics/s_val": float(1.0 / self.store.inv_s().item()), "lr": self.current_lr()}
+        if getattr(self, "_prior_on", False) and getattr(self.renderer, "last_prior_stats", None) is not None:
+            ps = self.renderer.last_prior_stats.tolist()       # this rank's batch, as the correspondence scalars are
+            rec.update({"Loss/depth_loss": ps[0], "Statistics/depth_abs": ps[2], "Statistics/depth_rays": ps[1],
+                        "Statistics/normal_rays": ps[5]})
         st = getattr(self.renderer, "last_state", None)
         if st is not None and getattr(self, "_last_rays", None) is not None:
             # upstream Statistics/cdf and Statistics/weight_max (App. A.8), masked by obj*keep like the colour loss
@@ -1563,11 +1600,7 @@ class Runner:
         if mvs_dir is None:
             mvs_dir = self.last_mvs_dir
         if mvs_dir is None:
-            root = os.path.join(self.base_exp_dir, "mvs")
-            runs = sorted(d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d, "depth"))) if os.path.isdir(root) else []
-            if not runs:
-                raise ValueError(f"fuse_depth: no depth maps under {root}: run --mode mvs_depth first, or give --mvs_dir")
-            mvs_dir = os.path.join(root, runs[-1])
+            mvs_dir = _newest_mvs_dir(self.base_exp_dir, "fuse_depth")
         if not os.path.isdir(os.path.join(str(mvs_dir), "depth")):
             raise ValueError(f"fuse_depth: {mvs_dir} holds no depth/ folder: run --mode mvs_depth first, or give its folder as --mvs_dir")
         mvs_dir = str(mvs_dir)

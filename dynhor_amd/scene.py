@@ -119,6 +119,56 @@ def make_sequence(n_frames=64, H=512, W=512, seed=4321, device="cpu", hand=True,
 
 
 @torch.no_grad()
+def make_depth_maps(frames: dict, chunk=1 << 16, march_steps=4096, bisect_steps=48):
+    """Analytic depth maps f32 [F,H,W] of a make_sequence dict: on every object pixel (label 1) the camera z of the first zero of
+    scene_sdf along the pixel's ray, found in fp64 from the fp32 poses -- the ray o + t d of dh_gen_rays (d = R^T normalize(K^-1 (x, y,
+    1)), o = -R^T T) is marched from the radius-0.75 ball in steps of max(sdf, 1e-4) until the sign changes, the bracket is bisected,
+    and z = t (R d)_z.  inf elsewhere, and on the few silhouette pixels whose ray never reaches a zero (make_sequence's fp32 tracer
+    labels a ray that passes within 5e-4 of the surface)."""
+    lab = frames["label"]
+    dev = lab.device
+    F_, H, W = lab.shape
+    R, T = frames["R"].to(dev).double(), frames["T"].reshape(-1, 3).to(dev).double()
+    Kinv = torch.inverse(frames["K"].to(dev).double())
+    out = torch.full((F_, H, W), float("inf"), dtype=torch.float32, device=dev)
+    for fi in range(F_):
+        idx_all = (lab[fi].reshape(-1) == 1).nonzero().reshape(-1)
+        for c0 in range(0, idx_all.numel(), chunk):
+            idx = idx_all[c0:c0 + chunk]
+            pix = torch.stack([(idx % W).double(), (idx // W).double(), torch.ones_like(idx, dtype=torch.float64)], -1)
+            dcam = pix @ Kinv.T
+            dcam = dcam / torch.linalg.norm(dcam, dim=-1, keepdim=True)
+            d = dcam @ R[fi]
+            o = (-(T[fi] @ R[fi])).expand_as(d)
+            t = -(o * d).sum(-1) - 0.75
+            s = scene_sdf(o + d * t[:, None])
+            lo, hi = t.clone(), t.clone()
+            found = s <= 0.0
+            end = t + 1.5
+            for _ in range(march_steps):
+                live = ~found & (t < end)
+                if not bool(live.any()):
+                    break
+                t_new = t + s.clamp(min=1e-4)
+                s_new = scene_sdf(o + d * t_new[:, None])
+                cross = live & (s_new <= 0.0)
+                lo = torch.where(cross, t, lo)
+                hi = torch.where(cross, t_new, hi)
+                found |= cross
+                t = torch.where(live, t_new, t)
+                s = torch.where(live, s_new, s)
+            for _ in range(bisect_steps):
+                mid = 0.5 * (lo + hi)
+                neg = scene_sdf(o + d * mid[:, None]) <= 0.0
+                hi = torch.where(neg, mid, hi)
+                lo = torch.where(neg, lo, mid)
+            z = (hi * dcam[:, 2]).float()
+            flat = out[fi].view(-1)
+            flat[idx[found]] = z[found]
+    return out
+
+
+@torch.no_grad()
 def make_correspondences(frames: dict, n_per_pair=2048, offsets=(1, 2, 5), noise_px=0.5, outlier_frac=0.1, seed=99):
     """Synthetic stand-in for the reference's `correspondence_infos` (README.md:43: dense DKM matches): for every frame i and
     partner j = i + offset, pixels of i on the visible object (label 1) are sphere-traced to the analytic surface and
@@ -192,7 +242,8 @@ def write_correspondences_to_disk(matches, dataroot: str, stems=None):
 def write_sequence_to_disk(frames: dict, dataroot: str, pose_dir: str | None = None, ext: str = "png"):
     """Write a sequence in the reference's data convention (README.md:27-45; ObjTracker/run.py:74-88,165-179):
     <dataroot>/rgb/%04d.<ext>, sam_seg/%04d.png (channel 1 == 255 object, last channel == 255 hand),
-    monocular_normal/%04d.png, and <pose_dir>/%04d.npz with R[3,3], T[1,3], K[3,3]."""
+    monocular_normal/%04d.png, and <pose_dir>/%04d.npz with R[3,3], T[1,3], K[3,3]; depth/%04d.npy (f32 [H,W], inf = none) when the
+    dict holds depth maps (make_depth_maps)."""
     import os
     import numpy as np
     from PIL import Image
@@ -202,8 +253,13 @@ def write_sequence_to_disk(frames: dict, dataroot: str, pose_dir: str | None = N
     os.makedirs(pose_dir, exist_ok=True)
     rgb = frames["rgb"].cpu().numpy(); lab = frames["label"].cpu().numpy(); nrm = frames["normal"].cpu().numpy()
     R = frames["R"].cpu().numpy(); T = frames["T"].cpu().numpy(); K = frames["K"].cpu().numpy()
+    depth = None if frames.get("depth") is None else frames["depth"].cpu().numpy().astype(np.float32)
+    if depth is not None:
+        os.makedirs(os.path.join(dataroot, "depth"), exist_ok=True)
     for i in range(rgb.shape[0]):
         stem = "%04d" % i
+        if depth is not None:
+            np.save(os.path.join(dataroot, "depth", stem + ".npy"), depth[i])
         Image.fromarray(rgb[i]).save(os.path.join(dataroot, "rgb", stem + "." + ext))
         m = np.zeros(rgb[i].shape, np.uint8)
         m[..., 1][lab[i] == 1] = 255

@@ -52,3 +52,27 @@ def int_in(block, key, v, lo, hi):
 def one_of(block, key, v, choices):
     if v not in choices:
         raise ValueError(f"{block} {key} must be one of {choices}, got {v!r}")
+
+
+# train.* keys of the priors with a validity (dh_prior_loss; DESIGN_NEXT_ROWS.md section 27).  depth_weight 0 = the depth term off;
+# depth_delta = the Huber width in the dataset's depth units (0.02 = 2 % of the unit sphere's radius); depth_start_iter = the first
+# iteration with the term; normal_skip_missing = the normal term over the pixels that have a normal.  The first three are first
+# settings, not tuned.
+PRIOR_DEFAULTS = {"depth_weight": 0.0, "depth_delta": 0.02, "depth_start_iter": 0, "normal_skip_missing": False}
+
+
+def prior_settings(train: dict) -> dict:
+    """The four prior keys of a train: block, checked.  The block holds every other training key too, so only a key that reads as one of
+    these -- it starts with depth_ or normal_skip -- and is not one is rejected as unknown."""
+    unknown = sorted(k for k in train if (k.startswith("depth_") or k.startswith("normal_skip")) and k not in PRIOR_DEFAULTS)
+    if unknown:
+        raise ValueError(f"train: unknown setting(s) {unknown}; known: {sorted(PRIOR_DEFAULTS)}")
+    pr = {k: train.get(k, v) for k, v in PRIOR_DEFAULTS.items()}
+    if not is_num(pr["depth_weight"]) or pr["depth_weight"] < 0:
+        raise ValueError(f"train depth_weight must be a number >= 0, got {pr['depth_weight']!r}")
+    if not is_num(pr["depth_delta"]) or not pr["depth_delta"] > 0:
+        raise ValueError(f"train depth_delta must be a number > 0, got {pr['depth_delta']!r}")
+    int_in("train", "depth_start_iter", pr["depth_start_iter"], 0, 2 ** 31 - 1)
+    if not isinstance(pr["normal_skip_missing"], bool):
+        raise ValueError(f"train normal_skip_missing must be true or false, got {pr['normal_skip_missing']!r}")
+    return pr

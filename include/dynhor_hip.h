@@ -305,6 +305,45 @@ int dh_render_scan_bwd_packed(const float* rays_o, const float* rays_d, const fl
                               const float* d_normal_map, const float* eik_coef, float* d_sdf, float* d_normals, float* d_colors,
                               float* d_inv_s, void* stream);
 
+/* Priors that carry a validity, on the training path: a depth term on the expected depth of a ray and the normal term of
+ * dh_neus_loss restricted to the rays that have a normal (DESIGN_NEXT_ROWS.md section 27).  dh_prior_loss takes dense rays
+ * (z, weights [B,n], sample_dist as dh_corr_loss takes them), dh_prior_loss_packed the occupancy-grid sampler's packed rays
+ * (t_start, step, seg_off, seg_cnt as dh_render_scan_bwd_packed takes them; max_samples is the caller's per-ray cap, the one
+ * dh_march_count took: a ray's samples past it are not read).  rays [B,14] as dh_gen_rays writes them (3..5 = d, 9 = obj,
+ * 10 = keep, 11..13 = the monocular normal), R [9] the frame's object->camera rotation, prior_depth [B] camera z.
+ *   depth   m_k = z_k + 0.5 (z_{k+1} - z_k), sample_dist for the last sample (dh_render_scan_fwd, dh_corr_loss); packed:
+ *           m_k = t_start_k + 0.5 step, the packed scan's own (m_k is fp32).  t^ = sum_k w_k m_k in fp64 (each lane of a wave adds
+ *           its samples lane, lane + 64, .. in ascending k with fma, then the 64 lanes fold in a fixed xor butterfly), c_z = R[6] d_0 +
+ *           R[7] d_1 + R[8] d_2, z^ = t^ c_z (dh_trace_compose's t (R d)_z: since R o + T = 0 this is the camera z of o + t^ d); c_z, e,
+ *           rho and rho' are fp64 of the fp32 inputs too -- e is what is left of two depths -- and the ray's coefficient rho'(e) c_z is
+ *           rounded to fp32.
+ *           v = [obj * keep > 0] [1e-3 < prior < inf] (inf, NaN and values <= 1e-3 mean "no prior"); packed: and the ray has a sample.
+ *           e = z^ - prior, rho = e^2 / (2 delta) if |e| <= delta else |e| - delta / 2 (dh_corr_loss's Huber form, slope 1 outside),
+ *           L_d = sum v rho / (sum v + 1e-5).
+ *           d_weights[b,k] = depth_weight v rho'(e) c_z / (sum v + 1e-5) m_k.  accumulate == 0: written for every sample of every
+ *           ray, exact zeros where v = 0.  accumulate != 0: added to what the buffer holds (stack it on dh_corr_loss's output);
+ *           rays whose coefficient is 0 are not touched, so depth_weight 0 leaves the buffer's bits as they are.
+ *   normal  (normal_map not null) dh_neus_loss's L1 + (1 - cos) between normalize(R normal_map) and the monocular normal,
+ *           operation by operation, with the weight q = obj keep [mono_0^2 + mono_1^2 + mono_2^2 >= 0.25] (grey 128 decodes to a
+ *           squared norm of 4.6e-5, an encoded unit normal to at least (1 - sqrt(3)/255)^2) and the normaliser sum q + 1e-5.
+ *           d_normal_map [B,3] (normal_weight > 0 and not null; untouched otherwise) is written for every ray, exact zeros where q = 0.
+ * stats[8] = L_d, sum v, sum v |e| / (sum v + 1e-5), depth_weight L_d, the masked normal loss, sum q (its ray count),
+ * normal_weight * that loss, 0.  The first three and [4], [5] do not depend on the weights: at weight 0 the call scores a ray set.
+ * The batch sums are fp64 sums of the per-ray fp32 values in a fixed order (no atomics): a result is bitwise reproducible.
+ * prior_depth null = no ray has a prior (z, weights, d_weights are then not read or written).  ws: dh_prior_loss_workspace(B)
+ * bytes, 16-byte aligned.  B == 0 is a no-op; DH_ERR_BAD_ARG for a null pointer, a negative count, n < 1, depth_delta not > 0, a
+ * weight that is negative or NaN; DH_ERR_UNSUPPORTED for max_samples > 1024 (seg_cnt lives on the device and is clamped to it).
+ * Limits: t^ is NOT divided by sum_k w_k (MonoSDF and dh_corr_loss do the same): a ray whose weights sum to less than 1 reads
+ * nearer than its surface. */
+int64_t dh_prior_loss_workspace(int64_t B);
+int dh_prior_loss(const float* rays, const float* R, const float* z, const float* weights, const float* normal_map,
+                  const float* prior_depth, int64_t B, int n, float sample_dist, float depth_weight, float depth_delta,
+                  float normal_weight, int accumulate, float* stats, float* d_weights, float* d_normal_map, void* ws, void* stream);
+int dh_prior_loss_packed(const float* rays, const float* R, const float* t_start, const float* weights, const float* normal_map,
+                         const float* prior_depth, int64_t B, const int64_t* seg_off, const int32_t* seg_cnt, int max_samples,
+                         float step, float depth_weight, float depth_delta, float normal_weight, int accumulate, float* stats,
+                         float* d_weights, float* d_normal_map, void* ws, void* stream);
+
 /* ---- optimiser -----------------------------------------------------------------------------------------
  * torch.optim.Adam step (upstream Runner uses Adam, App. A.8; the reference's own optimisers are Adam too:
  * ObjTracker/pose_initializtion.py:346, jointopt.py:135-141) fused over the flat vector; step counts from 1;
