@@ -19,10 +19,7 @@ import torch.nn as nn
 
 from . import _lib
 from .fields import ParamStore, SingleVarianceNetwork, _WNLinearParams
-from .renderer import NeuSRenderer, _p, add_prior_stats, prior_loss
-
-import ctypes as _ct
-_NULLP = _ct.c_void_p(0)
+from .renderer import NeuSRenderer, _p
 
 
 class HashGridTable(nn.Module):
@@ -232,14 +229,16 @@ class HashNeuSRenderer(NeuSRenderer):
         self.timer(tag, _lib.lib().dh_hash_sdf_nograd, _p(st.flat), _p(st.packed), _p(pts), n, self.radius, _p(out),
                    _lib.stream())
 
+    _net_outputs = NeuSRenderer._net_outputs + (("feat", (13,)),)
+
     def _net_forward(self, s, packed):
-        L, T, st = _lib.lib(), self.timer, self.store
-        P = s.B * s.n
-        s.feat = torch.empty(P, 13, device=s.pts.device)
+        """The parent's contract; on packed rays (net_state with n_active and buffers) s.n = 1, a direction per sample, and only the
+        first n_active points are evaluated."""
+        L, T, st, P = _lib.lib(), self.timer, self.store, s.P
         T("hash_geo_forward", L.dh_hash_geo_forward, _p(st.flat), _p(packed), _p(s.pts), P, self.radius, self.fd_eps,
-          _p(s.ws), 0 if s.infer_only else 1, _p(s.sdf), _p(s.feat), _p(s.normals), _NULLP, _lib.stream())
+          _p(s.ws), 0 if s.infer_only else 1, _p(s.sdf), _p(s.feat), _p(s.normals), _p(s.n_active), _lib.stream())
         T("hash_color_forward", L.dh_hash_color_forward, _p(packed), _p(s.feat), _p(s.normals), _p(s.rays_d), s.n, P,
-          _p(s.colors), _NULLP, _lib.stream())
+          _p(s.colors), _p(s.n_active), _lib.stream())
 
     def _weight_grads(self, P, ws, grad, n_dev):
         """dh_hash_weight_grads_parts in its two parts, CONCURRENTLY: the table scatter (bound by the memory side's atomic request rate:
@@ -270,15 +269,13 @@ class HashNeuSRenderer(NeuSRenderer):
             torch.cuda.current_stream(grad.device).wait_stream(side)
 
     def _net_backward(self, s, d_sdf, d_normals, d_colors, grad):
-        L, T, st = _lib.lib(), self.timer, self.store
-        P = s.B * s.n
-        d_feat = torch.empty(P, 13, device=s.pts.device)
+        L, T, st, P = _lib.lib(), self.timer, self.store, s.P
+        d_feat = torch.empty(P, 13, device=s.pts.device) if s.buffers is None else s.buffers.d_feat
         T("hash_color_backward", L.dh_hash_color_backward, _p(st.packed), _p(s.feat), _p(s.normals), _p(s.rays_d),
-          _p(d_colors), s.n, P, _p(s.ws), _p(d_feat), _p(d_normals), _NULLP, _lib.stream())
+          _p(d_colors), s.n, P, _p(s.ws), _p(d_feat), _p(d_normals), _p(s.n_active), _lib.stream())
         T("hash_geo_backward", L.dh_hash_geo_backward, _p(st.flat), _p(st.packed), _p(s.pts), _p(d_sdf), _p(d_feat),
-          _p(d_normals), P, self.radius, self.fd_eps, _p(s.ws), _NULLP, _lib.stream())
-        self._weight_grads(P, s.ws, grad, _NULLP)
-
+          _p(d_normals), P, self.radius, self.fd_eps, _p(s.ws), _p(s.n_active), _lib.stream())
+        self._weight_grads(P, s.ws, grad, _p(s.n_active))
 
     # ------------------------------------------------------------------ occupancy-grid marching path (packed rays)
     @torch.no_grad()
@@ -358,21 +355,14 @@ class HashNeuSRenderer(NeuSRenderer):
 
     @torch.no_grad()
     def _forward_packed(self, rays_o, rays_d, m, cos_anneal_ratio, background_rgb, want_nmap, infer_only=False):
-        from types import SimpleNamespace
-        L, T, st = _lib.lib(), self.timer, self.store
+        L, st = _lib.lib(), self.store
         packed = st.ensure_packed()
         dev = rays_o.device
-        B, P, buf = rays_o.shape[0], m.cap, m.buf
-        s = SimpleNamespace(B=B, m=m, car=float(cos_anneal_ratio), bg=background_rgb, rays_o=rays_o, rays_d=rays_d,
-                            infer_only=infer_only)
-        s.ws = self._workspace(P, infer_only)
-        self._ws_token += 1
-        s.ws_token = self._ws_token
-        s.sdf, s.normals, s.colors, s.feat = buf.sdf, buf.normals, buf.colors, buf.feat
-        T("hash_geo_forward", L.dh_hash_geo_forward, _p(st.flat), _p(packed), _p(m.pts), P, self.radius, self.fd_eps,
-          _p(s.ws), 0 if infer_only else 1, _p(s.sdf), _p(s.feat), _p(s.normals), _p(m.n_dev), _lib.stream())
-        T("hash_color_forward", L.dh_hash_color_forward, _p(packed), _p(s.feat), _p(s.normals), _p(m.dirs), 1, P,
-          _p(s.colors), _p(m.n_dev), _lib.stream())
+        B, buf = rays_o.shape[0], m.buf
+        # the network stages see the whole capacity as points with a direction each, m.n_dev of them in use, outputs in the buffers
+        s = self.net_state(m.pts, m.dirs, 1, 0 if infer_only else 1, n_active=m.n_dev, buffers=buf)
+        s.B, s.m, s.car, s.bg, s.rays_o, s.ray_dirs = B, m, float(cos_anneal_ratio), background_rgb, rays_o, rays_d      # B rays
+        self._net_forward(s, packed)
         s.inv_s = st.inv_s()
         s.weights, s.cdf, s.inside = buf.weights, buf.cdf, buf.inside
         s.color = torch.empty(B, 3, device=dev); s.wsum = torch.empty(B, 1, device=dev); s.wmax = torch.empty(B, 1, device=dev)
@@ -384,55 +374,45 @@ class HashNeuSRenderer(NeuSRenderer):
                                                _p(s.eik), _p(s.nmap), _lib.stream()))
         return s
 
+    def first_cdf(self, s):
+        if not hasattr(s, "m"):
+            return super().first_cdf(s)
+        # packed rays: cdf is the flat capacity buffer; a ray's first sample sits at its segment offset, rays without samples
+        # contribute nothing
+        return (s.cdf[s.m.off.clamp(max=s.cdf.shape[0] - 1)] * (s.m.cnt > 0)).view(-1, 1)
+
     @torch.no_grad()
     def _backward_packed(self, s, d_color, d_wsum, d_nmap, eik_coef, d_weights=None):
-        L, T, st = _lib.lib(), self.timer, self.store
-        if s.ws_token != self._ws_token:
-            raise RuntimeError("workspace was overwritten by a later render before backward()")
-        m, B, P, buf = s.m, s.B, s.m.cap, s.m.buf
-        dev = s.color.device
-        d_sdf, d_normals, d_colors, d_feat = buf.d_sdf.zero_(), buf.d_normals.zero_(), buf.d_colors.zero_(), buf.d_feat
-        d_inv_s = torch.empty(B, device=dev)
-        _lib.check(L.dh_render_scan_bwd_packed(_p(s.rays_o), _p(s.rays_d), _p(m.t_start), _p(s.sdf), _p(s.normals), _p(s.colors),
-                                               _p(s.inv_s), s.car, m.step, _p(s.bg), B, _p(m.off), _p(m.cnt), _p(d_color),
-                                               _p(d_wsum), _p(d_weights), _NULLP, _p(d_nmap), _p(eik_coef), _p(d_sdf), _p(d_normals),
-                                               _p(d_colors), _p(d_inv_s), _lib.stream()))
-        grad = st.grad_bucket()
-        T("hash_color_backward", L.dh_hash_color_backward, _p(st.packed), _p(s.feat), _p(s.normals), _p(m.dirs), _p(d_colors),
-          1, P, _p(s.ws), _p(d_feat), _p(d_normals), _p(m.n_dev), _lib.stream())
-        T("hash_geo_backward", L.dh_hash_geo_backward, _p(st.flat), _p(st.packed), _p(m.pts), _p(d_sdf), _p(d_feat),
-          _p(d_normals), P, self.radius, self.fd_eps, _p(s.ws), _p(m.n_dev), _lib.stream())
-        self._weight_grads(P, s.ws, grad, _p(m.n_dev))
-        raw = torch.exp(st.flat[st.var_off] * 10.0)
-        passthrough = ((raw >= 1e-6) & (raw <= 1e6)).float()
-        grad[st.var_off] = d_inv_s.sum() * 10.0 * raw * passthrough
-        st.grad_flat = grad
+        self._check_backward(s)
+        m, B, buf = s.m, s.B, s.buffers
+        d_sdf, d_normals, d_colors = buf.d_sdf.zero_(), buf.d_normals.zero_(), buf.d_colors.zero_()
+        d_inv_s = torch.empty(B, device=s.color.device)
+        _lib.check(_lib.lib().dh_render_scan_bwd_packed(
+            _p(s.rays_o), _p(s.ray_dirs), _p(m.t_start), _p(s.sdf), _p(s.normals), _p(s.colors), _p(s.inv_s), s.car, m.step, _p(s.bg), B,
+            _p(m.off), _p(m.cnt), _p(d_color), _p(d_wsum), _p(d_weights), _p(None), _p(d_nmap), _p(eik_coef), _p(d_sdf), _p(d_normals),
+            _p(d_colors), _p(d_inv_s), _lib.stream()))
+        grad = self.store.grad_bucket()
+        self._net_backward(s, d_sdf, d_normals, d_colors, grad)
+        self._variance_grad(d_inv_s, grad)
         return grad
 
     @torch.no_grad()
     def train_step_core(self, rays, near, far, R, cos_anneal_ratio, igr_weight=0.1, mask_weight=0.1, normal_weight=0.0,
                         background_rgb=None, t_rand=None, **kw):
-        """The parent's step on the hierarchical sampler; on the occupancy-grid sampler the packed one, with the priors of
-        dh_prior_loss_packed (prior_depth, depth_weight, depth_delta, normal_skip_missing as the parent takes them)."""
+        """The parent's step on the hierarchical sampler; on the occupancy-grid sampler the packed one: grid update, march, forward,
+        the parent's loss stage on the packed description of the samples (the priors of dh_prior_loss_packed: prior_depth,
+        depth_weight, depth_delta, normal_skip_missing as the parent takes them), backward."""
         if self.sampler != "occgrid":
             return super().train_step_core(rays, near, far, R, cos_anneal_ratio, igr_weight, mask_weight, normal_weight,
                                            background_rgb=background_rgb, t_rand=t_rand, **kw)
-        if kw.get("corr") is not None or kw.get("ray_grads"):
+        if kw.get("corr") is not None or kw.pop("ray_grads", False):
             raise ValueError("the correspondence term / pose refinement run on the hierarchical sampler")
-        prior_depth, depth_weight = kw.get("prior_depth"), float(kw.get("depth_weight", 0.0))
-        if depth_weight > 0.0 and prior_depth is None:
-            raise ValueError("train_step_core: depth_weight > 0 needs prior_depth [B]")
-        use_depth = depth_weight > 0.0
-        masked_normal = bool(kw.get("normal_skip_missing", False)) and normal_weight > 0.0
-        L = _lib.lib()
-        dev = rays.device
-        B = rays.shape[0]
         if self._march_iter % self.grid_update_every == 0:
             self.update_grid()
         self._march_iter += 1
         rays_o = rays[:, 0:3].contiguous(); rays_d = rays[:, 3:6].contiguous()
         if t_rand is None and self.perturb > 0:
-            t_rand = torch.rand(B, 1, device=dev)
+            t_rand = torch.rand(rays.shape[0], 1, device=rays.device)
         self._in_train_step = True           # _buffers: this batch size owns the never-evicted training entry
         try:
             m = self.march(rays_o, rays_d, near, far, t_rand if self.perturb > 0 else None)
@@ -440,27 +420,12 @@ class HashNeuSRenderer(NeuSRenderer):
             self._in_train_step = False
         bg = None if background_rgb is None else background_rgb.reshape(-1).contiguous().float()
         s = self._forward_packed(rays_o, rays_d, m, cos_anneal_ratio, bg, want_nmap=normal_weight > 0.0)
-        stats = torch.empty(8, device=dev)
-        d_color = torch.empty(B, 3, device=dev); d_wsum = torch.empty(B, device=dev)
-        d_nmap = torch.empty(B, 3, device=dev) if normal_weight > 0.0 else None
-        eik_coef = torch.empty(1, device=dev)
-        Rc = R.contiguous().float() if R is not None else None
-        _lib.check(L.dh_neus_loss(_p(s.color), _p(s.wsum), _p(s.nmap), _p(s.eik), _p(rays), _p(Rc), B, float(igr_weight),
-                                  float(mask_weight), 0.0 if masked_normal else float(normal_weight), _p(stats), _p(d_color),
-                                  _p(d_wsum), _p(d_nmap), _p(eik_coef), _lib.stream()))
-        d_weights = None
-        if use_depth or masked_normal:
-            if use_depth:
-                d_weights = m.buf.d_weights
-            self.last_prior_stats = prior_loss(rays, Rc, m.t_start, s.weights, s.nmap if masked_normal else None,
-                                               prior_depth if use_depth else None, m.step, depth_weight, kw.get("depth_delta", 0.02),
-                                               normal_weight if masked_normal else 0.0, False, d_weights,
-                                               d_nmap if masked_normal else None, packed=(m.off, m.cnt, self._cap_ladder[0]))
-            add_prior_stats(stats, self.last_prior_stats, use_depth, masked_normal)
-        self._backward_packed(s, d_color, d_wsum, d_nmap, eik_coef, d_weights)
+        a = self._loss_stage(s, rays, R, m.t_start, m.step, igr_weight, mask_weight, normal_weight,
+                             packed=(m.off, m.cnt, self._cap_ladder[0]), d_weights=m.buf.d_weights, **kw)
+        self._backward_packed(s, a.d_color, a.d_wsum, a.d_nmap, a.eik_coef, a.d_weights)
         self.last_state = s
         self._last_march = m
-        return stats
+        return a.stats
 
     @property
     def last_march(self):

@@ -14,8 +14,6 @@ The kernels run on the current stream; there is no CPU path.
 """
 from __future__ import annotations
 
-from types import SimpleNamespace
-
 import torch
 
 from . import _lib
@@ -23,7 +21,6 @@ from ._args import check_cams, check_faces, check_verts, device_tensor, same_dev
 from .mesh_clean import dilate_labels
 
 MODES = ("none", "views", "network", "views+network")
-NET_CHUNK = 1 << 20
 
 
 def _normals(fn, verts, faces, normals):
@@ -164,33 +161,14 @@ def bake_vertex_colors(verts, faces, dataset, erode_px: int = 1, min_cos: float 
 @torch.no_grad()
 def network_vertex_colors(renderer, verts, normals=None):
     """Colour network at every vertex f32 [V,3], viewed along -n: n = normals (unit) if given, else the normalised SDF gradient at the
-    vertex.  Runs the renderer's family hooks (_net_forward, one sample per "ray", forward-only workspace) in chunks of at most 2^20
-    points: a first pass for the gradient, a second for the colour with the direction.  Non-finite output (split_f16 range exceeded,
-    or a diverged network) raises DynhorHipError."""
+    vertex: renderer.eval_points, a first pass for the gradient (direction 0), a second for the colour with the direction.  Non-finite
+    output (split_f16 range exceeded, or a diverged network) raises DynhorHipError."""
     verts = check_verts("network_vertex_colors", verts)
-    if normals is not None:
+    if normals is None:
+        normals = torch.nn.functional.normalize(renderer.eval_points(verts, torch.zeros_like(verts), "network_vertex_colors")[0], dim=1)
+    else:
         normals = device_tensor("network_vertex_colors", "normals", normals, torch.float32, lambda s: s == tuple(verts.shape), "[V,3]")
-    dev = verts.device
-    packed = renderer.store.ensure_packed(renderer._arith())
-    out = torch.empty(verts.shape[0], 3, dtype=torch.float32, device=dev)
-    for s0 in range(0, verts.shape[0], NET_CHUNK):
-        pts = verts[s0:s0 + NET_CHUNK]
-        P = pts.shape[0]
-        s = SimpleNamespace(B=P, n=1, pts=pts, infer_only=True, ray_grads=False, ws=renderer._workspace(P, infer_only=True),
-                            sdf=torch.empty(P, device=dev), normals=torch.empty(P, 3, device=dev), colors=torch.empty(P, 3, device=dev))
-        if normals is None:
-            s.rays_d = torch.zeros(P, 3, device=dev)
-            renderer._net_forward(s, packed)
-            n = torch.nn.functional.normalize(s.normals, dim=1)
-        else:
-            n = normals[s0:s0 + P]
-        s.rays_d = (-n).contiguous()
-        renderer._net_forward(s, packed)
-        if not bool(torch.isfinite(s.colors).all()) or not bool(torch.isfinite(s.normals).all()):
-            raise _lib.DynhorHipError("network_vertex_colors: non-finite network output at the mesh vertices (split_f16 range "
-                                      "exceeded, or the network has diverged); use arithmetic 'split_bf16'")
-        out[s0:s0 + P] = s.colors
-    return out
+    return renderer.eval_points(verts, -normals, "network_vertex_colors")[1]
 
 
 def color_mesh(verts, faces, mode: str, dataset=None, renderer=None, erode_px: int = 1, min_cos: float = 0.1, depth_eps: float = 0.01,

@@ -23,6 +23,7 @@ from . import _lib
 from .fields import ParamStore, RenderingNetwork, SDFNetwork, SingleVarianceNetwork
 
 _NULL = ctypes.c_void_p(0)
+NET_CHUNK = 1 << 20          # points per forward pass of NeuSRenderer.eval_points
 
 
 def _p(t):
@@ -123,6 +124,21 @@ def prior_loss(rays, R, z, weights, nmap, prior_depth, sample_dist, depth_weight
     return stats
 
 
+@torch.no_grad()
+def corr_loss(rays_o, rays_d, z_vals, weights, corr, corr_frames, sample_dist, delta_px, weight, d_weights, pose_adj=None):
+    """dh_corr_loss on corr [B,4] = (u_j, v_j, certainty, frame_j) with corr_frames = (R_all [F,3,3], T_all [F,3], K [3,3]): returns
+    (stats [4], residual_px [B]) on the device, stats[3] = weight * the loss.  Writes d_weights [B,n] and, if given, pose_adj [B,7] (the
+    adjoint of the surface point x, of its image y = R_j x + T_j in the partner frame, and the expected depth t^); no host read."""
+    R_all, T_all, K = corr_frames
+    B, n = z_vals.shape
+    stats = torch.empty(4, device=rays_o.device)
+    resid = torch.empty(B, device=rays_o.device)
+    _lib.check(_lib.lib().dh_corr_loss(_p(rays_o), _p(rays_d), _p(z_vals), _p(weights), _p(corr.contiguous()), _p(R_all.contiguous()),
+                                       _p(T_all.contiguous()), int(R_all.shape[0]), _p(K.contiguous()), B, n, float(sample_dist),
+                                       float(delta_px), float(weight), _p(stats), _p(resid), _p(d_weights), _p(pose_adj), _lib.stream()))
+    return stats, resid
+
+
 def add_prior_stats(stats, pstats, use_depth, masked_normal):
     """Fold dh_prior_loss's weighted terms into dh_neus_loss's stats [8]: the total, and the normal loss the masked term replaces."""
     if use_depth:
@@ -178,31 +194,55 @@ class NeuSRenderer:
         return self._ws
 
     # ------------------------------------------------------------------ network stages (the model-family hooks;
-    # hash_fields.HashNeuSRenderer overrides these three + _workspace_need)
+    # hash_fields.HashNeuSRenderer overrides these three + _workspace_need + _net_outputs)
+    _net_outputs = (("sdf", ()), ("normals", (3,)), ("colors", (3,)))      # what _net_forward writes per point: (name, trailing shape)
+
     def _arith(self) -> int:
         return _lib.get_arithmetic() if self.arithmetic is None else int(self.arithmetic)
+
+    def net_state(self, pts, dirs, n_per_dir, save, n_active=None, buffers=None):
+        """The state the network hooks read, made here and nowhere else.  pts [P,3] with one direction of dirs per n_per_dir
+        consecutive points (a ray's samples; 1: a direction per point); save: 0 forward only (infer_only), 1 keep what _net_backward
+        needs, 2 also what the ray adjoints need (ray_grads).  Takes the workspace for P points and ALWAYS stamps it with a new token:
+        whatever state held the workspace before can no longer run its backward (_check_backward).  The outputs sdf [P], normals
+        [P,3], colors [P,3] (and the family's own) are allocated, or adopted from `buffers` (the packed path's pre-allocated set, which
+        also holds the adjoint buffers of the family's backward).  n_active: device count of the points in use (None: all P)."""
+        P = pts.shape[0]
+        s = SimpleNamespace(P=P, B=P // n_per_dir, n=n_per_dir, pts=pts, rays_d=dirs, save=save, infer_only=save == 0, ray_grads=save == 2,
+                            n_active=n_active, buffers=buffers)
+        s.ws = self._workspace(P, s.infer_only)
+        self._ws_token += 1
+        s.ws_token = self._ws_token
+        for name, shape in self._net_outputs:
+            setattr(s, name, torch.empty(P, *shape, device=pts.device) if buffers is None else getattr(buffers, name))
+        return s
+
+    def _check_backward(self, s):
+        """RuntimeError unless the forward state s saved for a backward and still owns the workspace."""
+        if s.infer_only:
+            raise RuntimeError("this forward pass was run with infer_only=True: nothing was saved for backward")
+        if s.ws_token != self._ws_token:
+            raise RuntimeError("NeuSRenderer workspace was overwritten by a later render() call before backward(); "
+                               "call backward() before rendering again (one live graph per renderer)")
 
     def _net_sdf_nograd(self, tag, pts, n, out):
         self.timer(tag, _lib.lib().dh_sdf_nograd_ex, self._arith(), _p(self.store.packed), _p(pts), n, _p(out), _lib.stream())
 
     def _net_forward(self, s, packed):
         """pts [P,3] -> s.sdf, s.normals (d sdf / d x), s.colors; saves what _net_backward needs in s.ws."""
-        L, T = _lib.lib(), self.timer
-        P = s.B * s.n
+        L, T, P = _lib.lib(), self.timer, s.P
         ar = s.arith = self._arith()          # the backward of this forward runs in the same arithmetic
         T("sdf_forward", L.dh_sdf_forward_ex, ar, _p(packed), _p(s.pts), P, _p(s.ws), _p(s.sdf), _lib.stream())
-        save = 0 if s.infer_only else (2 if getattr(s, "ray_grads", False) else 1)
-        T("sdf_gradient", L.dh_sdf_gradient_ex, ar, _p(packed), _p(s.pts), P, _p(s.ws), _p(s.normals), save, _lib.stream())
+        T("sdf_gradient", L.dh_sdf_gradient_ex, ar, _p(packed), _p(s.pts), P, _p(s.ws), _p(s.normals), s.save, _lib.stream())
         T("color_forward", L.dh_color_forward_ex, ar, _p(packed), _p(s.pts), _p(s.rays_d), s.n, _p(s.normals), P, _p(s.ws),
-          _p(s.colors), save, _lib.stream())
+          _p(s.colors), s.save, _lib.stream())
 
     def _net_backward(self, s, d_sdf, d_normals, d_colors, grad):
         """Adjoint of _net_forward into the flat gradient (every slot but `variance`).  With s.ray_grads (pose refinement) it
         also leaves s.d_pts [P,3] (d loss / d sample point) and s.d_dirs_pts [P,3] (d loss / d ray direction per point)."""
-        L, T, st = _lib.lib(), self.timer, self.store
-        P = s.B * s.n
+        L, T, st, P = _lib.lib(), self.timer, self.store, s.P
         ar = s.arith
-        if getattr(s, "ray_grads", False):
+        if s.ray_grads:
             s.d_pts = torch.empty(P, 3, device=s.pts.device)
             s.d_dirs_pts = torch.empty(P, 3, device=s.pts.device)
             T("color_backward", L.dh_color_backward_rays_ex, ar, _p(st.packed), _p(s.colors), _p(d_colors), _p(s.rays_d), s.n, P, _p(s.ws),
@@ -257,6 +297,27 @@ class NeuSRenderer:
         self.store.ensure_packed(self._arith())
         self._net_sdf_nograd("sdf_nograd", pts, pts.shape[0], out)
         return out.view(-1, 1)
+
+    @torch.no_grad()
+    def eval_points(self, pts, dirs, who):
+        """(normals [P,3] = the SDF gradient, colors [P,3]) of the networks at pts [P,3] seen along dirs [P,3]: forward-only passes
+        through the family hooks in chunks of at most NET_CHUNK points.  Non-finite output (split_f16 range exceeded, or a diverged
+        network) raises DynhorHipError in the name of the caller `who`.  Like every forward it takes the workspace: a forward whose
+        backward has not run yet loses it (_check_backward)."""
+        P = pts.shape[0]
+        normals, colors = torch.empty(P, 3, device=pts.device), torch.empty(P, 3, device=pts.device)
+        packed = self.store.ensure_packed(self._arith())
+        for s0 in range(0, P, NET_CHUNK):
+            p = pts[s0:s0 + NET_CHUNK].contiguous()
+            n = p.shape[0]
+            s = self.net_state(p, dirs[s0:s0 + n].contiguous(), 1, 0)
+            self._net_forward(s, packed)
+            normals[s0:s0 + n] = s.normals
+            colors[s0:s0 + n] = s.colors
+        if not bool(torch.isfinite(colors).all()) or not bool(torch.isfinite(normals).all()):
+            raise _lib.DynhorHipError(f"{who}: non-finite network output at the query points (split_f16 range exceeded, or the network "
+                                      "has diverged); use arithmetic 'split_bf16'")
+        return normals, colors
 
     # ------------------------------------------------------------------ geometry extraction (upstream extract_geometry)
     @torch.no_grad()
@@ -355,19 +416,9 @@ class NeuSRenderer:
         packed = st.ensure_packed(self._arith())
         dev = rays_o.device
         B, n = z_vals.shape
-        P = B * n
-        s = SimpleNamespace()
-        s.B, s.n, s.car, s.sample_dist = B, n, float(cos_anneal_ratio), 2.0 / self.n_samples
-        s.rays_o, s.rays_d, s.z_vals, s.bg = rays_o, rays_d, z_vals, background_rgb
-        s.ws = self._workspace(P, infer_only)
-        s.infer_only = infer_only
-        s.ray_grads = bool(ray_grads) and not infer_only
-        self._ws_token += 1
-        s.ws_token = self._ws_token
-        s.pts = torch.empty(P, 3, device=dev)
-        s.sdf = torch.empty(P, device=dev)
-        s.normals = torch.empty(P, 3, device=dev)
-        s.colors = torch.empty(P, 3, device=dev)
+        s = self.net_state(torch.empty(B * n, 3, device=dev), rays_d, n, 0 if infer_only else (2 if ray_grads else 1))
+        s.car, s.sample_dist = float(cos_anneal_ratio), 2.0 / self.n_samples
+        s.rays_o, s.z_vals, s.bg = rays_o, z_vals, background_rgb
         _lib.check(L.dh_midpoints(_p(rays_o), _p(rays_d), _p(z_vals), B, n, s.sample_dist, _p(s.pts), _lib.stream()))
         self._net_forward(s, packed)
         s.inv_s = st.inv_s()
@@ -385,17 +436,26 @@ class NeuSRenderer:
                                         _p(s.nmap), _lib.stream()))
         return s
 
+    def first_cdf(self, s):
+        """[B,1]: the cdf value at the first sample of every ray of the forward state s (Runner.report's Statistics/cdf)."""
+        return s.cdf[:, :1]
+
+    def _variance_grad(self, d_inv_s, grad):
+        """The variance slot of the flat gradient from the scan's d_inv_s [B], inv_s = clip(exp(10 v), 1e-6, 1e6); grad is then
+        complete and becomes store.grad_flat."""
+        st = self.store
+        raw = torch.exp(st.flat[st.var_off] * 10.0)
+        passthrough = ((raw >= 1e-6) & (raw <= 1e6)).float()
+        grad[st.var_off] = d_inv_s.sum() * 10.0 * raw * passthrough
+        st.grad_flat = grad
+
     @torch.no_grad()
     def _backward_core(self, s, d_color, d_wsum, d_weights, d_gradients, d_nmap, eik_coef, d_sdf_out=None, persistent=False):
         """Adjoint of _forward_core: returns the flat parameter gradient (also kept as store.grad_flat).  persistent: write it
         into the store's one long-lived bucket (the fused training step: same address every iteration for the all-reduce)."""
         L = _lib.lib()
         st = self.store
-        if s.infer_only:
-            raise RuntimeError("this forward pass was run with infer_only=True: nothing was saved for backward")
-        if s.ws_token != self._ws_token:
-            raise RuntimeError("NeuSRenderer workspace was overwritten by a later render() call before backward(); "
-                               "call backward() before rendering again (one live graph per renderer)")
+        self._check_backward(s)
         B, n = s.B, s.n
         P = B * n
         dev = s.color.device
@@ -420,11 +480,7 @@ class NeuSRenderer:
             d_sdf = (d_sdf + d_sdf_out.reshape(-1)).contiguous()
         grad = st.grad_bucket() if persistent else torch.empty(st.n, device=dev)
         self._net_backward(s, d_sdf, d_normals, d_colors, grad)
-        # variance: inv_s = clip(exp(10 v), 1e-6, 1e6)
-        raw = torch.exp(st.flat[st.var_off] * 10.0)
-        passthrough = ((raw >= 1e-6) & (raw <= 1e6)).float()
-        grad[st.var_off] = d_inv_s.sum() * 10.0 * raw * passthrough
-        st.grad_flat = grad
+        self._variance_grad(d_inv_s, grad)
         if s.ray_grads:
             # per-ray reduction of the point adjoints (sample depths are constants): x = o + mid * d
             dz = torch.cat([s.z_vals[:, 1:] - s.z_vals[:, :-1], torch.full_like(s.z_vals[:, :1], s.sample_dist)], -1)
@@ -467,6 +523,46 @@ class NeuSRenderer:
 
     # ------------------------------------------------------------------ fused training step (Runner hot loop)
     @torch.no_grad()
+    def _loss_stage(self, s, rays, R, z, sample_dist, igr_weight, mask_weight, normal_weight, packed=None, d_weights=None, corr=None,
+                    corr_weight=0.0, corr_frames=None, corr_delta_px=4.0, prior_depth=None, depth_weight=0.0, depth_delta=0.02,
+                    normal_skip_missing=False):
+        """Every loss term of train_step_core on the forward state s, for both descriptions of the samples: dense, z = z_vals [B,n]
+        with sample_dist; packed = (seg_off, seg_cnt, max_samples), z = t_start with sample_dist = the marching step, and d_weights =
+        the pre-allocated buffer the depth term writes (dense: allocated here).  dh_neus_loss; with corr and corr_weight > 0 corr_loss
+        (self.last_corr_stats, self.last_corr_residual_px); with depth_weight > 0 or normal_skip_missing prior_loss, stacked on the
+        correspondence term's d_weights or writing its own (self.last_prior_stats).  Returns a namespace: stats [8] with every term
+        folded in, the adjoints d_color, d_wsum, d_weights (None when no term has one), d_nmap (None without a normal term), eik_coef
+        for the backward, R as the kernels took it and pose_adj [B,7] (corr_loss's, under s.ray_grads; else None).  No host read."""
+        if depth_weight > 0.0 and prior_depth is None:
+            raise ValueError("train_step_core: depth_weight > 0 needs prior_depth [B]")
+        use_depth = depth_weight > 0.0
+        masked_normal = bool(normal_skip_missing) and normal_weight > 0.0
+        dev = rays.device
+        B = rays.shape[0]
+        a = SimpleNamespace(stats=torch.empty(8, device=dev), d_color=torch.empty(B, 3, device=dev), d_wsum=torch.empty(B, device=dev),
+                            d_nmap=torch.empty(B, 3, device=dev) if normal_weight > 0.0 else None, eik_coef=torch.empty(1, device=dev),
+                            R=R.contiguous().float() if R is not None else None, d_weights=None, pose_adj=None)
+        _lib.check(_lib.lib().dh_neus_loss(_p(s.color), _p(s.wsum), _p(s.nmap), _p(s.eik), _p(rays), _p(a.R), B, float(igr_weight),
+                                           float(mask_weight), 0.0 if masked_normal else float(normal_weight), _p(a.stats),
+                                           _p(a.d_color), _p(a.d_wsum), _p(a.d_nmap), _p(a.eik_coef), _lib.stream()))
+        if corr is not None and corr_weight > 0.0:
+            a.d_weights = torch.empty(B, s.n, device=dev)
+            a.pose_adj = torch.empty(B, 7, device=dev) if s.ray_grads else None
+            self.last_corr_stats, self.last_corr_residual_px = corr_loss(s.rays_o, s.rays_d, z, s.weights, corr, corr_frames, sample_dist,
+                                                                         corr_delta_px, corr_weight, a.d_weights, a.pose_adj)
+            a.stats[0] += self.last_corr_stats[3]
+        if use_depth or masked_normal:
+            stacked = a.d_weights is not None
+            if use_depth and not stacked:
+                a.d_weights = d_weights if d_weights is not None else torch.empty(B, s.n, device=dev)
+            self.last_prior_stats = prior_loss(rays, a.R, z, s.weights, s.nmap if masked_normal else None,
+                                               prior_depth if use_depth else None, sample_dist, depth_weight if use_depth else 0.0,
+                                               depth_delta, normal_weight if masked_normal else 0.0, stacked,
+                                               a.d_weights if use_depth else None, a.d_nmap if masked_normal else None, packed=packed)
+            add_prior_stats(a.stats, self.last_prior_stats, use_depth, masked_normal)
+        return a
+
+    @torch.no_grad()
     def train_step_core(self, rays, near, far, R, cos_anneal_ratio, igr_weight=0.1, mask_weight=0.1, normal_weight=0.0,
                         background_rgb=None, t_rand=None, corr=None, corr_weight=0.0, corr_frames=None, corr_delta_px=4.0,
                         ray_grads=False, prior_depth=None, depth_weight=0.0, depth_delta=0.02, normal_skip_missing=False):
@@ -486,62 +582,28 @@ class NeuSRenderer:
         term supplies d_nmap and stats[4].  Either leaves self.last_prior_stats [8]; neither launches anything when off.  The depth
         term needs no adjoint of its own under ray_grads: c_z = (R d)_z is the z of the camera-frame direction K^-1 (u, v, 1),
         which no pose enters, and the sample depths are constants there already, so all of it flows through d_weights."""
-        L = _lib.lib()
-        dev = rays.device
-        B = rays.shape[0]
-        if depth_weight > 0.0 and prior_depth is None:
-            raise ValueError("train_step_core: depth_weight > 0 needs prior_depth [B]")
-        use_depth = depth_weight > 0.0
-        masked_normal = bool(normal_skip_missing) and normal_weight > 0.0
         rays_o = rays[:, 0:3].contiguous()
         rays_d = rays[:, 3:6].contiguous()
         z_vals = self.sample_z(rays_o, rays_d, near, far, t_rand=t_rand)
         bg = None if background_rgb is None else background_rgb.reshape(-1).contiguous().float()
         s = self._forward_core(rays_o, rays_d, z_vals, cos_anneal_ratio, bg, want_nmap=normal_weight > 0.0, ray_grads=ray_grads)
-        stats = torch.empty(8, device=dev)
-        d_color = torch.empty(B, 3, device=dev)
-        d_wsum = torch.empty(B, device=dev)
-        d_nmap = torch.empty(B, 3, device=dev) if normal_weight > 0.0 else None
-        eik_coef = torch.empty(1, device=dev)
-        Rc = R.contiguous().float() if R is not None else None
-        _lib.check(L.dh_neus_loss(_p(s.color), _p(s.wsum), _p(s.nmap), _p(s.eik), _p(rays), _p(Rc), B, float(igr_weight),
-                                  float(mask_weight), 0.0 if masked_normal else float(normal_weight), _p(stats), _p(d_color),
-                                  _p(d_wsum), _p(d_nmap), _p(eik_coef), _lib.stream()))
-        d_weights = None
-        if corr is not None and corr_weight > 0.0:
-            R_all, T_all, K = corr_frames
-            cstats = torch.empty(4, device=dev)
-            resid = torch.empty(B, device=dev)
-            d_weights = torch.empty(B, s.n, device=dev)
-            pose_adj = torch.empty(B, 7, device=dev) if ray_grads else None
-            _lib.check(L.dh_corr_loss(_p(rays_o), _p(rays_d), _p(z_vals), _p(s.weights), _p(corr.contiguous()),
-                                      _p(R_all.contiguous()), _p(T_all.contiguous()), int(R_all.shape[0]), _p(K.contiguous()),
-                                      B, s.n, s.sample_dist, float(corr_delta_px), float(corr_weight), _p(cstats), _p(resid),
-                                      _p(d_weights), _p(pose_adj), _lib.stream()))
-            stats[0] += cstats[3]
-            self.last_corr_stats, self.last_corr_residual_px = cstats, resid
-        if use_depth or masked_normal:
-            stacked = d_weights is not None
-            if use_depth and not stacked:
-                d_weights = torch.empty(B, s.n, device=dev)
-            self.last_prior_stats = prior_loss(rays, Rc, z_vals, s.weights, s.nmap if masked_normal else None,
-                                               prior_depth if use_depth else None, s.sample_dist, depth_weight if use_depth else 0.0,
-                                               depth_delta, normal_weight if masked_normal else 0.0, stacked,
-                                               d_weights if use_depth else None, d_nmap if masked_normal else None)
-            add_prior_stats(stats, self.last_prior_stats, use_depth, masked_normal)
-        self._backward_core(s, d_color, d_wsum, d_weights, None, d_nmap, eik_coef, persistent=True)
+        a = self._loss_stage(s, rays, R, z_vals, s.sample_dist, igr_weight, mask_weight, normal_weight, corr=corr, corr_weight=corr_weight,
+                             corr_frames=corr_frames, corr_delta_px=corr_delta_px, prior_depth=prior_depth, depth_weight=depth_weight,
+                             depth_delta=depth_delta, normal_skip_missing=normal_skip_missing)
+        self._backward_core(s, a.d_color, a.d_wsum, a.d_weights, None, a.d_nmap, a.eik_coef, persistent=True)
         self.last_state = s
         if ray_grads:
             d_R = None
-            if normal_weight > 0.0 and Rc is not None:
+            if normal_weight > 0.0 and a.R is not None:
                 # n_cam = R n_obj enters the normal loss directly: d loss / d R = sum_b (R d_nmap_b) nmap_b^T  (d_nmap = R^T d n_cam)
-                d_R = (d_nmap @ Rc.T).T @ s.nmap
+                d_R = (a.d_nmap @ a.R.T).T @ s.nmap
             self.last_partner_pose_grads = None
-            if corr is not None and corr_weight > 0.0:
+            if a.pose_adj is not None:
                 # the correspondence term also depends on the rays DIRECTLY (x = o + t^ d at fixed t^) and on the partner
                 # frames' poses (y = R_j x + T_j); dh_corr_loss returns those adjoints per ray (ADVICE r2: without them the pose
                 # gradient of the combined configuration was incomplete)
-                d_x, d_y, t_hat = pose_adj[:, 0:3], pose_adj[:, 3:6], pose_adj[:, 6:7]
+                R_all, T_all, _ = corr_frames
+                d_x, d_y, t_hat = a.pose_adj[:, 0:3], a.pose_adj[:, 3:6], a.pose_adj[:, 6:7]
                 s.d_rays_o = s.d_rays_o + d_x
                 s.d_rays_d = s.d_rays_d + t_hat * d_x
                 x = rays_o + t_hat * rays_d
@@ -550,4 +612,4 @@ class NeuSRenderer:
                 d_T_all = torch.zeros_like(T_all).index_add_(0, j, d_y)
                 self.last_partner_pose_grads = (d_R_all, d_T_all)
             self.last_ray_grads = (s.d_rays_o, s.d_rays_d, d_R)
-        return stats
+        return a.stats

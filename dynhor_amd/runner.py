@@ -392,14 +392,7 @@ class Runner:
             # upstream Statistics/cdf and Statistics/weight_max (App. A.8), masked by obj*keep like the colour loss
             m = (self._last_rays[:, 9:10] * self._last_rays[:, 10:11])
             msum = float(m.sum()) + 1e-5
-            if st.cdf.dim() == 2:
-                cdf0 = st.cdf[:, :1]
-            else:
-                # packed rays (hash family, occupancy-grid sampler): cdf is the flat capacity buffer; a ray's first sample sits at
-                # its segment offset, rays without samples contribute nothing (st.cdf[:, :1] raised IndexError here)
-                off, cnt = st.m.off, st.m.cnt
-                cdf0 = (st.cdf[off.clamp(max=st.cdf.shape[0] - 1)] * (cnt > 0)).view(-1, 1)
-            rec["Statistics/cdf"] = float((cdf0 * m).sum()) / msum
+            rec["Statistics/cdf"] = float((self.renderer.first_cdf(st) * m).sum()) / msum
             rec["Statistics/weight_max"] = float((st.wmax * m).sum()) / msum
         if self.rank == 0:
             self.scalars.append(rec)
@@ -421,11 +414,9 @@ class Runner:
         """Outlier voting over ALL matches with the current geometry (forward-only render of every matched ray, residuals from
         dh_corr_loss, then Dataset.vote_correspondences).  Every rank evaluates the same matches with the same weights, so
         the certainties stay identical across ranks without a collective."""
-        from . import _lib
-        from .renderer import _p
+        from .renderer import corr_loss
         ds, ren = self.dataset, self.renderer
         res = torch.full((ds.corr.shape[0],), float("nan"), device=self.device)
-        R_all, T_all, K = ds.corr_frames()
         for f, (lo, hi) in ds._corr_range.items():
             for s0 in range(lo, hi, chunk):
                 m = ds.corr[s0:min(s0 + chunk, hi)]
@@ -436,11 +427,8 @@ class Runner:
                 z = ren.sample_z(o, d, near, far, perturb_overwrite=0)
                 st = ren._forward_core(o, d, z, self.get_cos_anneal_ratio(), None, want_nmap=False, infer_only=True)
                 corr = torch.cat([m[:, 2:4], torch.ones(B, 1, device=self.device), m[:, 5:6]], -1).contiguous()
-                cst = torch.empty(4, device=self.device); r = torch.empty(B, device=self.device)
-                dw = torch.empty(B, st.n, device=self.device)
-                _lib.check(_lib.lib().dh_corr_loss(_p(o), _p(d), _p(z), _p(st.weights), _p(corr), _p(R_all), _p(T_all),
-                                                  int(R_all.shape[0]), _p(K), B, st.n, st.sample_dist, float(self.corr_delta_px), 1.0,
-                                                  _p(cst), _p(r), _p(dw), None, _lib.stream()))
+                _, r = corr_loss(o, d, z, st.weights, corr, ds.corr_frames(), st.sample_dist, self.corr_delta_px, 1.0,
+                                 torch.empty(B, st.n, device=self.device))
                 # rays that render (almost) nothing have no surface estimate yet: leave them un-voted (NaN); a match whose point
                 # lands behind the partner camera comes back +inf and votes as an outlier
                 res[s0:s0 + B] = torch.where(st.wsum.view(-1) > 0.5, r, torch.full_like(r, float("nan")))

@@ -17,7 +17,6 @@ The template is a category-level prior: the fit starts training near a plausible
 from __future__ import annotations
 
 import time
-from types import SimpleNamespace
 
 import torch
 
@@ -80,18 +79,10 @@ def fit_forward(renderer, pts: torch.Tensor, ray_points: int):
     P = int(pts.shape[0])
     if P % ray_points:
         raise ValueError(f"fit_forward: {P} points are not a multiple of ray_points ({ray_points})")
-    st = renderer.store
-    dev = pts.device
-    packed = st.ensure_packed(renderer._arith())
-    s = SimpleNamespace(B=P // ray_points, n=int(ray_points), pts=pts.contiguous(), infer_only=False, ray_grads=False)
-    s.rays_d = torch.zeros(s.B, 3, device=dev)
-    s.rays_d[:, 2] = 1.0
-    s.ws = renderer._workspace(P, False)
-    renderer._ws_token += 1
-    s.ws_token = renderer._ws_token
-    s.sdf = torch.empty(P, device=dev)
-    s.normals = torch.empty(P, 3, device=dev)
-    s.colors = torch.empty(P, 3, device=dev)
+    packed = renderer.store.ensure_packed(renderer._arith())
+    dirs = torch.zeros(P // ray_points, 3, device=pts.device)
+    dirs[:, 2] = 1.0
+    s = renderer.net_state(pts.contiguous(), dirs, int(ray_points), 1)
     renderer._net_forward(s, packed)
     return s
 
@@ -101,7 +92,8 @@ def fit_backward(renderer, s, sdf_mesh: torch.Tensor, eik_weight: float):
     """The loss (a 0-dim device tensor) of the forward state s against the targets sdf_mesh [P], and its flat parameter gradient in
     the store's gradient bucket (also store.grad_flat): the colour slots exactly zero, the variance slot zero."""
     st = renderer.store
-    P = s.B * s.n
+    renderer._check_backward(s)
+    P = s.P
     diff = s.sdf - sdf_mesh
     gn = s.normals.norm(dim=1)
     loss = diff.abs().mean() + eik_weight * ((gn - 1.0) ** 2).mean()

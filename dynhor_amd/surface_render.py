@@ -32,7 +32,6 @@ BACKGROUNDS = ("white", "black", "frame")
 TRACE_DEFAULTS = {"eps": 2e-4, "relax": 0.8, "min_step": 1e-3, "max_step": 0.1, "refine_steps": 8, "max_steps": 48,
                   "scan_step": 0.01, "compact_every": 1}
 MAX_RAYS = 1 << 21           # rays traced at once (render_surface chunks the views)
-NET_CHUNK = 1 << 20          # hit points per forward pass
 SCAN_CHUNK = 1 << 20         # chord-scan samples per query
 
 _NULL = None
@@ -366,25 +365,8 @@ def compose(a, slot, normals, colors, background="white", frame_rgb=None, frame_
 
 @torch.no_grad()
 def network_at_hits(renderer, pts, dirs):
-    """(normals [P,3] = the SDF gradient, colors [P,3]) of the renderer's networks at pts seen along dirs: one forward pass through the
-    family hooks (_net_forward, one sample per "ray", forward-only workspace) in chunks of NET_CHUNK, as mesh_color.network_vertex_colors."""
-    dev = pts.device
-    P = pts.shape[0]
-    normals, colors = torch.empty(P, 3, device=dev), torch.empty(P, 3, device=dev)
-    packed = renderer.store.ensure_packed(renderer._arith())
-    for s0 in range(0, P, NET_CHUNK):
-        p = pts[s0:s0 + NET_CHUNK].contiguous()
-        n = p.shape[0]
-        s = SimpleNamespace(B=n, n=1, pts=p, rays_d=dirs[s0:s0 + n].contiguous(), infer_only=True, ray_grads=False,
-                            ws=renderer._workspace(n, infer_only=True), sdf=torch.empty(n, device=dev),
-                            normals=torch.empty(n, 3, device=dev), colors=torch.empty(n, 3, device=dev))
-        renderer._net_forward(s, packed)
-        normals[s0:s0 + n] = s.normals
-        colors[s0:s0 + n] = s.colors
-    if not bool(torch.isfinite(colors).all()) or not bool(torch.isfinite(normals).all()):
-        raise _lib.DynhorHipError("render_surface: non-finite network output at the hit points (split_f16 range exceeded, or the network "
-                                  "has diverged); use arithmetic 'split_bf16'")
-    return normals, colors
+    """(normals [P,3] = the SDF gradient, colors [P,3]) of the renderer's networks at pts seen along dirs (renderer.eval_points)."""
+    return renderer.eval_points(pts, dirs, "render_surface")
 
 
 @torch.no_grad()

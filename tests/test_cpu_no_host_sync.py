@@ -15,7 +15,8 @@ def _hot_functions():
     H, N = hash_fields.HashNeuSRenderer, renderer.NeuSRenderer
     return [H.train_step_core, H.march, H._forward_packed, H._backward_packed, H._net_forward, H._net_backward, H._net_sdf_nograd,
             H.update_grid, hash_fields.OccupancyGrid.update, N.train_step_core, N._forward_core, N._backward_core, N.sample_z,
-            N._net_forward, N._net_backward, N._net_sdf_nograd]
+            N._net_forward, N._net_backward, N._net_sdf_nograd, N.net_state, N._check_backward, N._loss_stage, N._variance_grad,
+            renderer.corr_loss, renderer.prior_loss, renderer.add_prior_stats]
 
 
 @pytest.mark.parametrize("fn", _hot_functions(), ids=lambda f: f.__qualname__)

@@ -68,10 +68,7 @@ def test_geo_forward_matches_oracle(n):
         gref = sdf_net.gradient(x.double()).squeeze(1)
         sdf_net.float()
     got_sdf = p_r.sdf(x)
-    s = type("S", (), {})()
-    s.B, s.n, s.pts, s.rays_d, s.infer_only = n, 1, x, x, True
-    s.ws = p_r._workspace(n, infer_only=True)
-    s.sdf = torch.empty(n, device="cuda"); s.normals = torch.empty(n, 3, device="cuda"); s.colors = torch.empty(n, 3, device="cuda")
+    s = p_r.net_state(x, x, 1, 0)
     p_r._net_forward(s, p_r.store.ensure_packed())
     torch.cuda.synchronize()
     e_sdf = (got_sdf.double() - ref[:, :1]).abs().max().item()
