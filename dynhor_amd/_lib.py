@@ -69,6 +69,8 @@ SIGNATURES = {
     "dh_hash_color_forward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp]),
     "dh_hash_color_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
     "dh_hash_geo_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _vp, _vp, _vp]),
+    "dh_hash_color_backward_rays": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dh_hash_geo_backward_rays": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _vp, _vp, _vp, _vp]),
     "dh_hash_weight_grads": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "dh_hash_weight_grads_parts": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp]),
     "dh_gen_rays": (_i32, [_vp] * 6 + [_i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
@@ -88,6 +90,8 @@ SIGNATURES = {
     "dh_trace_compose": (_i32, [_vp] * 6 + [_i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32] + [_vp] * 5),
     "dh_render_scan_fwd_packed": (_i32, [_vp] * 7 + [_f32, _f32, _vp, _i64] + [_vp] * 11),
     "dh_render_scan_bwd_packed": (_i32, [_vp] * 7 + [_f32, _f32, _vp, _i64] + [_vp] * 13),
+    "dh_render_scan_bwd_packed_rays": (_i32, [_vp] * 7 + [_f32, _f32, _vp, _i64] + [_vp] * 14),
+    "dh_ray_adjoint_packed": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _i64, _vp, _vp, _vp]),
     "dh_neus_loss": (_i32, [_vp] * 6 + [_i64, _f32, _f32, _f32] + [_vp] * 6),
     "dh_corr_loss": (_i32, [_vp] * 7 + [_i32, _vp, _i64, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "dh_prior_loss_workspace": (_i64, [_i64]),

@@ -420,6 +420,30 @@ int dh_render_scan_bwd_packed(const float* rays_o, const float* rays_d, const fl
                              d_inv_s, nullptr, seg_off, seg_cnt, static_cast<hipStream_t>(stream));
 }
 
+int dh_render_scan_bwd_packed_rays(const float* rays_o, const float* rays_d, const float* t_start, const float* sdf, const float* normals,
+                                   const float* colors, const float* inv_s, float cos_anneal_ratio, float step,
+                                   const float* background_rgb, int64_t B, const int64_t* seg_off, const int32_t* seg_cnt,
+                                   const float* d_color, const float* d_weight_sum, const float* d_weights, const float* d_gradients,
+                                   const float* d_normal_map, const float* eik_coef, float* d_sdf, float* d_normals, float* d_colors,
+                                   float* d_inv_s, float* d_rays_d, void* stream) {
+    if (B < 0) return DH_ERR_BAD_ARG;
+    if (B == 0) return DH_OK;
+    if (!rays_o || !rays_d || !t_start || !sdf || !normals || !colors || !inv_s || !seg_off || !seg_cnt || !d_color || !eik_coef ||
+        !d_sdf || !d_normals || !d_colors || !d_inv_s || !d_rays_d) return DH_ERR_BAD_ARG;
+    return launch_render_bwd(rays_o, rays_d, t_start, sdf, normals, colors, inv_s, cos_anneal_ratio, step, background_rgb, B, 0,
+                             d_color, d_weight_sum, d_weights, d_gradients, d_normal_map, eik_coef, d_sdf, d_normals, d_colors,
+                             d_inv_s, d_rays_d, seg_off, seg_cnt, static_cast<hipStream_t>(stream));
+}
+
+int dh_ray_adjoint_packed(const float* d_pts, const float* d_dirs_pts, const float* t_start, float step, const int64_t* seg_off,
+                          const int32_t* seg_cnt, int64_t B, float* d_rays_o, float* d_rays_d_accum, void* stream) {
+    if (B < 0) return DH_ERR_BAD_ARG;
+    if (B == 0) return DH_OK;
+    if (!d_pts || !d_dirs_pts || !t_start || !seg_off || !seg_cnt || !d_rays_o || !d_rays_d_accum) return DH_ERR_BAD_ARG;
+    return launch_ray_adjoint_packed(d_pts, d_dirs_pts, t_start, step, seg_off, seg_cnt, B, d_rays_o, d_rays_d_accum,
+                                     static_cast<hipStream_t>(stream));
+}
+
 int dh_adam_step(float* params, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                  float beta2, float eps, int64_t step, float grad_scale, void* stream) {
     if (n < 0 || step < 1) return DH_ERR_BAD_ARG;
@@ -584,7 +608,17 @@ int dh_hash_color_backward(const float* packed, const float* feature, const floa
     if (n <= 0 || n_per_ray <= 0 || n % n_per_ray || (n_active && n % 8)) return DH_ERR_BAD_ARG;
     if (!packed || !feature || !normals || !dirs || !d_color || !ws || !d_feature || !d_normals || !al16(packed) || !al16(ws))
         return DH_ERR_BAD_ARG;
-    return launch_sh_color_bwd(packed, feature, normals, dirs, d_color, n_per_ray, n, ws, d_feature, d_normals, n_active,
+    return launch_sh_color_bwd(packed, feature, normals, dirs, d_color, n_per_ray, n, ws, d_feature, d_normals, nullptr, n_active,
+                               static_cast<hipStream_t>(stream));
+}
+
+int dh_hash_color_backward_rays(const float* packed, const float* feature, const float* normals, const float* dirs,
+                                const float* d_color, int n_per_ray, int64_t n, float* ws, float* d_feature, float* d_normals,
+                                const int64_t* n_active, float* d_dirs_pts, void* stream) {
+    if (n <= 0 || n_per_ray <= 0 || n % n_per_ray || (n_active && n % 8)) return DH_ERR_BAD_ARG;
+    if (!packed || !feature || !normals || !dirs || !d_color || !ws || !d_feature || !d_normals || !d_dirs_pts || !al16(packed) ||
+        !al16(ws)) return DH_ERR_BAD_ARG;
+    return launch_sh_color_bwd(packed, feature, normals, dirs, d_color, n_per_ray, n, ws, d_feature, d_normals, d_dirs_pts, n_active,
                                static_cast<hipStream_t>(stream));
 }
 
@@ -594,7 +628,17 @@ int dh_hash_geo_backward(const float* params, const float* packed, const float* 
     if (n <= 0 || !(radius > 0.f) || !(eps > 0.f) || (n_active && n % 8)) return DH_ERR_BAD_ARG;
     if (!params || !packed || !pts || !d_sdf || !d_feature || !d_normals || !ws || !al16(params) || !al16(packed) || !al16(ws))
         return DH_ERR_BAD_ARG;
-    return launch_hash_geo_bwd(params, packed, pts, d_sdf, d_feature, d_normals, n, radius, eps, ws, n_active,
+    return launch_hash_geo_bwd(params, packed, pts, d_sdf, d_feature, d_normals, n, radius, eps, ws, nullptr, n_active,
+                               static_cast<hipStream_t>(stream));
+}
+
+int dh_hash_geo_backward_rays(const float* params, const float* packed, const float* pts, const float* d_sdf,
+                              const float* d_feature, const float* d_normals, int64_t n, float radius, float eps, float* ws,
+                              const int64_t* n_active, float* d_pts, void* stream) {
+    if (n <= 0 || !(radius > 0.f) || !(eps > 0.f) || (n_active && n % 8)) return DH_ERR_BAD_ARG;
+    if (!params || !packed || !pts || !d_sdf || !d_feature || !d_normals || !ws || !d_pts || !al16(params) || !al16(packed) ||
+        !al16(ws)) return DH_ERR_BAD_ARG;
+    return launch_hash_geo_bwd(params, packed, pts, d_sdf, d_feature, d_normals, n, radius, eps, ws, d_pts, n_active,
                                static_cast<hipStream_t>(stream));
 }
 

@@ -349,12 +349,32 @@ __device__ __forceinline__ void store_col(float* base, int64_t ld, int64_t r, co
     DH_UNROLL for (int k = 0; k < N; ++k) if (k < cnt) base[k * ld + r] = v[k];
 }
 
-// colour network adjoint.  d_normals is read-modify-written (the render-scan adjoint is already in it).
+// adjoint of sh4_eval: g[c] = sum_k dy[k] d y_k / d d_c (the 16 polynomials of an unnormalised d, differentiated term by term)
+__device__ __forceinline__ void sh4_grad(const float (&d)[3], const float* dy, float (&g)[3]) {
+    const float x = d[0], y = d[1], z = d[2];
+    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+    const float c1 = 0.48860251190291987f, c2 = 1.0925484305920792f, c3 = 0.94617469575755997f, c5 = 0.54627421529603959f;
+    const float c6 = 0.59004358992664352f, c7 = 2.8906114426405538f, c8 = 0.45704579946446572f, c9 = 0.3731763325901154f;
+    const float c10 = 1.4453057213202769f;
+    const float q = 1.f - 5.f * zz, t = 3.f * (yy - xx);
+    g[0] = -c1 * dy[3] + c2 * (y * dy[4] - z * dy[7]) + 2.f * c5 * x * dy[8] - 6.f * c6 * xy * dy[9] + c7 * yz * dy[10]
+           + c8 * q * dy[13] + 2.f * c10 * xz * dy[14] + c6 * t * dy[15];
+    g[1] = -c1 * dy[1] + c2 * (x * dy[4] - z * dy[5]) - 2.f * c5 * y * dy[8] + c6 * t * dy[9] + c7 * xz * dy[10]
+           + c8 * q * dy[11] - 2.f * c10 * yz * dy[14] + 6.f * c6 * xy * dy[15];
+    g[2] = c1 * dy[2] - c2 * (y * dy[5] + x * dy[7]) + 2.f * c3 * z * dy[6] + c7 * xy * dy[10] - 10.f * c8 * z * (y * dy[11] + x * dy[13])
+           + c9 * (15.f * zz - 3.f) * dy[12] + c10 * (xx - yy) * dy[14];
+}
+
+// colour network adjoint.  d_normals is read-modify-written (the render-scan adjoint is already in it).  RAYS (pose refinement): the
+// first layer's input adjoint is formed for the SH columns 13..28 too and chained through sh4_grad into d_dirs_pts [n,3], one row per
+// point (the caller sums a ray's rows); every other output is the same arithmetic as without it.
+template <bool RAYS>
 __global__ __launch_bounds__(256) void sh_color_bwd_kernel(const float* __restrict__ hp, const float* __restrict__ feat,
                                                            const float* __restrict__ normals, const float* __restrict__ dirs,
                                                            const float* __restrict__ d_color, int n_per_ray, int64_t n,
                                                            float* __restrict__ ws, HashWs O, float* __restrict__ d_feat,
-                                                           float* __restrict__ d_normals, const int64_t* __restrict__ n_act) {
+                                                           float* __restrict__ d_normals, float* __restrict__ d_dirs_pts,
+                                                           const int64_t* __restrict__ n_act) {
     __shared__ __attribute__((aligned(16))) float W[HP_WEIGHTS + 4];
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t na = active_rows(n_act, n);
@@ -433,7 +453,7 @@ __global__ __launch_bounds__(256) void sh_color_bwd_kernel(const float* __restri
     DH_UNROLL for (int j = 0; j < HM_HID; ++j) {
         const f32x4* wr = reinterpret_cast<const f32x4*>(W + HP_C0 + j * HM_CIN);
         DH_UNROLL for (int k4 = 0; k4 < HM_CIN / 4; ++k4) {
-            if (k4 >= 4 && k4 < 7) continue;                      // SH inputs: the direction is not differentiated
+            if (!RAYS && k4 >= 4 && k4 < 7) continue;             // SH inputs: the direction is differentiated under RAYS only
             const f32x4 w = wr[k4];
             din[4 * k4] = fmaf(w[0], dh1[j], din[4 * k4]); din[4 * k4 + 1] = fmaf(w[1], dh1[j], din[4 * k4 + 1]);
             din[4 * k4 + 2] = fmaf(w[2], dh1[j], din[4 * k4 + 2]); din[4 * k4 + 3] = fmaf(w[3], dh1[j], din[4 * k4 + 3]);
@@ -441,14 +461,22 @@ __global__ __launch_bounds__(256) void sh_color_bwd_kernel(const float* __restri
     }
     DH_UNROLL for (int c = 0; c < HM_FEAT; ++c) d_feat[p * HM_FEAT + c] = din[c];
     DH_UNROLL for (int c = 0; c < 3; ++c) d_normals[p * 3 + c] += din[HM_FEAT + 16 + c];
+    if (RAYS) {
+        float g[3];
+        sh4_grad(d, din + HM_FEAT, g);
+        DH_UNROLL for (int c = 0; c < 3; ++c) d_dirs_pts[p * 3 + c] = g[c];
+    }
 }
 
 // geometry adjoint: E = 7 evaluations per point (centre with the feature/sdf cotangent, +-eps per axis with
-// +-d_grad * 0.5/eps on the sdf output).  Writes the rows small_dw_kernel and the table scatter consume.
+// +-d_grad * 0.5/eps on the sdf output).  Writes the rows small_dw_kernel and the table scatter consume.  RAYS (pose refinement):
+// also the point adjoint through the xyz inputs, in[c] = x_c / radius of all E evaluations: d_pts [n,3] = (sum_e din_e[0..2]) / radius,
+// which hash_point_adjoint_kernel then completes with the encoding's share.
+template <bool RAYS>
 __global__ __launch_bounds__(256) void hash_geo_bwd_kernel(const float* __restrict__ hp, const float* __restrict__ pts,
                                                            const float* __restrict__ d_sdf, const float* __restrict__ d_feat,
                                                            const float* __restrict__ d_grad, int64_t n, float radius,
-                                                           float eps, float* __restrict__ ws, HashWs O,
+                                                           float eps, float* __restrict__ ws, HashWs O, float* __restrict__ d_pts,
                                                            const int64_t* __restrict__ n_act) {
     __shared__ __attribute__((aligned(16))) float W[HP_WEIGHTS + 4];
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -457,6 +485,7 @@ __global__ __launch_bounds__(256) void hash_geo_bwd_kernel(const float* __restri
     stage_weights(W, hp);
     if (p >= na) return;
     const float x[3] = {pts[p * 3], pts[p * 3 + 1], pts[p * 3 + 2]};
+    float dxyz[3] = {0.f, 0.f, 0.f};
     for (int e = 0; e < HW_E; ++e) {
         float xe[3] = {x[0], x[1], x[2]};
         float dout[16];
@@ -504,7 +533,101 @@ __global__ __launch_bounds__(256) void hash_geo_bwd_kernel(const float* __restri
         // encoding adjoint, level-major [16][E n] float2: coalesced here and in hash_table_bwd_kernel
         DH_UNROLL for (int l = 0; l < HG_L; ++l)
             *reinterpret_cast<float2*>(ws + O.din + ((int64_t)l * HW_E * n + row) * 2) = make_float2(din[3 + 2 * l], din[4 + 2 * l]);
+        if (RAYS) { DH_UNROLL for (int c = 0; c < 3; ++c) dxyz[c] += din[c]; }
     }
+    if (RAYS) { DH_UNROLL for (int c = 0; c < 3; ++c) d_pts[p * 3 + c] = dxyz[c] / radius; }
+}
+
+// Point adjoint of the encoding (pose refinement): what the 16 levels of the E = 7 evaluations add to d loss / d x,
+//   d_pts[p][a] += sum_e sum_l (scale_l / (2 radius)) sum_corners (d w_corner / d pos_a) <table[corner], din_e[l]>
+// -- the derivative of the trilinear blend inside the cell (floor has derivative 0), what autograd gives on the oracle with the point as
+// a leaf.  Reads what hash_geo_bwd_kernel left (X01, DIN) and the table; per level hash_encode7_kernel's gathers: the centre cell's 8
+// corners fetched once, a shifted evaluation re-using them or the shared face.  No atomics: one thread per point walks the 16 levels and
+// adds them in ascending order onto the xyz share, so the result is bitwise the same from launch to launch.  (The other form -- a thread
+// per (point, level) as hash_encode7_kernel has it, level partials [16][n][3] in the workspace and a small kernel that adds them -- was
+// built and timed next to this one: 0.730 against 0.693 ms for the whole geometry backward at 262,144 points, 0.539 against 0.517 ms at
+// 194,034 packed ones; it also costs 48 n floats of workspace and a launch.  DESIGN_NEXT_ROWS.md section 28.)
+__device__ __forceinline__ void point_adjoint_level(const HashLevels& H, const float2* lvl, int l, int64_t p, int64_t n,
+                                                    const float* __restrict__ X, int64_t lde, const float2* __restrict__ D,
+                                                    float radius, float (&g)[3]) {
+    const float x0[3] = {X[p], X[lde + p], X[2 * lde + p]};
+    uint32_t g0[3];
+    float w0[3];
+    hg_cell(H, l, x0, g0, w0);
+    float2 cf[8];
+    DH_UNROLL for (int corner = 0; corner < 8; ++corner)
+        cf[corner] = lvl[hg_index_local(H, l, g0[0] + (corner & 1), g0[1] + ((corner >> 1) & 1), g0[2] + (corner >> 2))];
+    DH_UNROLL for (int c = 0; c < 3; ++c) g[c] = 0.f;
+    {
+        const float2 d = D[p];
+        float s[8];
+        DH_UNROLL for (int corner = 0; corner < 8; ++corner) s[corner] = fmaf(cf[corner].x, d.x, cf[corner].y * d.y);
+        DH_UNROLL for (int a = 0; a < 3; ++a) {
+            const int b = (a + 1) % 3, c = (a + 2) % 3;
+            float t = 0.f;
+            DH_UNROLL for (int q = 0; q < 4; ++q) {
+                const int c0 = ((q & 1) << b) | ((q >> 1) << c), c1 = c0 | (1 << a);
+                t = fmaf(((q & 1) ? w0[b] : 1.f - w0[b]) * ((q >> 1) ? w0[c] : 1.f - w0[c]), s[c1] - s[c0], t);
+            }
+            g[a] += t;
+        }
+    }
+    const float sc = H.scale[l];
+    DH_UNROLL for (int e = 1; e < HW_E; ++e) {
+        const int a = (e - 1) >> 1, b = (a + 1) % 3, c = (a + 2) % 3;
+        const int64_t row = (int64_t)e * n + p;
+        const float pos = X[a * lde + row] * sc + 0.5f;
+        const float fl = floorf(pos);
+        const float wa = pos - fl;
+        const uint32_t ga = (uint32_t)(int)fl;
+        const int delta = (int)(ga - g0[a]);
+        const float2 d = D[row];
+        float s[2][4];                                   // <corner value, din_e> of plane ba, in-plane corner q
+        DH_UNROLL for (int ba = 0; ba < 2; ++ba) {
+            const int t = delta + ba;                    // plane position relative to the centre cell: 0 / 1 = already held
+            const bool shared = (unsigned)t < 2u;
+            float2 v[4];
+            DH_UNROLL for (int q = 0; q < 4; ++q) {
+                const int c0 = ((q & 1) << b) | ((q >> 1) << c), c1 = c0 | (1 << a);
+                v[q].x = t ? cf[c1].x : cf[c0].x;
+                v[q].y = t ? cf[c1].y : cf[c0].y;
+            }
+            if (!shared) {
+                DH_UNROLL for (int q = 0; q < 4; ++q) {
+                    uint32_t cc[3];
+                    cc[a] = ga + ba; cc[b] = g0[b] + (q & 1); cc[c] = g0[c] + (q >> 1);
+                    v[q] = lvl[hg_index_local(H, l, cc[0], cc[1], cc[2])];
+                }
+            }
+            DH_UNROLL for (int q = 0; q < 4; ++q) s[ba][q] = fmaf(v[q].x, d.x, v[q].y * d.y);
+        }
+        const float wb0 = 1.f - w0[b], wb1 = w0[b], wc0 = 1.f - w0[c], wc1 = w0[c];
+        // along the shifted axis: the two planes' difference, blended in the plane
+        g[a] += (wb0 * wc0) * (s[1][0] - s[0][0]) + (wb1 * wc0) * (s[1][1] - s[0][1]) + (wb0 * wc1) * (s[1][2] - s[0][2])
+                + (wb1 * wc1) * (s[1][3] - s[0][3]);
+        // across it: the planes blended with (1 - wa, wa) first
+        float m[4];
+        DH_UNROLL for (int q = 0; q < 4; ++q) m[q] = fmaf(wa, s[1][q] - s[0][q], s[0][q]);
+        g[b] += wc0 * (m[1] - m[0]) + wc1 * (m[3] - m[2]);
+        g[c] += wb0 * (m[2] - m[0]) + wb1 * (m[3] - m[1]);
+    }
+    const float k = sc / (2.f * radius);
+    DH_UNROLL for (int c = 0; c < 3; ++c) g[c] *= k;
+}
+
+__global__ __launch_bounds__(256) void hash_point_adjoint_kernel(HashLevels H, const float* __restrict__ table,
+                                                                 const float* __restrict__ ws, HashWs O, int64_t n, float radius,
+                                                                 float* __restrict__ d_pts, const int64_t* __restrict__ n_act) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= active_rows(n_act, n)) return;
+    float t[3] = {d_pts[p * 3], d_pts[p * 3 + 1], d_pts[p * 3 + 2]};
+    for (int l = 0; l < HG_L; ++l) {
+        float g[3];
+        point_adjoint_level(H, reinterpret_cast<const float2*>(table) + H.offset[l], l, p, n, ws + O.x01, O.lde,
+                            reinterpret_cast<const float2*>(ws + O.din) + (int64_t)l * HW_E * n, radius, g);
+        DH_UNROLL for (int c = 0; c < 3; ++c) t[c] += g[c];
+    }
+    DH_UNROLL for (int c = 0; c < 3; ++c) d_pts[p * 3 + c] = t[c];
 }
 
 // Table gradient.  Float atomics execute at the memory side in 64-B requests (MI355X_MICROARCH.md "Global float
@@ -857,20 +980,35 @@ namespace dh {
 int64_t hash_workspace_floats(int64_t n) { return make_hash_ws(n).fix + ((int64_t)hashgrid_entries() * 2 + HG_FIX_FLAG_WORDS) * 2; }
 int64_t hash_infer_workspace_floats(int64_t n) { return make_hash_ws(n).lde * 36; }
 
+// d_dirs_pts null: the direction is not differentiated
 int launch_sh_color_bwd(const float* hp, const float* feat, const float* normals, const float* dirs, const float* d_color,
-                        int n_per_ray, int64_t n, float* ws, float* d_feat, float* d_normals, const int64_t* n_act,
-                        hipStream_t st) {
-    hipLaunchKernelGGL(sh_color_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, hp, feat, normals, dirs,
-                       d_color, n_per_ray, n, ws, make_hash_ws(n), d_feat, d_normals, n_act);
+                        int n_per_ray, int64_t n, float* ws, float* d_feat, float* d_normals, float* d_dirs_pts,
+                        const int64_t* n_act, hipStream_t st) {
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (d_dirs_pts)
+        hipLaunchKernelGGL(sh_color_bwd_kernel<true>, grid, dim3(256), 0, st, hp, feat, normals, dirs, d_color, n_per_ray, n, ws,
+                           make_hash_ws(n), d_feat, d_normals, d_dirs_pts, n_act);
+    else
+        hipLaunchKernelGGL(sh_color_bwd_kernel<false>, grid, dim3(256), 0, st, hp, feat, normals, dirs, d_color, n_per_ray, n, ws,
+                           make_hash_ws(n), d_feat, d_normals, d_dirs_pts, n_act);
     return ok();
 }
 
+// d_pts null: the point is not differentiated; else the geometry adjoint, then the encoding's point adjoint on top of its xyz share
 int launch_hash_geo_bwd(const float* params, const float* hp, const float* pts, const float* d_sdf, const float* d_feat,
-                        const float* d_grad, int64_t n, float radius, float eps, float* ws, const int64_t* n_act,
+                        const float* d_grad, int64_t n, float radius, float eps, float* ws, float* d_pts, const int64_t* n_act,
                         hipStream_t st) {
-    (void)params;
-    hipLaunchKernelGGL(hash_geo_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, hp, pts, d_sdf, d_feat,
-                       d_grad, n, radius, eps, ws, make_hash_ws(n), n_act);
+    const HashWs O = make_hash_ws(n);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (!d_pts) {
+        hipLaunchKernelGGL(hash_geo_bwd_kernel<false>, grid, dim3(256), 0, st, hp, pts, d_sdf, d_feat, d_grad, n, radius, eps, ws, O,
+                           d_pts, n_act);
+        return ok();
+    }
+    hipLaunchKernelGGL(hash_geo_bwd_kernel<true>, grid, dim3(256), 0, st, hp, pts, d_sdf, d_feat, d_grad, n, radius, eps, ws, O, d_pts,
+                       n_act);
+    hipLaunchKernelGGL(hash_point_adjoint_kernel, grid, dim3(256), 0, st, hashgrid_levels(), params + hash_param_off().table, ws, O, n,
+                       radius, d_pts, n_act);
     return ok();
 }
 

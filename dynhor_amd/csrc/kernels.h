@@ -97,6 +97,9 @@ int launch_render_bwd(const float* o, const float* d, const float* z, const floa
                       int n, const float* d_color, const float* d_wsum, const float* d_weights, const float* d_gradients,
                       const float* d_nmap, const float* eik_coef, float* d_sdf, float* d_normals, float* d_colors,
                       float* d_inv_s, float* d_rays_d, const int64_t* seg_off, const int32_t* seg_cnt, hipStream_t st);
+// per-ray fold of the point adjoints over packed rays (pose refinement on the occupancy-grid sampler)
+int launch_ray_adjoint_packed(const float* d_pts, const float* d_dirs_pts, const float* t_start, float step, const int64_t* seg_off,
+                              const int32_t* seg_cnt, int64_t B, float* d_rays_o, float* d_rays_d, hipStream_t st);
 // occupancy-grid marching (march.hip)
 int launch_march_count(const float* o, const float* d, const float* near, const float* far, const float* u, const uint8_t* occ,
                        int res, float radius, float step, float half_step, int max_samples, int64_t B, int32_t* cnt,
@@ -169,10 +172,13 @@ int launch_hash_geo_fwd(const float* params, const float* hp, const float* pts, 
                         float* ws, int save, float* sdf, float* feat, float* grad, const int64_t* n_act, hipStream_t st);
 int launch_sh_color_fwd(const float* hp, const float* feat, const float* normals, const float* dirs, int n_per_ray,
                         int64_t n, float* color, const int64_t* n_act, hipStream_t st);
+// d_dirs_pts / d_pts (pose refinement; null: not formed): the adjoints w.r.t. the view direction and the sample point, [n,3] each
 int launch_sh_color_bwd(const float* hp, const float* feat, const float* normals, const float* dirs, const float* d_color,
-                        int n_per_ray, int64_t n, float* ws, float* d_feat, float* d_normals, const int64_t* n_act, hipStream_t st);
+                        int n_per_ray, int64_t n, float* ws, float* d_feat, float* d_normals, float* d_dirs_pts, const int64_t* n_act,
+                        hipStream_t st);
 int launch_hash_geo_bwd(const float* params, const float* hp, const float* pts, const float* d_sdf, const float* d_feat,
-                        const float* d_grad, int64_t n, float radius, float eps, float* ws, const int64_t* n_act, hipStream_t st);
+                        const float* d_grad, int64_t n, float radius, float eps, float* ws, float* d_pts, const int64_t* n_act,
+                        hipStream_t st);
 int launch_hash_weight_grads(const float* params, const float* hp, int64_t n, float* ws, float* grad, const int64_t* n_act,
                              int parts, hipStream_t st);
 

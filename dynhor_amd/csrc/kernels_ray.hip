@@ -449,7 +449,50 @@ __global__ __launch_bounds__(256) void render_bwd_kernel(const float* __restrict
     }
 }
 
+// ---------------------------------------------------------------- per-ray fold of the point adjoints, packed rays (pose refinement)
+// x_k = o + t_k d with t_k = t_start_k + step / 2 (the marcher's mid-point; the sample depths are constants):
+//   d_rays_o = sum_k d_pts_k,   d_rays_d += sum_k (t_k d_pts_k + d_dirs_pts_k)
+// One wave per ray.  Each lane adds its samples lane, lane + 64, .. in ascending k in fp64, then the 64 lanes fold in a fixed xor
+// butterfly: no atomics, bitwise reproducible.  A ray without samples gets zeros (d_rays_d keeps what it held: 0 is added).  The count
+// is read from seg_cnt on the device and clamped like the scan's.
+__global__ __launch_bounds__(256) void ray_adjoint_packed_kernel(const float* __restrict__ d_pts, const float* __restrict__ d_dirs_pts,
+                                                                 const float* __restrict__ t_start, float step,
+                                                                 const int64_t* __restrict__ seg_off, const int32_t* __restrict__ seg_cnt,
+                                                                 int64_t B, float* __restrict__ d_rays_o, float* __restrict__ d_rays_d) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t ray = (int64_t)blockIdx.x * 4 + wave;
+    if (ray >= B) return;                                 // wave-uniform
+    const int64_t rb = seg_off[ray];
+    const int n = min(seg_cnt[ray], 128 * RENDER_MAX_CHUNKS);
+    const float half = 0.5f * step;
+    double so[3] = {0.0, 0.0, 0.0}, sd[3] = {0.0, 0.0, 0.0};
+    for (int k = lane; k < n; k += 64) {
+        const double t = (double)(t_start[rb + k] + half);
+        DH_UNROLL for (int c = 0; c < 3; ++c) {
+            const double g = (double)d_pts[(rb + k) * 3 + c];
+            so[c] += g;
+            sd[c] += fma(t, g, (double)d_dirs_pts[(rb + k) * 3 + c]);
+        }
+    }
+    DH_UNROLL for (int c = 0; c < 3; ++c) {
+        DH_UNROLL for (int off = 32; off > 0; off >>= 1) { so[c] += __shfl_xor(so[c], off); sd[c] += __shfl_xor(sd[c], off); }
+    }
+    if (lane == 0) {
+        DH_UNROLL for (int c = 0; c < 3; ++c) {
+            d_rays_o[ray * 3 + c] = (float)so[c];
+            d_rays_d[ray * 3 + c] = (float)((double)d_rays_d[ray * 3 + c] + sd[c]);
+        }
+    }
+}
+
 // ================================================================ launchers
+
+int launch_ray_adjoint_packed(const float* d_pts, const float* d_dirs_pts, const float* t_start, float step, const int64_t* seg_off,
+                              const int32_t* seg_cnt, int64_t B, float* d_rays_o, float* d_rays_d, hipStream_t st) {
+    hipLaunchKernelGGL(ray_adjoint_packed_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, d_pts, d_dirs_pts, t_start, step,
+                       seg_off, seg_cnt, B, d_rays_o, d_rays_d);
+    return ok();
+}
 
 int launch_gen_rays(const uint8_t* rgb, const int8_t* label, const uint8_t* normal, const float* R, const float* T,
                     const float* Kinv, int H, int W, int frame, const int64_t* px, const int64_t* py, int64_t B,

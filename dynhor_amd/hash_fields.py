@@ -174,12 +174,15 @@ class HashNeuSRenderer(NeuSRenderer):
     sampler = "hierarchical": the NeuS 64 + 64 sampler of the fp32 family (four no-grad SDF passes per iteration).
     sampler = "occgrid": instant-nsr-pl's occupancy-grid marching with packed variable-length rays (csrc/march.hip): the
     iteration evaluates the networks only on the samples that fall into occupied cells; the fused training step and the
-    forward-only frame renderer take this path, render() (the autograd dict API) stays on the hierarchical sampler."""
+    forward-only frame renderer take this path, render() (the autograd dict API) stays on the hierarchical sampler.
+    ray_grads = True (pose refinement; the Runner sets it with train.refine_poses): the packed buffers also hold the per-point
+    adjoints d_pts / d_dirs_pts [capacity,3], and train_step_core(..., ray_grads=True) runs on the occupancy-grid sampler too.  The
+    hierarchical sampler needs no buffers and takes ray_grads per call, whatever this says."""
 
     def __init__(self, nerf, sdf_network: HashSDFNetwork, deviation_network: SingleVarianceNetwork,
                  color_network: SHRenderingNetwork, *args, sampler="hierarchical", march_samples_per_ray=512, grid_res=128,
                  grid_update_every=16, max_samples=128, max_samples_per_ray=1024, reproducible_table_grad=True,
-                 grid_refresh="all", grid_warmup_steps=256, **kwargs):
+                 grid_refresh="all", grid_warmup_steps=256, ray_grads=False, **kwargs):
         if not isinstance(sdf_network, HashSDFNetwork) or not isinstance(color_network, SHRenderingNetwork):
             raise TypeError("HashNeuSRenderer needs HashSDFNetwork + SHRenderingNetwork")
         if sampler not in ("hierarchical", "occgrid"):
@@ -190,6 +193,7 @@ class HashNeuSRenderer(NeuSRenderer):
         self.radius = sdf_network.radius
         self.fd_eps = sdf_network.fd_eps
         self.sampler = sampler
+        self.ray_grads = bool(ray_grads)
         # the table scatter in fixed point (include/dynhor_hip.h dh_hash_weight_grads_parts, parts bit 4; the default: it costs nothing,
         # profiles/r05_hash_reproducible_scatter.json): the family's training step is bitwise reproducible like the NeuS family's.
         # False: float atomics, the library's only order-dependent sums (kept for comparison)
@@ -269,12 +273,22 @@ class HashNeuSRenderer(NeuSRenderer):
             torch.cuda.current_stream(grad.device).wait_stream(side)
 
     def _net_backward(self, s, d_sdf, d_normals, d_colors, grad):
+        """The parent's contract.  With s.ray_grads the `_rays` entries run in place of the plain ones (own timer tags) and leave s.d_pts,
+        s.d_dirs_pts [P,3] (packed rays: in the buffers, rows past n_active untouched); the parameter path is bitwise the same."""
         L, T, st, P = _lib.lib(), self.timer, self.store, s.P
         d_feat = torch.empty(P, 13, device=s.pts.device) if s.buffers is None else s.buffers.d_feat
-        T("hash_color_backward", L.dh_hash_color_backward, _p(st.packed), _p(s.feat), _p(s.normals), _p(s.rays_d),
-          _p(d_colors), s.n, P, _p(s.ws), _p(d_feat), _p(d_normals), _p(s.n_active), _lib.stream())
-        T("hash_geo_backward", L.dh_hash_geo_backward, _p(st.flat), _p(st.packed), _p(s.pts), _p(d_sdf), _p(d_feat),
-          _p(d_normals), P, self.radius, self.fd_eps, _p(s.ws), _p(s.n_active), _lib.stream())
+        if s.ray_grads:
+            s.d_pts = torch.empty(P, 3, device=s.pts.device) if s.buffers is None else s.buffers.d_pts
+            s.d_dirs_pts = torch.empty(P, 3, device=s.pts.device) if s.buffers is None else s.buffers.d_dirs_pts
+            T("hash_color_backward_rays", L.dh_hash_color_backward_rays, _p(st.packed), _p(s.feat), _p(s.normals), _p(s.rays_d),
+              _p(d_colors), s.n, P, _p(s.ws), _p(d_feat), _p(d_normals), _p(s.n_active), _p(s.d_dirs_pts), _lib.stream())
+            T("hash_geo_backward_rays", L.dh_hash_geo_backward_rays, _p(st.flat), _p(st.packed), _p(s.pts), _p(d_sdf), _p(d_feat),
+              _p(d_normals), P, self.radius, self.fd_eps, _p(s.ws), _p(s.n_active), _p(s.d_pts), _lib.stream())
+        else:
+            T("hash_color_backward", L.dh_hash_color_backward, _p(st.packed), _p(s.feat), _p(s.normals), _p(s.rays_d),
+              _p(d_colors), s.n, P, _p(s.ws), _p(d_feat), _p(d_normals), _p(s.n_active), _lib.stream())
+            T("hash_geo_backward", L.dh_hash_geo_backward, _p(st.flat), _p(st.packed), _p(s.pts), _p(d_sdf), _p(d_feat),
+              _p(d_normals), P, self.radius, self.fd_eps, _p(s.ws), _p(s.n_active), _lib.stream())
         self._weight_grads(P, s.ws, grad, _p(s.n_active))
 
     # ------------------------------------------------------------------ occupancy-grid marching path (packed rays)
@@ -307,6 +321,8 @@ class HashNeuSRenderer(NeuSRenderer):
                                   ray_idx=z(cap, dt=torch.int32), sdf=z(cap), normals=z(cap, 3), colors=z(cap, 3), feat=z(cap, 13),
                                   weights=z(cap), cdf=z(cap), inside=z(cap), d_sdf=z(cap), d_normals=z(cap, 3), d_colors=z(cap, 3), d_weights=z(cap),
                                   d_feat=z(cap, 13), caps=torch.tensor(self._cap_ladder, dtype=torch.int32, device=dev))
+            if self.ray_grads:
+                buf.d_pts, buf.d_dirs_pts = z(cap, 3), z(cap, 3)
             self._packed_buf[role] = buf
         return buf
 
@@ -354,13 +370,13 @@ class HashNeuSRenderer(NeuSRenderer):
                                t_start=buf.t_start, pts=buf.pts, dirs=buf.dirs, ray_idx=buf.ray_idx, buf=buf)
 
     @torch.no_grad()
-    def _forward_packed(self, rays_o, rays_d, m, cos_anneal_ratio, background_rgb, want_nmap, infer_only=False):
+    def _forward_packed(self, rays_o, rays_d, m, cos_anneal_ratio, background_rgb, want_nmap, infer_only=False, ray_grads=False):
         L, st = _lib.lib(), self.store
         packed = st.ensure_packed()
         dev = rays_o.device
         B, buf = rays_o.shape[0], m.buf
         # the network stages see the whole capacity as points with a direction each, m.n_dev of them in use, outputs in the buffers
-        s = self.net_state(m.pts, m.dirs, 1, 0 if infer_only else 1, n_active=m.n_dev, buffers=buf)
+        s = self.net_state(m.pts, m.dirs, 1, 0 if infer_only else (2 if ray_grads else 1), n_active=m.n_dev, buffers=buf)
         s.B, s.m, s.car, s.bg, s.rays_o, s.ray_dirs = B, m, float(cos_anneal_ratio), background_rgb, rays_o, rays_d      # B rays
         self._net_forward(s, packed)
         s.inv_s = st.inv_s()
@@ -387,13 +403,22 @@ class HashNeuSRenderer(NeuSRenderer):
         m, B, buf = s.m, s.B, s.buffers
         d_sdf, d_normals, d_colors = buf.d_sdf.zero_(), buf.d_normals.zero_(), buf.d_colors.zero_()
         d_inv_s = torch.empty(B, device=s.color.device)
-        _lib.check(_lib.lib().dh_render_scan_bwd_packed(
-            _p(s.rays_o), _p(s.ray_dirs), _p(m.t_start), _p(s.sdf), _p(s.normals), _p(s.colors), _p(s.inv_s), s.car, m.step, _p(s.bg), B,
-            _p(m.off), _p(m.cnt), _p(d_color), _p(d_wsum), _p(d_weights), _p(None), _p(d_nmap), _p(eik_coef), _p(d_sdf), _p(d_normals),
-            _p(d_colors), _p(d_inv_s), _lib.stream()))
+        L = _lib.lib()
+        scan = (_p(s.rays_o), _p(s.ray_dirs), _p(m.t_start), _p(s.sdf), _p(s.normals), _p(s.colors), _p(s.inv_s), s.car, m.step, _p(s.bg), B,
+                _p(m.off), _p(m.cnt), _p(d_color), _p(d_wsum), _p(d_weights), _p(None), _p(d_nmap), _p(eik_coef), _p(d_sdf), _p(d_normals),
+                _p(d_colors), _p(d_inv_s))
+        if s.ray_grads:
+            s.d_rays_o, s.d_rays_d = torch.empty(B, 3, device=s.color.device), torch.empty(B, 3, device=s.color.device)
+            _lib.check(L.dh_render_scan_bwd_packed_rays(*scan, _p(s.d_rays_d), _lib.stream()))
+        else:
+            _lib.check(L.dh_render_scan_bwd_packed(*scan, _lib.stream()))
         grad = self.store.grad_bucket()
         self._net_backward(s, d_sdf, d_normals, d_colors, grad)
         self._variance_grad(d_inv_s, grad)
+        if s.ray_grads:
+            # per-ray fold of the point adjoints onto the scan's d_rays_d (x = o + (t_start + step / 2) d, sample depths constant)
+            self.timer("ray_adjoint_packed", L.dh_ray_adjoint_packed, _p(s.d_pts), _p(s.d_dirs_pts), _p(m.t_start), m.step, _p(m.off),
+                       _p(m.cnt), B, _p(s.d_rays_o), _p(s.d_rays_d), _lib.stream())
         return grad
 
     @torch.no_grad()
@@ -401,12 +426,18 @@ class HashNeuSRenderer(NeuSRenderer):
                         background_rgb=None, t_rand=None, **kw):
         """The parent's step on the hierarchical sampler; on the occupancy-grid sampler the packed one: grid update, march, forward,
         the parent's loss stage on the packed description of the samples (the priors of dh_prior_loss_packed: prior_depth,
-        depth_weight, depth_delta, normal_skip_missing as the parent takes them), backward."""
+        depth_weight, depth_delta, normal_skip_missing as the parent takes them), backward.  ray_grads (a renderer built with
+        ray_grads=True): the backward also folds the per-point adjoints into self.last_ray_grads = (d_rays_o, d_rays_d, d_R or None) as
+        the parent leaves them, rays without samples getting zeros; self.last_partner_pose_grads = None (no correspondence term here)."""
         if self.sampler != "occgrid":
             return super().train_step_core(rays, near, far, R, cos_anneal_ratio, igr_weight, mask_weight, normal_weight,
                                            background_rgb=background_rgb, t_rand=t_rand, **kw)
-        if kw.get("corr") is not None or kw.pop("ray_grads", False):
-            raise ValueError("the correspondence term / pose refinement run on the hierarchical sampler")
+        if kw.get("corr") is not None:
+            raise ValueError("the correspondence term runs on the hierarchical sampler")
+        ray_grads = bool(kw.pop("ray_grads", False))
+        if ray_grads and not self.ray_grads:
+            raise ValueError("pose refinement on the occupancy-grid sampler needs the adjoint buffers: build the renderer with "
+                             "ray_grads=True (the Runner does with train.refine_poses)")
         if self._march_iter % self.grid_update_every == 0:
             self.update_grid()
         self._march_iter += 1
@@ -419,12 +450,17 @@ class HashNeuSRenderer(NeuSRenderer):
         finally:
             self._in_train_step = False
         bg = None if background_rgb is None else background_rgb.reshape(-1).contiguous().float()
-        s = self._forward_packed(rays_o, rays_d, m, cos_anneal_ratio, bg, want_nmap=normal_weight > 0.0)
+        s = self._forward_packed(rays_o, rays_d, m, cos_anneal_ratio, bg, want_nmap=normal_weight > 0.0, ray_grads=ray_grads)
         a = self._loss_stage(s, rays, R, m.t_start, m.step, igr_weight, mask_weight, normal_weight,
                              packed=(m.off, m.cnt, self._cap_ladder[0]), d_weights=m.buf.d_weights, **kw)
         self._backward_packed(s, a.d_color, a.d_wsum, a.d_nmap, a.eik_coef, a.d_weights)
         self.last_state = s
         self._last_march = m
+        if ray_grads:
+            # n_cam = R n_obj enters the normal loss directly (the parent's formula)
+            d_R = (a.d_nmap @ a.R.T).T @ s.nmap if normal_weight > 0.0 and a.R is not None else None
+            self.last_partner_pose_grads = None
+            self.last_ray_grads = (s.d_rays_o, s.d_rays_d, d_R)
         return a.stats
 
     @property

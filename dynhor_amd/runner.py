@@ -218,6 +218,11 @@ class Runner:
         self.nerf_outside = None
         self.store = store_cls(self.sdf_network, self.deviation_network, self.color_network, self.device)
         extra = dict(self.conf["model"]["hash_renderer"]) if family == "hash" else {}
+        if family == "hash" and tr["refine_poses"]:
+            if self.corr_weight > 0.0 and extra.get("sampler") == "occgrid":
+                raise ValueError("train.corr_weight > 0 with model.family 'hash', model.hash_renderer.sampler 'occgrid' and "
+                                 "train.refine_poses is not supported: the correspondence term runs on the hierarchical sampler")
+            extra["ray_grads"] = True        # the packed path's adjoint buffers (hash_fields.HashNeuSRenderer)
         ar = self.conf["model"].get("arithmetic")
         if ar is not None:
             from . import _lib

@@ -304,6 +304,21 @@ int dh_render_scan_bwd_packed(const float* rays_o, const float* rays_d, const fl
                               const float* d_color, const float* d_weight_sum, const float* d_weights, const float* d_gradients,
                               const float* d_normal_map, const float* eik_coef, float* d_sdf, float* d_normals, float* d_colors,
                               float* d_inv_s, void* stream);
+/* Pose refinement on packed rays.  dh_render_scan_bwd_packed_rays = dh_render_scan_bwd_packed + d_rays_d [B,3] (written): the adjoint
+ * of the ray direction through true_cos = d . n, as dh_render_scan_bwd_rays forms it on dense rays; every shared output is bitwise that
+ * of dh_render_scan_bwd_packed.  dh_ray_adjoint_packed folds the per-point adjoints of the network stages into the rays: with
+ * t_k = t_start_k + step / 2, the marcher's mid-point x_k = o + t_k d (sample depths are constants),
+ *   d_rays_o [B,3] = sum_k d_pts_k (written),   d_rays_d_accum [B,3] += sum_k (t_k d_pts_k + d_dirs_pts_k)
+ * over the samples of each ray (seg_cnt read on the device and clamped to 1024 like the scan's).  One wave per ray, fp64 sums in a fixed
+ * order, no atomics: bitwise reproducible; a ray without samples gets zeros in d_rays_o and keeps d_rays_d_accum.  B == 0 is a no-op. */
+int dh_render_scan_bwd_packed_rays(const float* rays_o, const float* rays_d, const float* t_start, const float* sdf, const float* normals,
+                                   const float* colors, const float* inv_s, float cos_anneal_ratio, float step,
+                                   const float* background_rgb, int64_t B, const int64_t* seg_off, const int32_t* seg_cnt,
+                                   const float* d_color, const float* d_weight_sum, const float* d_weights, const float* d_gradients,
+                                   const float* d_normal_map, const float* eik_coef, float* d_sdf, float* d_normals, float* d_colors,
+                                   float* d_inv_s, float* d_rays_d, void* stream);
+int dh_ray_adjoint_packed(const float* d_pts, const float* d_dirs_pts, const float* t_start, float step, const int64_t* seg_off,
+                          const int32_t* seg_cnt, int64_t B, float* d_rays_o, float* d_rays_d_accum, void* stream);
 
 /* Priors that carry a validity, on the training path: a depth term on the expected depth of a ray and the normal term of
  * dh_neus_loss restricted to the rays that have a normal (DESIGN_NEXT_ROWS.md section 27).  dh_prior_loss takes dense rays
@@ -403,6 +418,26 @@ int dh_hash_geo_backward(const float* params, const float* packed, const float* 
                          const int64_t* n_active, void* stream);
 int dh_hash_weight_grads(const float* params, const float* packed, int64_t n, float* ws, float* grad, const int64_t* n_active,
                          void* stream);
+/* Pose refinement: the same two calls, which also leave the adjoints w.r.t. the view direction and the sample point.  Every other
+ * output and every workspace row is bitwise what dh_hash_color_backward / dh_hash_geo_backward write, so dh_hash_weight_grads follows
+ * unchanged.  No float atomics: both results are bitwise the same from launch to launch.  Rows >= *n_active are not touched.
+ *   dh_hash_color_backward_rays: d_dirs_pts [n,3], one row PER POINT (written): the first layer's input adjoint of the 16 SH columns
+ *       chained through the analytic gradient of the SH-4 polynomials (plain polynomials of an unnormalised direction).  The caller sums
+ *       the n_per_ray rows of a ray; with n_per_ray = 1 a row is the sample's own direction.
+ *   dh_hash_geo_backward_rays: d_pts [n,3] (written) = d loss / d x of the sample point x through the E = 7 evaluations x_e (centre,
+ *       +-eps per axis; d x_e / d x = I) with din_e the adjoint of evaluation e's 35 inputs:
+ *         the xyz inputs   in[c] = x_c / radius:            (1 / radius) sum_e din_e[0..2]
+ *         the 16 levels    pos = x01 scale_l + 0.5:         sum_e sum_l (scale_l / (2 radius)) sum_corners (d w_corner / d pos) <table[corner], din_e[l]>
+ *       -- the derivative of the trilinear blend inside the cell; floor has derivative 0, so the result jumps at cell faces (the value
+ *       does not).  ONE call launches two kernels: the geometry adjoint, which also adds up the xyz share, and a gather of one
+ *       thread per point that walks the 16 levels in ascending order (per level the gathers of the forward's encoder: the centre cell's 8
+ *       corners once, a shifted evaluation re-using them or the shared face) and adds them on top.  It needs no workspace of its own. */
+int dh_hash_color_backward_rays(const float* packed, const float* feature, const float* normals, const float* dirs,
+                                const float* d_color, int n_per_ray, int64_t n, float* ws, float* d_feature, float* d_normals,
+                                const int64_t* n_active, float* d_dirs_pts, void* stream);
+int dh_hash_geo_backward_rays(const float* params, const float* packed, const float* pts, const float* d_sdf,
+                              const float* d_feature, const float* d_normals, int64_t n, float radius, float eps, float* ws,
+                              const int64_t* n_active, float* d_pts, void* stream);
 /* The same in two parts, for data-parallel callers: parts & 1 writes the table gradient (the leading dh_hashgrid_entries() x 2 floats
  * of grad: 49 MB), parts & 2 the five small linears.  Calling the table part, starting its all-reduce on a side stream, then the
  * linears, hides the large collective behind the small weight-gradient GEMMs (dynhor_amd/hash_fields.py).
