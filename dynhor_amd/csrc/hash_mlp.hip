@@ -48,39 +48,52 @@ __device__ __forceinline__ void stage_weights(float* lds, const float* __restric
     __syncthreads();
 }
 
-__device__ __forceinline__ void hg_cell(const HashLevels& H, int l, const float (&x01)[3], uint32_t (&g)[3], float (&w)[3]) {
-    const float s = H.scale[l];
+// ---------------------------------------------------------------- geometry network, one evaluation
+// The E = 7 evaluation points of a sample at world position x: e = 0 the centre, e = 1 + 2 axis + sign the point shifted by +eps
+// (sign 0) or -eps (sign 1) along that axis.  xe: its world position; x01 = (xe + radius) / (2 radius): its position in the scene box
+// [0,1]^3, radius the box's half-size.  CONTRACT: this is the only place that forms x01.  The forward encoder floors x01 * scale + 0.5
+// computed from pts; the table scatter and the point adjoint floor the X01 rows the geometry backward stored from here.  All three must
+// floor the same fp32 value, or the gradients of a sample near a cell face go to the neighbouring cell at the fine levels.
+__device__ __forceinline__ void eval_point(int e, const float (&x)[3], float eps, float radius, float (&xe)[3], float (&x01)[3]) {
     DH_UNROLL for (int c = 0; c < 3; ++c) {
-        const float pos = x01[c] * s + 0.5f;
-        const float f = floorf(pos);
-        w[c] = pos - f;
-        g[c] = (uint32_t)(int)f;
+        xe[c] = (e > 0 && c == (e - 1) >> 1) ? x[c] + ((e - 1) & 1 ? -eps : eps) : x[c];
+        x01[c] = (xe[c] + radius) / (2.f * radius);
     }
 }
 
-// ---------------------------------------------------------------- geometry network, one evaluation
-// x: world position; radius: scene box half-size (x01 = (x + r) / 2r).  FULL: all 13 outputs, else sdf only.
+// pre-activation of hidden unit j of the geometry MLP: 36-wide dot (35 inputs + a padding column) plus bias, weights in LDS
+__device__ __forceinline__ float geo_hidden_pre(const float* W, int j, const float (&in)[36]) {
+    const f32x4* wr = reinterpret_cast<const f32x4*>(W + HP_G0 + j * 36);
+    float a = W[HP_G0B + j];
+    DH_UNROLL for (int k4 = 0; k4 < 9; ++k4) {
+        const f32x4 w = wr[k4];
+        a = fmaf(w[0], in[4 * k4], a); a = fmaf(w[1], in[4 * k4 + 1], a);
+        a = fmaf(w[2], in[4 * k4 + 2], a); a = fmaf(w[3], in[4 * k4 + 3], a);
+    }
+    return a;
+}
+
+// the geometry MLP on one input (xyz in [-1,1], 32 encodings, padding); FULL: all 13 outputs, else sdf only
 template <bool FULL>
-__device__ __forceinline__ void geo_eval(const HashLevels& H, const float* __restrict__ table, const float* W,
-                                         const float (&x)[3], float radius, float (&out)[HM_GOUT]) {
-    float in[36];
-    float x01[3];
-    DH_UNROLL for (int c = 0; c < 3; ++c) { x01[c] = (x[c] + radius) / (2.f * radius); in[c] = x01[c] * 2.f - 1.f; }
-    DH_UNROLL for (int l = 0; l < HG_L; ++l) hg_encode_level(H, table, l, x01, in[3 + 2 * l], in[4 + 2 * l]);
-    in[35] = 0.f;
+__device__ __forceinline__ void geo_mlp(const float* W, const float (&in)[36], float (&out)[HM_GOUT]) {
     DH_UNROLL for (int c = 0; c < HM_GOUT; ++c) out[c] = W[HP_G1B + c];
     for (int j = 0; j < HM_HID; ++j) {
-        const f32x4* wr = reinterpret_cast<const f32x4*>(W + HP_G0 + j * 36);
-        float a = W[HP_G0B + j];
-        DH_UNROLL for (int k4 = 0; k4 < 9; ++k4) {
-            const f32x4 w = wr[k4];
-            a = fmaf(w[0], in[4 * k4], a); a = fmaf(w[1], in[4 * k4 + 1], a);
-            a = fmaf(w[2], in[4 * k4 + 2], a); a = fmaf(w[3], in[4 * k4 + 3], a);
-        }
-        const float h = softplus100(a);
+        const float h = softplus100(geo_hidden_pre(W, j, in));
         out[0] = fmaf(W[HP_G1 + j], h, out[0]);
         if (FULL) { DH_UNROLL for (int c = 1; c < HM_GOUT; ++c) out[c] = fmaf(W[HP_G1 + c * 64 + j], h, out[c]); }
     }
+}
+
+// one evaluation at x from the table: the 16 levels' encodings, then the MLP
+template <bool FULL>
+__device__ __forceinline__ void geo_eval(const HashLevels& H, const float* __restrict__ table, const float* W,
+                                         const float (&x)[3], float radius, float (&out)[HM_GOUT]) {
+    float in[36], xe[3], x01[3];
+    eval_point(0, x, 0.f, radius, xe, x01);
+    DH_UNROLL for (int c = 0; c < 3; ++c) in[c] = x01[c] * 2.f - 1.f;
+    DH_UNROLL for (int l = 0; l < HG_L; ++l) hg_encode_level(H, table, l, x01, in[3 + 2 * l], in[4 + 2 * l]);
+    in[35] = 0.f;
+    geo_mlp<FULL>(W, in, out);
 }
 
 // sdf only (hierarchical up-sampling evaluations)
@@ -109,22 +122,45 @@ __global__ __launch_bounds__(256) void hash_sdf_nograd_kernel(HashLevels H, cons
 // it: levels 0 and 1 -- 16^3 and 23^3 entries = 32 / 95 KiB, the only ones that fit -- launched apart with persistent workgroups
 // that copy the level's slice into LDS and gather from there.  At 262,144 points the staging costs more than the L1 / L2 hits it
 // replaces: hash_geo_forward 0.48 vs 0.44 ms on one box, so the single launch below stays)
-__device__ __forceinline__ uint32_t hg_index_local(const HashLevels& H, int l, uint32_t x, uint32_t y, uint32_t z) {
-    const uint32_t res = H.res[l];
-    return H.dense[l] ? ((x + y * res + z * res * res) % H.size[l]) : (((x * 1u) ^ (y * 2654435761u) ^ (z * 805459861u)) & (HG_T - 1));
+
+// The 7-point stencil gather, shared by the forward encoder and the point adjoint.  stencil_centre: the 8 corners of the centre cell g0,
+// cf[dx + 2 dy + 4 dz].  stencil_plane: the four corners v[q] of plane ba (0: at ga, 1: at ga + 1) of the cell that an evaluation
+// shifted along axis a lies in (ga, delta: hg_shift), q = (bit along b) + 2 (bit along c) with b = (a + 1) % 3, c = (a + 2) % 3.  A
+// plane that coincides with a face of the centre cell is taken from cf; any other is gathered.
+__device__ __forceinline__ void stencil_centre(const HashLevels& H, const float2* lvl, int l, const uint32_t (&g0)[3], float2 (&cf)[8]) {
+    DH_UNROLL for (int corner = 0; corner < 8; ++corner)
+        cf[corner] = lvl[hg_index_local(H, l, g0[0] + (corner & 1), g0[1] + ((corner >> 1) & 1), g0[2] + (corner >> 2))];
 }
+__device__ __forceinline__ void stencil_plane(const HashLevels& H, const float2* lvl, int l, const uint32_t (&g0)[3],
+                                              const float2 (&cf)[8], int a, uint32_t ga, int delta, int ba, float2 (&v)[4]) {
+    const int b = (a + 1) % 3, c = (a + 2) % 3;
+    const int t = delta + ba;                            // plane position relative to the centre cell: 0 / 1 = already held
+    const bool shared = (unsigned)t < 2u;
+    DH_UNROLL for (int q = 0; q < 4; ++q) {
+        const int c0 = ((q & 1) << b) | ((q >> 1) << c), c1 = c0 | (1 << a);
+        v[q].x = t ? cf[c1].x : cf[c0].x;
+        v[q].y = t ? cf[c1].y : cf[c0].y;
+    }
+    if (!shared) {
+        DH_UNROLL for (int q = 0; q < 4; ++q) {
+            uint32_t cc[3];
+            cc[a] = ga + ba; cc[b] = g0[b] + (q & 1); cc[c] = g0[c] + (q >> 1);
+            v[q] = lvl[hg_index_local(H, l, cc[0], cc[1], cc[2])];
+        }
+    }
+}
+
 __device__ __forceinline__ void encode7_point(const HashLevels& H, const float2* lvl, int l, int64_t p,
                                               const float* __restrict__ pts, int64_t n, float radius, float eps,
                                               float* __restrict__ gin, int64_t lde) {
     const float x[3] = {pts[p * 3], pts[p * 3 + 1], pts[p * 3 + 2]};
-    float x01[3];
-    DH_UNROLL for (int c = 0; c < 3; ++c) x01[c] = (x[c] + radius) / (2.f * radius);
+    float xe[3], x01[3];
+    eval_point(0, x, eps, radius, xe, x01);
     uint32_t g0[3];
     float w0[3];
     hg_cell(H, l, x01, g0, w0);
     float2 cf[8];
-    DH_UNROLL for (int corner = 0; corner < 8; ++corner)
-        cf[corner] = lvl[hg_index_local(H, l, g0[0] + (corner & 1), g0[1] + ((corner >> 1) & 1), g0[2] + (corner >> 2))];
+    stencil_centre(H, lvl, l, g0, cf);
     float* o0 = gin + (int64_t)(3 + 2 * l) * lde + p;
     float* o1 = o0 + lde;
     {
@@ -140,30 +176,13 @@ __device__ __forceinline__ void encode7_point(const HashLevels& H, const float2*
     const float s = H.scale[l];
     DH_UNROLL for (int e = 1; e < 7; ++e) {
         const int a = (e - 1) >> 1, b = (a + 1) % 3, c = (a + 2) % 3;
-        const float xe = x[a] + ((e - 1) & 1 ? -eps : eps);
-        const float pos = ((xe + radius) / (2.f * radius)) * s + 0.5f;
-        const float fl = floorf(pos);
-        const float wa = pos - fl;
-        const uint32_t ga = (uint32_t)(int)fl;
-        const int delta = (int)(ga - g0[a]);
+        eval_point(e, x, eps, radius, xe, x01);
+        const auto [wa, ga, delta] = hg_shift(s, x01[a], g0[a]);
         float a0 = 0.f, a1 = 0.f;
         DH_UNROLL for (int ba = 0; ba < 2; ++ba) {
-            const int t = delta + ba;                    // plane position relative to the centre cell: 0 / 1 = already held
-            const bool shared = (unsigned)t < 2u;
             const float wpa = ba ? wa : 1.f - wa;
             float2 v[4];
-            DH_UNROLL for (int q = 0; q < 4; ++q) {
-                const int c0 = ((q & 1) << b) | ((q >> 1) << c), c1 = c0 | (1 << a);
-                v[q].x = t ? cf[c1].x : cf[c0].x;
-                v[q].y = t ? cf[c1].y : cf[c0].y;
-            }
-            if (!shared) {
-                DH_UNROLL for (int q = 0; q < 4; ++q) {
-                    uint32_t cc[3];
-                    cc[a] = ga + ba; cc[b] = g0[b] + (q & 1); cc[c] = g0[c] + (q >> 1);
-                    v[q] = lvl[hg_index_local(H, l, cc[0], cc[1], cc[2])];
-                }
-            }
+            stencil_plane(H, lvl, l, g0, cf, a, ga, delta, ba, v);
             DH_UNROLL for (int q = 0; q < 4; ++q) {
                 const float wt = wpa * ((q & 1) ? w0[b] : 1.f - w0[b]) * ((q >> 1) ? w0[c] : 1.f - w0[c]);
                 a0 = fmaf(wt, v[q].x, a0);
@@ -194,27 +213,13 @@ __global__ __launch_bounds__(256) void hash_encode7_kernel(HashLevels H, const f
     encode7_point(H, reinterpret_cast<const float2*>(table) + H.offset[l], l, p, pts, n, radius, eps, gin, lde);
 }
 
-// the geometry MLP on one encoded input (rows 3..34 of GIN); FULL: all 13 outputs, else sdf only
-template <bool FULL>
-__device__ __forceinline__ void geo_mlp(const float* W, const float (&in)[36], float (&out)[HM_GOUT]) {
-    DH_UNROLL for (int c = 0; c < HM_GOUT; ++c) out[c] = W[HP_G1B + c];
-    for (int j = 0; j < HM_HID; ++j) {
-        const f32x4* wr = reinterpret_cast<const f32x4*>(W + HP_G0 + j * 36);
-        float a = W[HP_G0B + j];
-        DH_UNROLL for (int k4 = 0; k4 < 9; ++k4) {
-            const f32x4 w = wr[k4];
-            a = fmaf(w[0], in[4 * k4], a); a = fmaf(w[1], in[4 * k4 + 1], a);
-            a = fmaf(w[2], in[4 * k4 + 2], a); a = fmaf(w[3], in[4 * k4 + 3], a);
-        }
-        const float h = softplus100(a);
-        out[0] = fmaf(W[HP_G1 + j], h, out[0]);
-        if (FULL) { DH_UNROLL for (int c = 1; c < HM_GOUT; ++c) out[c] = fmaf(W[HP_G1 + c * 64 + j], h, out[c]); }
-    }
-}
-
-__device__ __forceinline__ void load_geo_input(const float* __restrict__ gin, int64_t lde, int64_t row, const float (&xe)[3],
-                                               float radius, float (&in)[36]) {
-    DH_UNROLL for (int c = 0; c < 3; ++c) in[c] = ((xe[c] + radius) / (2.f * radius)) * 2.f - 1.f;
+// the MLP's input of evaluation e of point p: xyz from eval_point's x01 (also returned), the encodings from rows 3..34 of GIN
+__device__ __forceinline__ void load_geo_input(const float* __restrict__ gin, int64_t lde, int64_t n, int64_t p, int e,
+                                               const float (&x)[3], float eps, float radius, float (&x01)[3], float (&in)[36]) {
+    float xe[3];
+    eval_point(e, x, eps, radius, xe, x01);
+    const int64_t row = (int64_t)e * n + p;
+    DH_UNROLL for (int c = 0; c < 3; ++c) in[c] = x01[c] * 2.f - 1.f;
     DH_UNROLL for (int k = 3; k < 35; ++k) in[k] = gin[(int64_t)k * lde + row];
     in[35] = 0.f;
 }
@@ -231,17 +236,15 @@ __global__ __launch_bounds__(256) void hash_geo_mlp_fwd_kernel(const float* __re
     stage_weights(W, hp);
     if (p >= na) return;
     const float x[3] = {pts[p * 3], pts[p * 3 + 1], pts[p * 3 + 2]};
-    float in[36], out[HM_GOUT];
-    load_geo_input(gin, lde, p, x, radius, in);
+    float in[36], x01[3], out[HM_GOUT];
+    load_geo_input(gin, lde, n, p, 0, x, eps, radius, x01, in);
     geo_mlp<true>(W, in, out);
     sdf[p] = out[0];
     DH_UNROLL for (int c = 0; c < HM_FEAT; ++c) feat[p * HM_FEAT + c] = out[c];
     DH_UNROLL for (int i = 0; i < 3; ++i) {
         float sd[2];
         DH_UNROLL for (int sg = 0; sg < 2; ++sg) {
-            float xe[3] = {x[0], x[1], x[2]};
-            xe[i] += sg ? -eps : eps;
-            load_geo_input(gin, lde, (int64_t)(1 + 2 * i + sg) * n + p, xe, radius, in);
+            load_geo_input(gin, lde, n, p, 1 + 2 * i + sg, x, eps, radius, x01, in);
             float o[HM_GOUT];
             geo_mlp<false>(W, in, o);
             sd[sg] = o[0];
@@ -487,7 +490,6 @@ __global__ __launch_bounds__(256) void hash_geo_bwd_kernel(const float* __restri
     const float x[3] = {pts[p * 3], pts[p * 3 + 1], pts[p * 3 + 2]};
     float dxyz[3] = {0.f, 0.f, 0.f};
     for (int e = 0; e < HW_E; ++e) {
-        float xe[3] = {x[0], x[1], x[2]};
         float dout[16];
         DH_UNROLL for (int c = 0; c < 16; ++c) dout[c] = 0.f;
         if (e == 0) {
@@ -496,13 +498,11 @@ __global__ __launch_bounds__(256) void hash_geo_bwd_kernel(const float* __restri
         } else {
             const int axis = (e - 1) >> 1;
             const float sgn = (e - 1) & 1 ? -1.f : 1.f;
-            DH_UNROLL for (int c = 0; c < 3; ++c) if (c == axis) xe[c] += sgn * eps;
             dout[0] = sgn * d_grad[p * 3 + axis] * (0.5f / eps);
         }
         const int64_t row = (int64_t)e * n + p;
         float in[36], x01[3];
-        DH_UNROLL for (int c = 0; c < 3; ++c) x01[c] = (xe[c] + radius) / (2.f * radius);
-        load_geo_input(ws + O.gin, O.lde, row, xe, radius, in);       // encodings: rows 3..34 left by the forward
+        load_geo_input(ws + O.gin, O.lde, n, p, e, x, eps, radius, x01, in);       // encodings: rows 3..34 left by the forward
         DH_UNROLL for (int c = 0; c < 3; ++c) ws[O.gin + c * O.lde + row] = in[c];
         ws[O.gin + 35 * O.lde + row] = 1.f;             // ones column: dW0[:,35] accumulates the bias gradient
         store_col(ws + O.x01, O.lde, row, x01);
@@ -511,12 +511,7 @@ __global__ __launch_bounds__(256) void hash_geo_bwd_kernel(const float* __restri
         DH_UNROLL for (int k = 0; k < 36; ++k) din[k] = 0.f;
         for (int j = 0; j < HM_HID; ++j) {
             const f32x4* wr = reinterpret_cast<const f32x4*>(W + HP_G0 + j * 36);
-            float a = W[HP_G0B + j];
-            DH_UNROLL for (int k4 = 0; k4 < 9; ++k4) {
-                const f32x4 w = wr[k4];
-                a = fmaf(w[0], in[4 * k4], a); a = fmaf(w[1], in[4 * k4 + 1], a);
-                a = fmaf(w[2], in[4 * k4 + 2], a); a = fmaf(w[3], in[4 * k4 + 3], a);
-            }
+            const float a = geo_hidden_pre(W, j, in);
             const float h = softplus100(a);
             float dh = 0.f;
             if (e == 0) { DH_UNROLL for (int c = 0; c < HM_GOUT; ++c) dh = fmaf(W[HP_G1 + c * 64 + j], dout[c], dh); }
@@ -541,8 +536,8 @@ __global__ __launch_bounds__(256) void hash_geo_bwd_kernel(const float* __restri
 // Point adjoint of the encoding (pose refinement): what the 16 levels of the E = 7 evaluations add to d loss / d x,
 //   d_pts[p][a] += sum_e sum_l (scale_l / (2 radius)) sum_corners (d w_corner / d pos_a) <table[corner], din_e[l]>
 // -- the derivative of the trilinear blend inside the cell (floor has derivative 0), what autograd gives on the oracle with the point as
-// a leaf.  Reads what hash_geo_bwd_kernel left (X01, DIN) and the table; per level hash_encode7_kernel's gathers: the centre cell's 8
-// corners fetched once, a shifted evaluation re-using them or the shared face.  No atomics: one thread per point walks the 16 levels and
+// a leaf.  Reads what hash_geo_bwd_kernel left (X01, DIN) and the table, per level through hash_encode7_kernel's stencil gather
+// (stencil_centre / stencil_plane).  No atomics: one thread per point walks the 16 levels and
 // adds them in ascending order onto the xyz share, so the result is bitwise the same from launch to launch.  (The other form -- a thread
 // per (point, level) as hash_encode7_kernel has it, level partials [16][n][3] in the workspace and a small kernel that adds them -- was
 // built and timed next to this one: 0.730 against 0.693 ms for the whole geometry backward at 262,144 points, 0.539 against 0.517 ms at
@@ -555,8 +550,7 @@ __device__ __forceinline__ void point_adjoint_level(const HashLevels& H, const f
     float w0[3];
     hg_cell(H, l, x0, g0, w0);
     float2 cf[8];
-    DH_UNROLL for (int corner = 0; corner < 8; ++corner)
-        cf[corner] = lvl[hg_index_local(H, l, g0[0] + (corner & 1), g0[1] + ((corner >> 1) & 1), g0[2] + (corner >> 2))];
+    stencil_centre(H, lvl, l, g0, cf);
     DH_UNROLL for (int c = 0; c < 3; ++c) g[c] = 0.f;
     {
         const float2 d = D[p];
@@ -576,29 +570,12 @@ __device__ __forceinline__ void point_adjoint_level(const HashLevels& H, const f
     DH_UNROLL for (int e = 1; e < HW_E; ++e) {
         const int a = (e - 1) >> 1, b = (a + 1) % 3, c = (a + 2) % 3;
         const int64_t row = (int64_t)e * n + p;
-        const float pos = X[a * lde + row] * sc + 0.5f;
-        const float fl = floorf(pos);
-        const float wa = pos - fl;
-        const uint32_t ga = (uint32_t)(int)fl;
-        const int delta = (int)(ga - g0[a]);
+        const auto [wa, ga, delta] = hg_shift(sc, X[a * lde + row], g0[a]);
         const float2 d = D[row];
         float s[2][4];                                   // <corner value, din_e> of plane ba, in-plane corner q
         DH_UNROLL for (int ba = 0; ba < 2; ++ba) {
-            const int t = delta + ba;                    // plane position relative to the centre cell: 0 / 1 = already held
-            const bool shared = (unsigned)t < 2u;
             float2 v[4];
-            DH_UNROLL for (int q = 0; q < 4; ++q) {
-                const int c0 = ((q & 1) << b) | ((q >> 1) << c), c1 = c0 | (1 << a);
-                v[q].x = t ? cf[c1].x : cf[c0].x;
-                v[q].y = t ? cf[c1].y : cf[c0].y;
-            }
-            if (!shared) {
-                DH_UNROLL for (int q = 0; q < 4; ++q) {
-                    uint32_t cc[3];
-                    cc[a] = ga + ba; cc[b] = g0[b] + (q & 1); cc[c] = g0[c] + (q >> 1);
-                    v[q] = lvl[hg_index_local(H, l, cc[0], cc[1], cc[2])];
-                }
-            }
+            stencil_plane(H, lvl, l, g0, cf, a, ga, delta, ba, v);
             DH_UNROLL for (int q = 0; q < 4; ++q) s[ba][q] = fmaf(v[q].x, d.x, v[q].y * d.y);
         }
         const float wb0 = 1.f - w0[b], wb1 = w0[b], wc0 = 1.f - w0[c], wc1 = w0[c];
@@ -717,11 +694,7 @@ __global__ __launch_bounds__(256) void hash_table_bwd_kernel(HashLevels H, const
     DH_UNROLL for (int e = 1; e < HW_E; ++e) {
         const int a = (e - 1) >> 1;
         const int64_t row = (int64_t)e * n + pc;
-        const float pos = X[a * O.lde + row] * s + 0.5f;
-        const float fl = floorf(pos);
-        const float wa = pos - fl;
-        const uint32_t ga = (uint32_t)(int)fl;
-        const int delta = (int)(ga - g0[a]);
+        const auto [wa, ga, delta] = hg_shift(s, X[a * O.lde + row], g0[a]);
         const float d = valid ? D[row * 2] : 0.f;
         DH_UNROLL for (int ba = 0; ba < 2; ++ba) {
             const int t = delta + ba;                    // plane position relative to the centre cell: 0 / 1 = shared

@@ -37,29 +37,47 @@ static inline HashLevels make_levels() {
 }
 static inline const HashLevels& levels() { static const HashLevels h = make_levels(); return h; }
 
-__device__ __forceinline__ uint32_t hg_index(const HashLevels& H, int l, uint32_t x, uint32_t y, uint32_t z) {
+// entry index of corner (x, y, z) inside level l (`lvl` = table + offset[l] entries)
+__device__ __forceinline__ uint32_t hg_index_local(const HashLevels& H, int l, uint32_t x, uint32_t y, uint32_t z) {
     const uint32_t res = H.res[l];
     // dense corner coordinates reach `res` at the far faces: wrap inside the level (tcnn does the same)
-    const uint32_t idx = H.dense[l] ? ((x + y * res + z * res * res) % H.size[l])
-                                    : (((x * 1u) ^ (y * 2654435761u) ^ (z * 805459861u)) & (HG_T - 1));
-    return idx + H.offset[l];
+    return H.dense[l] ? ((x + y * res + z * res * res) % H.size[l]) : (((x * 1u) ^ (y * 2654435761u) ^ (z * 805459861u)) & (HG_T - 1));
+}
+__device__ __forceinline__ uint32_t hg_index(const HashLevels& H, int l, uint32_t x, uint32_t y, uint32_t z) {
+    return hg_index_local(H, l, x, y, z) + H.offset[l];
 }
 
-
-inline HashLevels hashgrid_levels() { return levels(); }
-
-// trilinear blend of the 8 corner rows of level l at x01 in [0,1]^3
-__device__ __forceinline__ void hg_encode_level(const HashLevels& H, const float* __restrict__ table, int l,
-                                                const float (&x01)[3], float& f0, float& f1) {
+// the cell of level l that x01 in [0,1]^3 lies in: lower corner g (outside the box the negative floor wraps in uint32) and the
+// position w in [0,1)^3 inside it
+__device__ __forceinline__ void hg_cell(const HashLevels& H, int l, const float (&x01)[3], uint32_t (&g)[3], float (&w)[3]) {
     const float s = H.scale[l];
-    float w[3];
-    uint32_t g[3];
     _Pragma("unroll") for (int c = 0; c < 3; ++c) {
         const float pos = x01[c] * s + 0.5f;
         const float f = floorf(pos);
         w[c] = pos - f;
         g[c] = (uint32_t)(int)f;
     }
+}
+
+// one axis of an evaluation shifted along it (the +-eps points of the finite-difference normals): from the level's scale s, the
+// shifted coordinate x01a in [0,1] and the centre cell's g0a -- the position wa inside its cell, that cell's lower corner ga and how
+// many cells it lies from the centre's (hg_cell's arithmetic on one axis: the two must agree on the cell)
+struct HgShift { float wa; uint32_t ga; int delta; };
+__device__ __forceinline__ HgShift hg_shift(float s, float x01a, uint32_t g0a) {
+    const float pos = x01a * s + 0.5f;
+    const float fl = floorf(pos);
+    const uint32_t ga = (uint32_t)(int)fl;
+    return {pos - fl, ga, (int)(ga - g0a)};
+}
+
+inline HashLevels hashgrid_levels() { return levels(); }
+
+// trilinear blend of the 8 corner rows of level l at x01 in [0,1]^3
+__device__ __forceinline__ void hg_encode_level(const HashLevels& H, const float* __restrict__ table, int l,
+                                                const float (&x01)[3], float& f0, float& f1) {
+    float w[3];
+    uint32_t g[3];
+    hg_cell(H, l, x01, g, w);
     float a0 = 0.f, a1 = 0.f;
     _Pragma("unroll") for (int corner = 0; corner < 8; ++corner) {
         const int dx = corner & 1, dy = (corner >> 1) & 1, dz = corner >> 2;

@@ -1,5 +1,5 @@
 """Record tests/golden/train_step.json: what six training iterations of the Runner leave behind, bit for bit, in both model families
-and on both samplers of the hash family (A-E), and what the network stages give outside the training step (F: vertex colours,
+and on both samplers of the hash family (A-E, G, H), and what the network stages give outside the training step (F: vertex colours,
 colours at hit points, three steps of the SDF warm start).  tests/test_gpu_train_step_replay.py replays the file.
 
     python tests/golden/make_golden_train_step.py [--out path]
@@ -9,7 +9,7 @@ mesh_color.network_vertex_colors, surface_render.network_at_hits and sdf_init.fi
 must not move a bit, twice, and keep the file only when both runs wrote the same bytes; a difference in the test is a finding to
 explain, never a reason to run this again.
 
-Every case A-E builds a Runner on the synthetic scene (6 frames of 64 x 64, the default seeds, no report, checkpoint or validation)
+Every case A-E, G, H builds a Runner on the synthetic scene (6 frames of 64 x 64, the default seeds, no report, checkpoint or validation)
 and records the stats [8] of each of 6 iterations, the side statistics the step leaves (last_prior_stats, last_corr_stats), the
 SHA-256 of store.flat at the end and, where the poses move, of dataset.R and dataset.T.
   A  NeuS, batch 77 (77 x 128 points: ragged against a pair workgroup), normal_weight 0.05
@@ -19,6 +19,9 @@ SHA-256 of store.flat at the end and, where the poses move, of dataset.R and dat
      correspondence term sums the partner poses' gradients with float atomics: not reproducible, so not recorded.)
   D  hash family, hierarchical sampler, batch 77
   E  hash family, occupancy-grid sampler (grid 32^3, refreshed every 2 iterations), batch 128, the depth and masked normal priors
+  G  hash family, hierarchical sampler, batch 77, pose refinement from iteration 1 on, the normal term, no correspondences
+  H  hash family, occupancy-grid sampler as in E, batch 128, pose refinement from iteration 1 on, the normal term, no correspondences
+     (G and H: the point and direction adjoints of the hash-grid kernels, which D and E do not run)
 json keeps a Python float exactly, so the replay compares without a tolerance."""
 import argparse
 import hashlib
@@ -39,6 +42,7 @@ SYNTHETIC = {"n_frames": 6, "H": 64, "W": 64, "seed": 11}
 QUIET = {"report_freq": 10 ** 9, "save_freq": 10 ** 9, "val_freq": 0, "warm_up_end": 2, "end_iter": 2000}
 HASH_OCCGRID = {"sampler": "occgrid", "march_samples_per_ray": 256, "grid_res": 32, "grid_update_every": 2}
 PRIORS = {"depth_weight": 0.5, "normal_weight": 0.05, "normal_skip_missing": True}
+HASH_REFINE = {"refine_poses": True, "pose_start_iter": 1, "normal_weight": 0.05}
 CASES = {
     "A_neus_ragged": dict(family="neus", train={"batch_size": 77, "normal_weight": 0.05}),
     "B_neus_full_loss_stack": dict(family="neus", synthetic={"correspondences": 256, "depth": True},
@@ -49,6 +53,11 @@ CASES = {
                                        "depth_weight": 0.5}),
     "D_hash_hierarchical": dict(family="hash", train={"batch_size": 77}),
     "E_hash_occgrid": dict(family="hash", hash_renderer=HASH_OCCGRID, synthetic={"depth": True}, train=dict(PRIORS, batch_size=128)),
+}
+# recorded after F, so that A-F run in the order in which they were first recorded
+HASH_POSE_CASES = {
+    "G_hash_hierarchical_refine_poses": dict(family="hash", train=dict(HASH_REFINE, batch_size=77)),
+    "H_hash_occgrid_refine_poses": dict(family="hash", hash_renderer=HASH_OCCGRID, train=dict(HASH_REFINE, batch_size=128)),
 }
 
 
@@ -117,13 +126,15 @@ def _network_case(root, family, device):
 
 
 def run_cases(device="cuda:0"):
-    """{case: its record} of the cases A-E and of F for both families."""
+    """{case: its record} of the cases A-E, of F for both families, and of G and H."""
     out = {}
     with tempfile.TemporaryDirectory() as root:
         for name, spec in CASES.items():
             out[name] = _train_case(root, name, spec, device)
         for family in ("neus", "hash"):
             out["F_network_stages_" + family] = _network_case(root, family, device)
+        for name, spec in HASH_POSE_CASES.items():
+            out[name] = _train_case(root, name, spec, device)
     return json.loads(json.dumps(out))
 
 

@@ -1,7 +1,9 @@
 """The training step of both model families and the network stages outside it against tests/golden/train_step.json (recorded twice,
 byte for byte the same, by tests/golden/make_golden_train_step.py on an MI355X before the network-stage state and the loss stage were
-made one): six Runner iterations of NeuS (ragged batch; the full loss stack; pose refinement), of the hash family on both samplers, and
-vertex colours, hit-point colours and SDF warm-start steps of both families must give the recorded numbers bit for bit."""
+made one; cases G and H, the hash family's pose refinement, recorded in the same way before the hash-grid kernels' shared helpers): six
+Runner iterations of NeuS (ragged batch; the full loss stack; pose refinement), of the hash family on both samplers without and with
+pose refinement, and vertex colours, hit-point colours and SDF warm-start steps of both families must give the recorded numbers bit for
+bit."""
 import importlib.util
 import json
 import os
@@ -26,7 +28,8 @@ def replay():
 
 def test_the_recording_covers_the_cases():
     assert sorted(RECORDED) == ["A_neus_ragged", "B_neus_full_loss_stack", "C_neus_refine_poses", "D_hash_hierarchical", "E_hash_occgrid",
-                                "F_network_stages_hash", "F_network_stages_neus"]
+                                "F_network_stages_hash", "F_network_stages_neus", "G_hash_hierarchical_refine_poses",
+                                "H_hash_occgrid_refine_poses"]
     for name, rec in RECORDED.items():
         if name[0] == "F":
             assert len(rec["fit_loss"]) == len(rec["fit_sdf_sha256"]) == 3 and len(set(rec["fit_sdf_sha256"])) == 3, name
@@ -35,7 +38,7 @@ def test_the_recording_covers_the_cases():
         assert len(rec["stats"]) == 6 and all(len(s) == 8 for s in rec["stats"]) and len(rec["flat_sha256"]) == 64, name
         assert all((p is not None) == (name[0] in "BCE") for p in rec["prior_stats"]), name
         assert all((c is not None) == (name[0] == "B") for c in rec["corr_stats"]), name
-        assert ("R_sha256" in rec) == ("T_sha256" in rec) == (name[0] == "C"), name
+        assert ("R_sha256" in rec) == ("T_sha256" in rec) == (name[0] in "CGH"), name
     depth_rays = [p[1] for p in RECORDED["B_neus_full_loss_stack"]["prior_stats"]]
     assert depth_rays[:2] == [0.0, 0.0] and all(n > 0 for n in depth_rays[2:])          # the depth term comes on inside the run
 
