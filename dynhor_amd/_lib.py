@@ -97,6 +97,13 @@ SIGNATURES = {
     "dh_prior_loss_workspace": (_i64, [_i64]),
     "dh_prior_loss": (_i32, [_vp] * 6 + [_i64, _i32, _f32, _f32, _f32, _f32, _i32] + [_vp] * 5),
     "dh_prior_loss_packed": (_i32, [_vp] * 6 + [_i64, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _i32] + [_vp] * 5),
+    "dh_ray_depth": (_i32, [_vp] * 4 + [_i64, _i32, _f32] + [_vp] * 4),
+    "dh_ray_depth_packed": (_i32, [_vp] * 4 + [_i64, _vp, _vp, _i32, _f32] + [_vp] * 4),
+    "dh_warp_loss_workspace": (_i64, [_i64]),
+    "dh_warp_loss": (_i32, [_vp, _vp, _i64, _i32, _i32] + [_vp] * 5 + [_i32, _i32] + [_vp] * 4
+                     + [_i64, _i32, _i64, _f32, _i32, _i32, _f32, _f32, _f32] + [_vp] * 5),
+    "dh_ray_depth_bwd": (_i32, [_vp] * 7 + [_i64, _i32, _f32, _f32, _i32] + [_vp] * 3),
+    "dh_ray_depth_bwd_packed": (_i32, [_vp] * 7 + [_i64, _vp, _vp, _i32, _f32, _f32, _i32] + [_vp] * 3),
     "dh_nearest_sqdist_workspace": (_i64, [_i64, _i64]),
     "dh_nearest_sqdist": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "dh_mesh_sdf_record_floats": (_i32, []),

@@ -1277,6 +1277,101 @@ int dh_mvs_check(const float* depth, int64_t n_frames, int H, int W, const float
     return launch_mvs_check(depth, (int)n_frames, H, W, R, T, K, Kinv, nbr, n_nbr, depth_rel, count, static_cast<hipStream_t>(stream));
 }
 
+namespace {
+inline bool misaligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
+
+// the checks the two forms of dh_ray_depth and dh_ray_depth_bwd share; DH_OK + *run = false for the no-op
+int ray_depth_args(const float* rays, const float* R, const float* samples, int64_t B, bool* run) {
+    *run = false;
+    if (B < 0) return DH_ERR_BAD_ARG;
+    if (B == 0) return DH_OK;
+    if (!rays || !R || !samples || misaligned4(rays) || misaligned4(R) || misaligned4(samples)) return DH_ERR_BAD_ARG;
+    *run = true;
+    return DH_OK;
+}
+}  // namespace
+
+int dh_ray_depth(const float* rays, const float* R, const float* z, const float* weights, int64_t B, int n, float sample_dist, float* t,
+                 float* wsum, float* zc, void* stream) {
+    if (n < 1 || !std::isfinite(sample_dist)) return DH_ERR_BAD_ARG;
+    bool run;
+    const int rc = ray_depth_args(rays, R, z, B, &run);
+    if (rc != DH_OK || !run) return rc;
+    if (!weights || !t || !wsum || !zc || misaligned4(weights) || misaligned4(t) || misaligned4(wsum) || misaligned4(zc)) return DH_ERR_BAD_ARG;
+    return launch_ray_depth(rays, R, z, weights, B, n, nullptr, nullptr, n, sample_dist, t, wsum, zc, static_cast<hipStream_t>(stream));
+}
+
+int dh_ray_depth_packed(const float* rays, const float* R, const float* t_start, const float* weights, int64_t B, const int64_t* seg_off,
+                        const int32_t* seg_cnt, int max_samples, float step, float* t, float* wsum, float* zc, void* stream) {
+    if (max_samples < 0 || !std::isfinite(step)) return DH_ERR_BAD_ARG;
+    if (max_samples > 1024) return DH_ERR_UNSUPPORTED;
+    bool run;
+    const int rc = ray_depth_args(rays, R, t_start, B, &run);
+    if (rc != DH_OK || !run) return rc;
+    if (!weights || !t || !wsum || !zc || !seg_off || !seg_cnt || misaligned4(weights) || misaligned4(t) || misaligned4(wsum) ||
+        misaligned4(zc) || (reinterpret_cast<uintptr_t>(seg_off) & 7u) != 0 || misaligned4(seg_cnt))
+        return DH_ERR_BAD_ARG;
+    return launch_ray_depth(rays, R, t_start, weights, B, 0, seg_off, seg_cnt, max_samples, step, t, wsum, zc,
+                            static_cast<hipStream_t>(stream));
+}
+
+int dh_ray_depth_bwd(const float* rays, const float* R, const float* z, const float* t, const float* wsum, const float* ray_f,
+                     const float* stats, int64_t B, int n, float sample_dist, float warp_weight, int accumulate, float* d_weights,
+                     float* d_normal_map, void* stream) {
+    if (n < 1 || !std::isfinite(sample_dist) || !(warp_weight >= 0.f) || accumulate < 0 || accumulate > 3) return DH_ERR_BAD_ARG;
+    bool run;
+    const int rc = ray_depth_args(rays, R, z, B, &run);
+    if (rc != DH_OK || !run) return rc;
+    if (!t || !wsum || !ray_f || !stats || misaligned4(t) || misaligned4(wsum) || misaligned4(ray_f) || misaligned4(stats) ||
+        misaligned4(d_weights) || misaligned4(d_normal_map))
+        return DH_ERR_BAD_ARG;
+    return launch_ray_depth_bwd(rays, R, z, t, wsum, ray_f, stats, B, n, nullptr, nullptr, n, sample_dist, warp_weight, accumulate,
+                                d_weights, d_normal_map, static_cast<hipStream_t>(stream));
+}
+
+int dh_ray_depth_bwd_packed(const float* rays, const float* R, const float* t_start, const float* t, const float* wsum, const float* ray_f,
+                            const float* stats, int64_t B, const int64_t* seg_off, const int32_t* seg_cnt, int max_samples, float step,
+                            float warp_weight, int accumulate, float* d_weights, float* d_normal_map, void* stream) {
+    if (max_samples < 0 || !std::isfinite(step) || !(warp_weight >= 0.f) || accumulate < 0 || accumulate > 3) return DH_ERR_BAD_ARG;
+    if (max_samples > 1024) return DH_ERR_UNSUPPORTED;
+    bool run;
+    const int rc = ray_depth_args(rays, R, t_start, B, &run);
+    if (rc != DH_OK || !run) return rc;
+    if (!t || !wsum || !ray_f || !stats || !seg_off || !seg_cnt || misaligned4(t) || misaligned4(wsum) || misaligned4(ray_f) ||
+        misaligned4(stats) || misaligned4(d_weights) || misaligned4(d_normal_map) || (reinterpret_cast<uintptr_t>(seg_off) & 7u) != 0 ||
+        misaligned4(seg_cnt))
+        return DH_ERR_BAD_ARG;
+    return launch_ray_depth_bwd(rays, R, t_start, t, wsum, ray_f, stats, B, 0, seg_off, seg_cnt, max_samples, step, warp_weight, accumulate,
+                                d_weights, d_normal_map, static_cast<hipStream_t>(stream));
+}
+
+int64_t dh_warp_loss_workspace(int64_t B) {
+    if (B < 0) return DH_ERR_BAD_ARG;
+    return warp_loss_workspace(B);
+}
+
+int dh_warp_loss(const uint8_t* gray, const uint8_t* valid, int64_t n_frames, int H, int W, const float* R, const float* T, const float* K,
+                 const float* Kinv, const int32_t* nbr, int n_nbr, int frame, const int32_t* pix, const float* z, const float* wsum,
+                 const float* normal, int64_t B, int P, int64_t min_va, float min_vb, int topk, int min_views, float min_cos,
+                 float min_wsum, float warp_weight, float* out_f, int32_t* out_i, float* stats, void* ws, void* stream) {
+    if (B < 0) return DH_ERR_BAD_ARG;
+    const int rc = sil_args(n_frames, H, W);
+    if (rc != DH_OK) return rc;
+    if (P < 1 || P > warp_max_patch() || n_nbr < 1 || n_nbr > warp_max_neighbours() || topk < 1 || topk > warp_max_neighbours() ||
+        min_views < 1 || min_views > warp_max_neighbours() || min_va < 1 || !(min_vb > 0.f) || !std::isfinite(min_vb) ||
+        !(min_cos >= -1.f && min_cos <= 1.f) || !std::isfinite(min_wsum) || !(warp_weight >= 0.f) || !std::isfinite(warp_weight))
+        return DH_ERR_BAD_ARG;                                                                       // a NaN fails every comparison
+    if (B >= ((int64_t)1 << 31)) return DH_ERR_UNSUPPORTED;
+    if (B == 0) return DH_OK;
+    if (frame < 0 || frame >= n_frames) return DH_ERR_BAD_ARG;
+    if (!gray || !valid || !R || !T || !K || !Kinv || !nbr || !pix || !z || !wsum || !normal || !out_f || !out_i || !stats || !ws ||
+        misaligned4(R) || misaligned4(T) || misaligned4(K) || misaligned4(Kinv) || misaligned4(nbr) || misaligned4(pix) || misaligned4(z) ||
+        misaligned4(wsum) || misaligned4(normal) || misaligned4(out_f) || misaligned4(out_i) || misaligned4(stats) || misaligned16(ws))
+        return DH_ERR_BAD_ARG;
+    return launch_warp_loss(gray, valid, (int)n_frames, H, W, R, T, K, Kinv, nbr, n_nbr, frame, pix, z, wsum, normal, B, P, min_va, min_vb,
+                            topk, min_views, min_cos, min_wsum, warp_weight, out_f, out_i, stats, ws, static_cast<hipStream_t>(stream));
+}
+
 int dh_tsdf_integrate(const float* pts, int64_t n, const float* depth, const uint8_t* weight, const float* R, const float* T, const float* K,
                       int64_t n_frames, int H, int W, float trunc, int64_t* num, int32_t* den, int32_t* obs, void* stream) {
     if (n < 0 || n_frames < 0 || H < 1 || W < 1 || !(trunc > 0.f) || !std::isfinite(trunc)) return DH_ERR_BAD_ARG;

@@ -217,6 +217,20 @@ int launch_prior_loss(const float* rays, const float* R, const float* z, const f
                       void* ws, hipStream_t st);
 int launch_sum64_reduce(const double* partial, int64_t groups, int blocks, int K, double* out, hipStream_t st);
 
+// multi-view photometric consistency of the training step (warp_loss.hip); seg_off == nullptr: dense rays [B,n]
+int warp_max_patch();
+int warp_max_neighbours();
+int64_t warp_loss_workspace(int64_t B);
+int launch_ray_depth(const float* rays, const float* R, const float* z, const float* weights, int64_t B, int n, const int64_t* seg_off,
+                     const int32_t* seg_cnt, int max_samples, float sample_dist, float* t_out, float* w_out, float* z_out, hipStream_t st);
+int launch_ray_depth_bwd(const float* rays, const float* R, const float* z, const float* t_in, const float* w_in, const float* ray_f,
+                         const float* stats, int64_t B, int n, const int64_t* seg_off, const int32_t* seg_cnt, int max_samples,
+                         float sample_dist, float warp_w, int accumulate, float* d_weights, float* d_nmap, hipStream_t st);
+int launch_warp_loss(const uint8_t* gray, const uint8_t* valid, int n_frames, int H, int W, const float* R, const float* T, const float* K,
+                     const float* Kinv, const int32_t* nbr, int n_nbr, int frame, const int32_t* pix, const float* z, const float* wsum,
+                     const float* normal, int64_t B, int P, int64_t min_va, float min_vb, int topk, int min_views, float min_cos,
+                     float min_wsum, float warp_w, float* out_f, int32_t* out_i, float* stats, void* ws, hipStream_t st);
+
 // mesh cleaning (mesh_clean.hip): label dilation, silhouette votes per vertex, connected components by union-find
 int launch_label_dilate(const int8_t* label, int64_t n_frames, int H, int W, int radius, uint8_t* tmp, uint8_t* keep, hipStream_t st);
 int launch_mesh_mask_votes(const float* verts, int64_t nv, const uint8_t* keep, const float* R, const float* T, const float* K,

@@ -426,7 +426,8 @@ class HashNeuSRenderer(NeuSRenderer):
                         background_rgb=None, t_rand=None, **kw):
         """The parent's step on the hierarchical sampler; on the occupancy-grid sampler the packed one: grid update, march, forward,
         the parent's loss stage on the packed description of the samples (the priors of dh_prior_loss_packed: prior_depth,
-        depth_weight, depth_delta, normal_skip_missing as the parent takes them), backward.  ray_grads (a renderer built with
+        depth_weight, depth_delta, normal_skip_missing, and warp, the multi-view photometric term on dh_ray_depth_packed, as the parent
+        takes them), backward.  ray_grads (a renderer built with
         ray_grads=True): the backward also folds the per-point adjoints into self.last_ray_grads = (d_rays_o, d_rays_d, d_R or None) as
         the parent leaves them, rays without samples getting zeros; self.last_partner_pose_grads = None (no correspondence term here)."""
         if self.sampler != "occgrid":
@@ -435,6 +436,8 @@ class HashNeuSRenderer(NeuSRenderer):
         if kw.get("corr") is not None:
             raise ValueError("the correspondence term runs on the hierarchical sampler")
         ray_grads = bool(kw.pop("ray_grads", False))
+        if kw.get("warp") is not None and ray_grads:
+            raise ValueError("train_step_core: the warp term has no pose adjoint (ray_grads)")
         if ray_grads and not self.ray_grads:
             raise ValueError("pose refinement on the occupancy-grid sampler needs the adjoint buffers: build the renderer with "
                              "ray_grads=True (the Runner does with train.refine_poses)")
@@ -450,7 +453,8 @@ class HashNeuSRenderer(NeuSRenderer):
         finally:
             self._in_train_step = False
         bg = None if background_rgb is None else background_rgb.reshape(-1).contiguous().float()
-        s = self._forward_packed(rays_o, rays_d, m, cos_anneal_ratio, bg, want_nmap=normal_weight > 0.0, ray_grads=ray_grads)
+        s = self._forward_packed(rays_o, rays_d, m, cos_anneal_ratio, bg, want_nmap=normal_weight > 0.0 or kw.get("warp") is not None,
+                                 ray_grads=ray_grads)
         a = self._loss_stage(s, rays, R, m.t_start, m.step, igr_weight, mask_weight, normal_weight,
                              packed=(m.off, m.cnt, self._cap_ladder[0]), d_weights=m.buf.d_weights, **kw)
         self._backward_packed(s, a.d_color, a.d_wsum, a.d_nmap, a.eik_coef, a.d_weights)

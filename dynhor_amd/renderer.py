@@ -525,12 +525,15 @@ class NeuSRenderer:
     @torch.no_grad()
     def _loss_stage(self, s, rays, R, z, sample_dist, igr_weight, mask_weight, normal_weight, packed=None, d_weights=None, corr=None,
                     corr_weight=0.0, corr_frames=None, corr_delta_px=4.0, prior_depth=None, depth_weight=0.0, depth_delta=0.02,
-                    normal_skip_missing=False):
+                    normal_skip_missing=False, warp=None):
         """Every loss term of train_step_core on the forward state s, for both descriptions of the samples: dense, z = z_vals [B,n]
         with sample_dist; packed = (seg_off, seg_cnt, max_samples), z = t_start with sample_dist = the marching step, and d_weights =
         the pre-allocated buffer the depth term writes (dense: allocated here).  dh_neus_loss; with corr and corr_weight > 0 corr_loss
         (self.last_corr_stats, self.last_corr_residual_px); with depth_weight > 0 or normal_skip_missing prior_loss, stacked on the
-        correspondence term's d_weights or writing its own (self.last_prior_stats).  Returns a namespace: stats [8] with every term
+        correspondence term's d_weights or writing its own (self.last_prior_stats); with warp (warp_loss.step_input) the multi-view
+        photometric term (warp_loss.warp_term: dh_ray_depth -> dh_warp_loss -> dh_ray_depth_bwd), after the others and stacked on their
+        d_weights and d_nmap, either of which it allocates when no other term has (self.last_warp_stats [8], self.last_warp_rays =
+        (out_f [B,8], out_i [B,4])).  Returns a namespace: stats [8] with every term
         folded in, the adjoints d_color, d_wsum, d_weights (None when no term has one), d_nmap (None without a normal term), eik_coef
         for the backward, R as the kernels took it and pose_adj [B,7] (corr_loss's, under s.ray_grads; else None).  No host read."""
         if depth_weight > 0.0 and prior_depth is None:
@@ -560,12 +563,24 @@ class NeuSRenderer:
                                                depth_delta, normal_weight if masked_normal else 0.0, stacked,
                                                a.d_weights if use_depth else None, a.d_nmap if masked_normal else None, packed=packed)
             add_prior_stats(a.stats, self.last_prior_stats, use_depth, masked_normal)
+        if warp is not None:
+            from .warp_loss import warp_term
+            if a.R is None or s.nmap is None:
+                raise ValueError("train_step_core: the warp term needs the frame's R and a forward pass with the normal map")
+            add_w, add_n = a.d_weights is not None, a.d_nmap is not None
+            if not add_w:
+                a.d_weights = d_weights if d_weights is not None else torch.empty(B, s.n, device=dev)
+            if not add_n:
+                a.d_nmap = torch.empty(B, 3, device=dev)
+            self.last_warp_stats, *self.last_warp_rays = warp_term(warp, rays, a.R, z, s.weights, s.nmap, sample_dist, a.d_weights, a.d_nmap,
+                                                                   add_w, add_n, packed=packed, call=self.timer)
+            a.stats[0] += self.last_warp_stats[3]
         return a
 
     @torch.no_grad()
     def train_step_core(self, rays, near, far, R, cos_anneal_ratio, igr_weight=0.1, mask_weight=0.1, normal_weight=0.0,
                         background_rgb=None, t_rand=None, corr=None, corr_weight=0.0, corr_frames=None, corr_delta_px=4.0,
-                        ray_grads=False, prior_depth=None, depth_weight=0.0, depth_delta=0.02, normal_skip_missing=False):
+                        ray_grads=False, prior_depth=None, depth_weight=0.0, depth_delta=0.02, normal_skip_missing=False, warp=None):
         """rays [B,14] (dh_gen_rays layout), R [3,3] object->camera of the frame.  Returns stats [8] on device:
         loss, colour, eikonal, mask, normal, psnr, sum(obj*keep), sum(keep); leaves the flat gradient in
         store.grad_flat.  No host synchronisation.
@@ -581,15 +596,21 @@ class NeuSRenderer:
         takes the normal term over the rays that HAVE a monocular normal: dh_neus_loss then runs at normal weight 0 and the masked
         term supplies d_nmap and stats[4].  Either leaves self.last_prior_stats [8]; neither launches anything when off.  The depth
         term needs no adjoint of its own under ray_grads: c_z = (R d)_z is the z of the camera-frame direction K^-1 (u, v, 1),
-        which no pose enters, and the sample depths are constants there already, so all of it flows through d_weights."""
+        which no pose enters, and the sample depths are constants there already, so all of it flows through d_weights.
+        Multi-view photometric consistency (dh_warp_loss, DESIGN_NEXT_ROWS.md section 30): warp = warp_loss.step_input(..) adds
+        warp.weight * the term; the forward then forms the normal map whatever normal_weight is.  It leaves self.last_warp_stats [8]
+        and launches nothing when warp is None.  The term has no pose adjoint: with ray_grads it raises."""
+        if warp is not None and ray_grads:
+            raise ValueError("train_step_core: the warp term has no pose adjoint (ray_grads)")
         rays_o = rays[:, 0:3].contiguous()
         rays_d = rays[:, 3:6].contiguous()
         z_vals = self.sample_z(rays_o, rays_d, near, far, t_rand=t_rand)
         bg = None if background_rgb is None else background_rgb.reshape(-1).contiguous().float()
-        s = self._forward_core(rays_o, rays_d, z_vals, cos_anneal_ratio, bg, want_nmap=normal_weight > 0.0, ray_grads=ray_grads)
+        s = self._forward_core(rays_o, rays_d, z_vals, cos_anneal_ratio, bg, want_nmap=normal_weight > 0.0 or warp is not None,
+                               ray_grads=ray_grads)
         a = self._loss_stage(s, rays, R, z_vals, s.sample_dist, igr_weight, mask_weight, normal_weight, corr=corr, corr_weight=corr_weight,
                              corr_frames=corr_frames, corr_delta_px=corr_delta_px, prior_depth=prior_depth, depth_weight=depth_weight,
-                             depth_delta=depth_delta, normal_skip_missing=normal_skip_missing)
+                             depth_delta=depth_delta, normal_skip_missing=normal_skip_missing, warp=warp)
         self._backward_core(s, a.d_color, a.d_wsum, a.d_weights, None, a.d_nmap, a.eik_coef, persistent=True)
         self.last_state = s
         if ray_grads:

@@ -31,7 +31,8 @@ from .pose_photo import DEFAULTS as POSE_PHOTO_DEFAULTS
 from .pose_sil import DEFAULTS as POSE_SIL_DEFAULTS
 from .renderer import NeuSRenderer
 from .sdf_init import SDF_INIT_DEFAULTS
-from .settings import PRIOR_DEFAULTS, int_in, is_int, merge, one_of, prior_settings
+from .settings import PRIOR_DEFAULTS, int_in, is_int, merge, one_of, prior_settings, warp_settings
+from .warp_loss import DEFAULTS as WARP_DEFAULTS
 
 DEFAULT_CONF = {
     "seq_name": "synthetic", "exp_name": "neus",
@@ -50,6 +51,9 @@ DEFAULT_CONF = {
               # priors with a validity (dh_prior_loss, DESIGN_NEXT_ROWS.md section 27; settings.PRIOR_DEFAULTS): the depth term reads
               # data_info.depth; normal_skip_missing takes the normal term over the pixels that have a normal.  First settings, not tuned
               **PRIOR_DEFAULTS,
+              # multi-view photometric consistency (dh_warp_loss, DESIGN_NEXT_ROWS.md section 30; warp_loss.DEFAULTS): warp_weight 0 = off;
+              # the grey tables are built at the first iteration >= warp_start_iter.  First settings, not tuned.  Not with refine_poses
+              "warp_weight": 0.0, **{"warp_" + k: (list(v) if isinstance(v, tuple) else v) for k, v in WARP_DEFAULTS.items()},
               # per-frame pose refinement: 6-D rotation + translation per frame, rotation at 10x lr
               "refine_poses": False, "pose_lr": 1e-4, "pose_rot_lr_mult": 10.0, "pose_start_iter": 0},
     # family "neus": the 8x256 / 4x256 fp32 MLPs (BASELINE.json configs[1]); "hash": hash-grid + shallow MLPs (configs[3])
@@ -180,6 +184,12 @@ class Runner:
         pr = prior_settings(tr)
         self.depth_weight, self.depth_delta, self.depth_start_iter = pr["depth_weight"], pr["depth_delta"], pr["depth_start_iter"]
         self.normal_skip_missing = pr["normal_skip_missing"]
+        self.warp_conf = warp_settings(tr)
+        self.warp_weight = self.warp_conf.pop("weight")
+        self.warp_tables = None          # warp_loss.frames_for's tables, built at the first iteration with the term
+        if self.warp_weight > 0.0 and tr["refine_poses"]:
+            raise ValueError("train.warp_weight > 0 with train.refine_poses is not supported: the multi-view photometric term has no "
+                             "pose adjoint and its grey tables and homographies would go stale as the poses move")
         self.iter_step = 0
         if prior_dir is not None:
             d = _newest_mvs_dir(self.base_exp_dir, "--prior_dir auto") if prior_dir == "auto" else str(prior_dir)
@@ -321,12 +331,18 @@ class Runner:
                          depth_delta=self.depth_delta)
         if self.normal_skip_missing:
             prior["normal_skip_missing"] = True
+        if self.warp_weight > 0.0 and self.iter_step >= self.warp_conf["start_iter"]:
+            from . import warp_loss
+            if self.warp_tables is None:
+                self.warp_tables = warp_loss.frames_for(self.dataset, self.train_frames, **self.warp_conf)
+            prior["warp"] = warp_loss.step_input(self.warp_tables, self.dataset, frame, self.warp_weight)
+        self._warp_on = "warp" in prior
         stats = self.renderer.train_step_core(rays, near, far, self.dataset.R[frame], self.get_cos_anneal_ratio(),
                                               self.igr_weight, self.mask_weight, self.normal_weight, background_rgb=bg,
                                               t_rand=t_rand, corr=corr, corr_weight=self.corr_weight,
                                               corr_frames=self.dataset.corr_frames() if corr is not None else None,
                                               corr_delta_px=self.corr_delta_px, ray_grads=refine, **prior)
-        self._prior_on = bool(prior)
+        self._prior_on = any(k != "warp" for k in prior)
         if refine:
             # chain the per-ray adjoints into this frame's 9 pose numbers (torch autograd over the ray formula), step, and
             # write the refined pose back into the resident frame table the HIP ray gather reads
@@ -392,6 +408,9 @@ class Runner:
             ps = self.renderer.last_prior_stats.tolist()       # this rank's batch, as the correspondence scalars are
             rec.update({"Loss/depth_loss": ps[0], "Statistics/depth_abs": ps[2], "Statistics/depth_rays": ps[1],
                         "Statistics/normal_rays": ps[5]})
+        if getattr(self, "_warp_on", False) and getattr(self.renderer, "last_warp_stats", None) is not None:
+            ws = self.renderer.last_warp_stats.tolist()        # this rank's batch
+            rec.update({"Loss/warp_loss": ws[0], "Statistics/warp_score": ws[2], "Statistics/warp_rays": ws[1]})
         st = getattr(self.renderer, "last_state", None)
         if st is not None and getattr(self, "_last_rays", None) is not None:
             # upstream Statistics/cdf and Statistics/weight_max (App. A.8), masked by obj*keep like the colour loss

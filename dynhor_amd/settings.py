@@ -76,3 +76,19 @@ def prior_settings(train: dict) -> dict:
     if not isinstance(pr["normal_skip_missing"], bool):
         raise ValueError(f"train normal_skip_missing must be true or false, got {pr['normal_skip_missing']!r}")
     return pr
+
+
+def warp_settings(train: dict) -> dict:
+    """The multi-view photometric term's keys of a train: block (dh_warp_loss; DESIGN_NEXT_ROWS.md section 30), checked: `weight`
+    (train.warp_weight, 0 = the term off) and every key of warp_loss.DEFAULTS (train.warp_<key>).  Only a key that starts with warp_ and is
+    none of these is rejected as unknown; prior_settings' keys are not looked at."""
+    from .warp_loss import DEFAULTS, check_settings
+    known = {"warp_weight"} | {"warp_" + k for k in DEFAULTS}
+    unknown = sorted(k for k in train if k.startswith("warp_") and k not in known)
+    if unknown:
+        raise ValueError(f"train: unknown setting(s) {unknown}; known: {sorted(known)}")
+    w = train.get("warp_weight", 0.0)
+    if not is_num(w) or w < 0:
+        raise ValueError(f"train warp_weight must be a number >= 0, got {w!r}")
+    s = check_settings({k: train["warp_" + k] for k in DEFAULTS if "warp_" + k in train})
+    return {"weight": float(w), **s}

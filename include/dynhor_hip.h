@@ -359,6 +359,83 @@ int dh_prior_loss_packed(const float* rays, const float* R, const float* t_start
                          float step, float depth_weight, float depth_delta, float normal_weight, int accumulate, float* stats,
                          float* d_weights, float* d_normal_map, void* ws, void* stream);
 
+/* Multi-view photometric consistency on the training path (DESIGN_NEXT_ROWS.md section 30): the grey patch about a ray's pixel is
+ * carried into the neighbouring frames by the homography of the plane through the ray's surface point with the rendered normal and
+ * scored by normalised cross-correlation; the mean of the best few 1 - score is the ray's loss, differentiated with respect to the
+ * ray's depth and normal.  Pixel centres are integers, x is the column, dot(a, b) = (a0 b0 + a1 b1) + a2 b2 (the conventions of
+ * dh_mvs_sweep below).  Poses and intrinsics are constants of the term.
+ *
+ * dh_ray_depth / dh_ray_depth_packed: the two sample layouts of dh_prior_loss / dh_prior_loss_packed, with its m_k.  Per ray, in
+ *   fp64 of the fp32 inputs (each lane of a wave adds its samples lane, lane + 64, .. in ascending k, then a fixed xor butterfly):
+ *   W = sum_k w_k, t = sum_k w_k m_k / W (0 when W is not > 0: a packed ray without a sample), z = t c_z with c_z = R[6] d_0 + R[7] d_1 +
+ *   R[8] d_2; t [B], wsum [B], zc [B] are those three rounded to fp32.  The depth IS divided by W: a surface point is wanted, not
+ *   an expected depth that reads near while the ray is not yet opaque.
+ *
+ * dh_warp_loss: gray, valid u8 [n_frames,H,W] (dh_match_gray); R f32 [n_frames,9], T f32 [n_frames,3]; K, Kinv f32 [9] in DEVICE
+ *   memory; nbr int32 [n_frames,n_nbr] (an entry outside [0, n_frames): none), 1 <= n_nbr <= 8; frame = the frame i of the batch;
+ *   pix int32 [B,2] = (px, py); z [B] camera depth, wsum [B], normal [B,3] = the rendered normal in the OBJECT frame (any length);
+ *   P in 1..7 (N = (2P+1)^2); min_va >= 1; min_vb > 0; topk, min_views in 1..8; min_cos in [-1, 1].  Per ray:
+ *   gate    flag 16 unless wsum >= min_wsum (a NaN fails).
+ *   source  the N grey bytes a about (px, py) of frame i; flag 1 when one lies outside the image or is invalid, or when
+ *           va = N sum a^2 - (sum a)^2 < min_va (exact integers).
+ *   plane   p = (px, py, 1) as floats, e = Kinv p, e_r = (Kinv[r][0] px + Kinv[r][1] py) + Kinv[r][2]; n_c[r] = dot(R_i row r, n);
+ *           ne = dot(n_c, e); flag 8 unless z is finite, z > 1e-3, |n_c| = sqrt(dot(n_c, n_c)) > 1e-6 and
+ *           -ne / (|n_c| sqrt(dot(e, e))) >= min_cos (a NaN fails); g = z ne.  With any flag nothing more is done.
+ *   tap     (c, r), c, r in [-P, P], row-major: x = float(px + c), y = float(py + r); u_r = (Kinv[r][0] x + Kinv[r][1] y) + Kinv[r][2];
+ *           sigma = dot(n_c, u) / g.
+ *   neighbour j = nbr[i][.]: R_ij[r][c] = dot(R_j row r, R_i row c), t_ij[r] = T_j[r] - dot(R_ij row r, T_i) (dh_mvs_sweep's);
+ *           G = K R_ij, A = G Kinv (entry [r][c] = dot(row r, column c)), b_v[r] = dot(K row r, t_ij);
+ *           h_r = ((A[r][0] x + A[r][1] y) + A[r][2]) + b_v[r] sigma; the tap needs h_2 > 1e-3; (tx, ty) = (h_0 / h_2, h_1 / h_2).
+ *           All of this is fp32, every operation an IEEE operation as written (no contraction): floor tx, floor ty can be restated
+ *           bit for bit.  The tap needs 0 <= tx < W - 1, 0 <= ty < H - 1 (a NaN fails) and its four pixels valid; wx, wy, top, bot and
+ *           the bilinear value b are dh_mvs_sweep's fp32 operations.  A failing tap makes j invalid for the ray.
+ *           sb = sum b, sb2 = sum b b, sab = sum a b are fp64 sums of the fp32 b (a lane adds its taps lane, lane + 64, .. in
+ *           ascending order, then a fixed xor butterfly); from here on everything is fp64.  vb = N sb2 - sb sb; j is invalid unless
+ *           vb >= min_vb; score_j = (N sab - sum a sb) / sqrt(va vb), l_j = 1 - score_j.
+ *   ray     valid = the number of valid neighbours; flag 2 (alone) when valid < min_views.  Else the k = min(topk, valid) smallest
+ *           l_j are chosen, the earlier entry of nbr on a tie, and l_r = their sum / k.  The sum (and those of the scores and gradients) runs
+ *           over the eight entry slots of nbr, 0 in a slot not chosen, in one fixed tree: ((s0 + s4) + (s2 + s6)) + ((s1 + s5) + (s3 + s7)).
+ *   gradient  the exact derivative at fixed floor tx, floor ty and a fixed choice: per tap s_t = d l_j / d b_t (grad b . d q / d sigma),
+ *           d l_j / d b_t = score_j (N b_t - sb) / vb - (N a_t - sum a) / sqrt(va vb), grad b = ((g01 - g00) + wy ((g11 - g10) -
+ *           (g01 - g00)), (g10 - g00) + wx ((g11 - g10) - (g01 - g00))), d q / d sigma = (b_v[0:2] - (tx, ty) b_v[2]) / h_2;
+ *           g_z = -sum_t s_t sigma_t / z, g_nc = sum_t s_t (u_t / g - sigma_t e / ne), both averaged over the chosen,
+ *           g_n = R_i^T g_nc (orthogonal to n by construction).  u_t / g - sigma_t e / ne is what is left of two nearly equal vectors:
+ *           it is formed as (u_t - rho_t e) / g with rho_t = dot(n_c, u_t) / ne, sigma_t = rho_t / z, and e, n_c, ne, g, u_t in fp64 of the
+ *           fp32 inputs; s_t is fp64 of the fp32 b_t, tx, ty, h_2.
+ *   out_f f32 [B,8] = (l_r, g_z, g_n[3], the mean score of the chosen, the best score, 0); out_i int32 [B,4] = (valid, chosen count,
+ *   flags, bitmask of the chosen entries of nbr).  A ray with a flag: (0, 0, 0, 0, 0, -2, -2, 0) and (valid, 0, flags, 0).
+ *   stats f32 [8] = (L = sum l_r / max(count, 1), count, the mean over the counted rays of the chosen's mean score, warp_weight L,
+ *   the rays with flag 1, with flag 2, with flag 8, with flag 16): fp64 sums of the per-ray fp32 values in block order, no atomics.
+ *   A ray's outputs depend on that ray's inputs alone: bitwise the same from launch to launch and for every split of the batch into
+ *   calls.  ws: dh_warp_loss_workspace(B) bytes, 16-byte aligned.  Runs on `stream` and does not wait for it.
+ *
+ * dh_ray_depth_bwd / dh_ray_depth_bwd_packed: the adjoint of z = t c_z and of the normal into the renderer's two channels, with
+ *   s = warp_weight / max(stats[1], 1) read on the device: d_weights[r,k] gets c_r (m_k - t_r), c_r = fp32(s g_z c_z / W_r), and
+ *   d_normal_map[r] gets fp32(s g_n); ray_f = dh_warp_loss's out_f, t, wsum = dh_ray_depth's.  accumulate bit 0: add to d_weights
+ *   instead of writing it, bit 1: the same for d_normal_map; when adding, a ray whose coefficient is 0 is not touched; when
+ *   writing, every sample of every ray is written, exact zeros for a ray that does not count.  Either pointer may be null.
+ *
+ * B == 0 is a no-op that writes nothing.  DH_ERR_BAD_ARG: a null or misaligned pointer, a negative count, n < 1, frame outside
+ * [0, n_frames), P outside 1..7, n_nbr, topk or min_views outside 1..8, min_va < 1, a setting that is NaN or outside its range,
+ * accumulate outside 0..3.  DH_ERR_UNSUPPORTED: max_samples > 1024, B or n_frames >= 2^31, H or W > 2^24.
+ * Limits: no occlusion test beyond the top-k choice and the validity map; the surface point is the weight-normalised expected
+ * depth, not a zero crossing; no pose or intrinsics adjoint. */
+int dh_ray_depth(const float* rays, const float* R, const float* z, const float* weights, int64_t B, int n, float sample_dist, float* t,
+                 float* wsum, float* zc, void* stream);
+int dh_ray_depth_packed(const float* rays, const float* R, const float* t_start, const float* weights, int64_t B, const int64_t* seg_off,
+                        const int32_t* seg_cnt, int max_samples, float step, float* t, float* wsum, float* zc, void* stream);
+int64_t dh_warp_loss_workspace(int64_t B);
+int dh_warp_loss(const uint8_t* gray, const uint8_t* valid, int64_t n_frames, int H, int W, const float* R, const float* T, const float* K,
+                 const float* Kinv, const int32_t* nbr, int n_nbr, int frame, const int32_t* pix, const float* z, const float* wsum,
+                 const float* normal, int64_t B, int P, int64_t min_va, float min_vb, int topk, int min_views, float min_cos,
+                 float min_wsum, float warp_weight, float* out_f, int32_t* out_i, float* stats, void* ws, void* stream);
+int dh_ray_depth_bwd(const float* rays, const float* R, const float* z, const float* t, const float* wsum, const float* ray_f,
+                     const float* stats, int64_t B, int n, float sample_dist, float warp_weight, int accumulate, float* d_weights,
+                     float* d_normal_map, void* stream);
+int dh_ray_depth_bwd_packed(const float* rays, const float* R, const float* t_start, const float* t, const float* wsum, const float* ray_f,
+                            const float* stats, int64_t B, const int64_t* seg_off, const int32_t* seg_cnt, int max_samples, float step,
+                            float warp_weight, int accumulate, float* d_weights, float* d_normal_map, void* stream);
+
 /* ---- optimiser -----------------------------------------------------------------------------------------
  * torch.optim.Adam step (upstream Runner uses Adam, App. A.8; the reference's own optimisers are Adam too:
  * ObjTracker/pose_initializtion.py:346, jointopt.py:135-141) fused over the flat vector; step counts from 1;
